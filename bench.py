@@ -20,6 +20,10 @@ Before ``--warmup`` an untimed pre-warm (``--prewarm-s``, default 0.6 s of the s
 ``prewarm_s``) brings the GPU to its sustained clocks, so a short timed region (the driver's 20 steps = 14 ms) reads
 the same as a long one.
 
+``--dump-outputs DIR`` writes what the last timed step returned (its logits; the feature images with ``--featurize-only``)
+as ``DIR/<name>.npy`` once timing is done.  Inputs and weights are seeded, so two builds run with the same arguments can
+be compared output for output.
+
 Extra objects on that line: ``roofline`` (featurise kernel vs HBM: algorithmic bytes per clip over the kernel's
 HIP-event time inside the timed region; ``traffic`` = HBM-side bytes per launch COLLECTED IN THIS RUN by child runs of
 this script under ``rocprofv3 --pmc`` (FETCH_SIZE; WRITE_SIZE; MFMA busy -- three passes, ~6 s; ``--no-live-pmc`` or a missing
@@ -60,6 +64,26 @@ DTYPE_LABEL = {
     "fp32": "f32: exact-f32 MFMA (v_mfma_f32_32x32x2_f32); featuriser f32",
 }
 SHIPPED = dict(use_pcen=False, use_pre_emphasis=False, use_delta_delta=False, use_spectral_contrast=False)
+DUMP_LIMIT_BYTES = 64 * 2**20           # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """``--dump-outputs``: write every array as ``out_dir/<name>.npy`` (float64 stays float64, anything else becomes float32).
+    Arrays that together exceed ``limit`` bytes each keep a fixed, seeded sample of their rows (axis 0; the same rows on every
+    run with the same arguments), sized in proportion to the array.  Returns ``{name: (rows written, rows computed)}``."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        n = a.shape[0] if a.ndim else 1
+        if total > limit and a.ndim and n > 0:
+            keep = int(limit * (a.nbytes / total)) // (a.nbytes // n)
+            a = a[np.sort(np.random.default_rng(0).choice(n, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (a.shape[0] if a.ndim else 1, n)
+    return written
 
 
 def measured_pmc(batch: int, variant: str) -> dict:
@@ -336,7 +360,12 @@ def parse_args(argv=None):
     ap.add_argument("--total-clips", type=int, default=0,
                     help="configs[3]: one pass over a stream of this many distinct clips (all ranks together); "
                          "overrides --steps and --rotate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (logits; features with "
+                         "--featurize-only) as DIR/<name>.npy, at most 64 MiB in all (a seeded sample of rows beyond that)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dtype == "bf16":              # the pre-r03 name of the approximate mode (argparse does not check an env default)
         print("bench.py: COUGH_BENCH_DTYPE=bf16 is the APPROXIMATE single-bf16 mode, now called bf16_approx", file=sys.stderr)
         args.dtype = "bf16_approx"
@@ -435,7 +464,7 @@ def main():
             pre.featurize_batch(wav, normalize=True, out=feats[:wav.shape[0]])
             if timed:
                 ev[i][1].record()
-            return None
+            return feats[:wav.shape[0]]
         # one C-ABI call: featurise (+ stem) -> residual blocks -> head; features are not materialised
         logits = pipe(wav, normalize=True, events=(ev[i][0], ev[i][1]) if timed else None)
         if timed:
@@ -472,7 +501,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(K):
-        step(i, True)
+        last = step(i, True)
     drain()
     torch.cuda.synchronize()
     if dist:
@@ -484,6 +513,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        if publisher is not None and last is publisher.out:
+            # the drained bucket ends with the last step's clips of all ranks, in global clip order
+            last = publisher.out[:publisher.last_n][publisher.last_n - step_total[K - 1]:]
+        name = "features" if args.featurize_only else "logits"
+        kept, rows = dump_outputs(args.dump_outputs, {name: last.cpu().numpy()})[name]
+        print(f"bench.py: wrote {os.path.join(args.dump_outputs, name + '.npy')} ({kept} of {rows} rows)", file=sys.stderr)
 
     # kernel times are quoted on full batches; a --total-clips stream shorter than one batch has only a ragged step
     full = [i for i in range(K) if batches[i].shape[0] == B] or [i for i in range(K) if batches[i].shape[0] > 0]

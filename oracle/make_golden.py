@@ -14,6 +14,10 @@ Run in the BUILD CONTAINER only (needs ``/root/reference``):
   default-init head (|w| <= 0.088, margin spread 0.014) would hide any
   reduced-precision error of the conv stack behind a near-degenerate Linear
   layer.  This is what pins ``oracle/resnet.py`` and the HIP classifier.
+* ``resnet_f64_golden.npz`` -- the same module's logits / softmax / argmax in
+  float64 on the same weights and inputs (``reference_f64``): the float32
+  logits carry ~2.5e-5 of rounding error whose exact value depends on the
+  host's conv kernels, the float64 ones pin the restatement on any host.
 * ``features_golden.npz`` -- produced by ``oracle/featurizer.py`` (the
   torch-CPU restatement; torchaudio itself is unavailable, so these vectors are
   labelled "oracle-generated", not "reference-generated") for synthetic clips
@@ -22,6 +26,7 @@ Run in the BUILD CONTAINER only (needs ``/root/reference``):
 """
 from __future__ import annotations
 
+import copy
 import importlib.util
 import os
 import sys
@@ -47,6 +52,16 @@ def load_reference_model_module():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def reference_f64(net, x) -> dict:
+    """resnet_f64_golden.npz: logits, softmax and argmax of the reference module ``net`` in float64 on the float32
+    inputs ``x``."""
+    net64 = copy.deepcopy(net).double().eval()
+    with torch.no_grad():
+        logits = net64(x.double())
+        preds, probs = net64.predict(x.double())
+    return {"logits": logits.numpy(), "probs": probs.numpy(), "preds": preds.numpy()}
 
 
 def main():
@@ -93,6 +108,7 @@ def main():
                         x=x.numpy(), a1=a1.numpy(), a2=a2.numpy(), a3=a3.numpy(),
                         logits=logits.numpy(), probs=probs.numpy(), preds=preds.numpy(),
                         **{"sd." + k: v for k, v in sd.items()})
+    np.savez_compressed(os.path.join(OUT, "resnet_f64_golden.npz"), **reference_f64(net, x))
     m = logits[:, 1] - logits[:, 0]
     print("margin std %.3f, min |margin| %.4f, max |logit| %.3f, max |fc.2.weight| %.2f"
           % (m.std(), m.abs().min(), logits.abs().max(), net.fc[2].weight.abs().max()))

@@ -141,3 +141,32 @@ def test_streaming_bench_parent_command_and_single_aggregated_line():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench_streaming.py"), "--gpus", "2"], env=env, capture_output=True,
                        text=True, timeout=120)
     assert p.returncode == 2 and p.stdout == "" and "only 1 device(s) visible" in p.stderr
+
+
+def test_steps_must_be_at_least_one():
+    """ms_per_step is elapsed / steps: zero timed steps is an argument error, not a division by zero after the run."""
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--steps", "7"]).steps == 7 and bench.parse_args([]).dump_outputs is None
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_past_the_limit(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 kept); beyond the byte limit every array keeps the same
+    seeded rows on every call, and the files stay within the limit."""
+    import numpy as np
+    small = np.arange(12, dtype=np.float16).reshape(6, 2)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"logits": small}) == {"logits": (6, 6)}
+    got = np.load(tmp_path / "a" / "logits.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+
+    big = np.random.default_rng(1).standard_normal((1000, 8))                 # 64 000 B of float64
+    other = np.arange(1000 * 4, dtype=np.float32).reshape(1000, 4)            # 16 000 B
+    limit = 40000
+    w1 = bench.dump_outputs(str(tmp_path / "b"), {"x": big, "y": other}, limit=limit)
+    w2 = bench.dump_outputs(str(tmp_path / "c"), {"x": big, "y": other}, limit=limit)
+    assert w1 == w2 and w1["x"][1] == w1["y"][1] == 1000 and 0 < w1["x"][0] < 1000 and 0 < w1["y"][0] < 1000
+    x1, x2 = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert x1.dtype == np.float64 and np.array_equal(x1, x2)
+    assert sum((tmp_path / "b" / f).stat().st_size - 128 for f in ("x.npy", "y.npy")) <= limit
+    rows = [int(np.flatnonzero((big == r).all(axis=1))[0]) for r in x1]
+    assert rows == sorted(rows)                                              # rows of the full output, in order

@@ -46,6 +46,31 @@ def test_default_line_has_every_contract_field(monkeypatch, capsys):
     assert s["bound"] == "hbm" and s["algorithmic_bytes_per_launch"] == 512 * 167828 and 0 < s["frac"] < 1
 
 
+@pytest.mark.parametrize("featurize_only", [False, True], ids=["logits", "features"])
+def test_dump_outputs_hold_what_the_last_timed_step_computed(monkeypatch, capsys, tmp_path, featurize_only):
+    """--dump-outputs: the 5th timed step of a 3-batch rotation scores batch 1 (clips 512..1023), so the file must equal a fresh
+    call of the same path on those clips with the benchmark's weights."""
+    import numpy as np
+    import bench
+    import cough_detector_amd as cda
+    from cough_detector_amd import synth
+    d = _run(monkeypatch, capsys, "--steps", "5", "--warmup", "1", "--batch", "512", "--rotate", "3", "--cpu-seconds", "0",
+             "--prewarm-s", "0", "--no-live-pmc", "--stft-launches", "1", "--dump-outputs", str(tmp_path),
+             *(["--featurize-only"] if featurize_only else []))
+    assert d["steps"] == 5
+    pre = cda.AudioPreprocessor(device="cuda", **bench.SHIPPED)
+    clips = synth.device_clips(512, 512)
+    if featurize_only:
+        got, want = np.load(tmp_path / "features.npy"), pre.featurize_batch(clips, normalize=True)
+    else:
+        model = cda.create_model("residual", n_mels=90, num_classes=2, in_channels=1, compute_dtype="bf16x3")
+        model.load_state_dict(synth.random_state_dict(seed=3))
+        model.cuda().eval()
+        got, want = np.load(tmp_path / "logits.npy"), cda.CoughPipeline(pre, model)(clips, normalize=True)
+    assert got.dtype == np.float32 and got.shape == tuple(want.shape)
+    assert np.array_equal(got, want.cpu().numpy())
+
+
 def test_short_total_clips_stream_does_not_crash(monkeypatch, capsys):
     """a --total-clips stream shorter than one batch has no full step; the line must still come out."""
     d = _run(monkeypatch, capsys, "--total-clips", "300", "--batch", "512", "--cpu-seconds", "0", "--prewarm-s", "0.05")

@@ -3,7 +3,7 @@
 set -u
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/$1; KERN=$2; shift 2
 mkdir -p "$OUT"
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 SCRIPT=$REPO/$1; shift
 ARGS=("$@")
 cd /tmp && export TMPDIR=/tmp

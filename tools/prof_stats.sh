@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel-trace stats of one python script; prints the top kernels.  Usage: bash tools/prof_stats.sh <outdir> <script.py> [args...]
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/$1; shift
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 SCRIPT=$REPO/$1; shift
 mkdir -p "$OUT"; cd /tmp && export TMPDIR=/tmp
 export COUGH_BENCH_LIVE_PMC=0   # bench.py must not start rocprofv3 children of its own under this profiler

@@ -1,6 +1,6 @@
 #!/bin/bash
 # VGPR / spill / occupancy summary of one translation unit: tools/res_usage.sh featurize.hip [extra flags]
-cd /root/repo/cough_detector_amd/csrc
+cd "$(dirname "$0")/../cough_detector_amd/csrc" || exit 1
 f=$1; shift
 hipcc -O3 -std=c++20 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -fno-slp-vectorize -fvisibility=hidden -Rpass-analysis=kernel-resource-usage "$@" -c $f -o /tmp/res_usage.o 2>&1 \
  | grep -E "Function Name|VGPRs:|AGPRs:|VGPRs Spill|Occupancy|error|warning" | sed 's/.*remark: *//;s/ *\[-Rpass[^]]*\]//g' \

@@ -1,8 +1,9 @@
 """Numerical study (CPU, float64 reference): which operand precisions keep the residual net within the 1e-3 logit tolerance.
 Result (profiles/r05_classifier_operand_precision.txt): single-f16 activations with split-f16 weights (2 MFMAs per product instead of
 3) are 2e-3..8e-3 off -- outside the tolerance; split-bf16 both sides (the shipped bf16x3) is 7e-5..2e-4.  Not built."""
-import sys, numpy as np, torch, torch.nn.functional as F
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, numpy as np, torch, torch.nn.functional as F
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/tests')
 from oracle import resnet as ores
 from parity import realistic_state_dict, synth_batch
 from oracle import featurizer as ofeat
