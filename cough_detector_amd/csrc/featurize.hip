@@ -28,6 +28,8 @@
 // PCS (PCEN values feed the stem), GEO (run-time STFT geometry at n_fft 512: hop, window, waveform length and frame count are
 // kernel arguments -- other sample rates / hops / windows / segment durations, waveforms of other lengths through any handle, and
 // the filterbanks the fixed-geometry kernels do not take: odd band counts, more than 20 MFCCs, PCEN off 64 bands).
+// Routing: plan_featurize (end of this file) decides what a call of a given waveform length runs; launch_featurize takes its
+// instantiation from K1_TABLE, and the generic kernel chain (featurize_generic.hip) serves everything else.
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -128,7 +130,7 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
     return *reinterpret_cast<uint16_t*>(&b);
 }
 // geometry of the fused stem for the 90x101 feature image (resnet.hip: stem_bf16_kernel / stem_lds)
-constexpr int ST_H = 90, ST_P1H = 22, ST_P1W = 25, ST_ROWS = 94, ST_PITCH = 106;   // image width = NFRAMES
+constexpr int ST_P1H = 22, ST_P1W = 25, ST_ROWS = 94, ST_PITCH = 106;   // image width = NFRAMES
 constexpr int ST_PER = ST_P1H * ST_P1W, ST_TILES = (ST_PER + 7) / 8;
 constexpr size_t ST_IMG = size_t(ST_ROWS) * ST_PITCH * 2;   // bytes of one bf16 image
 static_assert(ST_IMG <= LDS_MEL, "the bf16 feature image aliases the dB buffer");
@@ -1100,14 +1102,10 @@ struct cough_featurizer {
     int nbase;           // rows the featurise kernel writes (mel [+ MFCC, delta, delta-delta])
     cough::ContrastCfg contrast;   // n_bands == 0: no spectral-contrast rows
     int n_cus;           // compute units of the device the featuriser was created on
-    int kind;            // the one-launch kernel that serves the constructor's segment length: 0 none (generic chain), 1 the
-                         // shipped sparse-filterbank instantiations, 2 the full-band ones (any filterbank, run-time n_mels / n_mfcc),
-                         // 3 the full-band ones with a run-time STFT geometry (n_fft 512, hop <= 256)
-    char* d_full;        // kind 2: CSR filterbank + DCT rows (one blob)
-    cough::FullBank full;
-    size_t full_lds;     // kind 2 / 3: dynamic LDS of a workgroup at the segment length
-    bool geo_any;        // the CSR tables exist and the run-time-geometry kernel can serve this configuration: waveforms of OTHER lengths
-                         // that fit its limits (geo_fits) take it too, whatever `kind` serves the segment
+    int path;            // COUGH_PATH_*: the kernels that serve the constructor's segment length (segment_path)
+    char* d_full;        // CSR filterbank + DCT rows of the full-band / run-time-geometry kernels (one blob); nullptr when the
+                         // configuration is outside the run-time-geometry kernel's limits (geo_basic)
+    cough::FullBank full;   // pointers into d_full and the bank's sizes; plan_featurize adds a call's sample and frame count
     cough::GenFeat* gen; // the generic kernel chain's tables (featurize_generic.hip): every geometry the tuned kernel does not
                          // cover, and -- for every featuriser -- waveforms of any other length (extract_features of any N)
 };
@@ -1130,102 +1128,84 @@ bool geo_fits(const cough_feat_config& c, int n_taps, int n) {
     return covered && T <= 1024 && (!c.use_pcen || T <= 208) && (!c.use_mfcc || size_t(c.n_mfcc) * T * 4 <= LDS_XCH_FULL) &&
            full_lds_bytes(c.n_mels, n_taps, int(T)) <= 80 * 1024;
 }
-}  // namespace
-}  // namespace cough
 
-extern "C" int cough_featurizer_create(cough_featurizer** out, const cough_feat_config* cfg,
-                                       const float* window, const float* mel_fb, const float* dct) {
-    using namespace cough;
-    COUGH_REQUIRE(out && cfg && window && mel_fb && dct, COUGH_EINVAL, "cough_featurizer_create: NULL argument");
-    // The one-launch kernel serves the shipped STFT geometry (16 kHz, n_fft 512, hop 160, window 400, 1 s).  kind 1: the shipped
-    // 64-mel / 13-MFCC layout with a filterbank of <= 8 taps per band below bin 128 (any f_max <= sample_rate / 4) -- taps in
-    // registers, half the spectrum formed; kind 2: every other filterbank at that geometry (f_max up to the Nyquist bin, 2..128
-    // mel bands, up to 20 MFCCs) -- all 257 bins, CSR filterbank in LDS.  Everything else goes to the generic kernel chain
-    // (featurize_generic.hip), whose tables every featuriser carries for waveforms of other lengths.
-    const int nfreq0 = NFFT / 2 + 1;
-    // (the sample rate only shapes the filterbank, which arrives as a table: 2 s at 8 kHz or 0.5 s at 32 kHz are the same STFT)
-    const bool stft_ok = cfg->n_fft == NFFT && cfg->hop_length == HOP && cfg->win_length == WIN &&
-                         cfg->segment_samples == NS;
-    bool tuned = stft_ok && cfg->n_mels == NMEL && cfg->n_mfcc == NMFCC;
-    if (tuned) {
-        for (int m = 0; m < NMEL && tuned; ++m) {
-            int first = -1, last = -1;
-            for (int k = 0; k < nfreq0; ++k)
-                if (mel_fb[k * NMEL + m] != 0.f) { if (first < 0) first = k; last = k; }
-            if (first >= 0 && (last >= NBIN || last - first >= MAXW)) tuned = false;
-        }
-    }
-    // full-band CSR tables (kind 2)
-    std::vector<int> f_lo, f_hi, f_off;
-    std::vector<float> f_taps, f_dct;
-    FullBank fb{};
-    // kind 3: the full-band kernel with a run-time STFT geometry at n_fft = 512 -- other sample rates / hops / windows / segment
-    // lengths (geo_basic / geo_fits above), and at the shipped STFT what the fixed-geometry full-band kernels do not take: an odd
-    // number of mel bands (they store the mel rows in pairs), more than 20 MFCCs (they keep MFCC and delta rows side by side in the
-    // scratch), PCEN with another band count than 64.  Contrast rows come from the generic chain's kernels behind it.
-    const int geo_frames = cfg->hop_length > 0 ? cfg->segment_samples / cfg->hop_length + 1 : 0;
-    const bool basic = geo_basic(*cfg);
-    if (basic) {   // the CSR tables: for kinds 2 and 3, and for waveforms of other lengths on any kind
-        const int nm = cfg->n_mels, nc = cfg->use_mfcc ? cfg->n_mfcc : 1;
-        fb.n_mels = nm;
-        fb.n_mfcc = nc;
-        for (int m = 0; m < nm; ++m) {
-            int first = -1, last = -1;
-            for (int k = 0; k < nfreq0; ++k)
-                if (mel_fb[k * nm + m] != 0.f) { if (first < 0) first = k; last = k; }
-            if (first < 0) { first = 0; last = -1; }   // empty band: no taps, mel power 0
-            // the kernel reads taps and powers as aligned pairs: the band starts at an even bin and has an even number of taps
-            // (zero taps as padding; bin 257 of a power row is scratch of the frame's own finite transform, times 0)
-            const int lo2 = first & ~1, hi2 = last >= first ? (last + 2) & ~1 : lo2;
-            f_lo.push_back(lo2);
-            f_hi.push_back(hi2);
-            f_off.push_back(hi2 > lo2 ? int(f_taps.size()) : 0);   // an empty band points at a valid pair (weight 0 in the kernel)
-            for (int k = lo2; k < hi2; ++k) f_taps.push_back(k >= first && k <= last ? 0.25f * mel_fb[k * nm + m] : 0.f);   // |2X|^2 / 4
-            const int w = (hi2 - lo2 + 3) / 4 * 4;   // the kernel walks a band's taps four at a time
-            if (w > fb.maxw[m >> 6]) fb.maxw[m >> 6] = w;
-        }
-        if (f_taps.size() < 2) f_taps.assign(2, 0.f);
-        fb.n_taps = int(f_taps.size());
-        fb.cph = (nc + 1) / 2;
-        const int n_chunks = (fb.cph + 6) / 7;
-        fb.cw = (fb.cph + n_chunks - 1) / n_chunks;   // 7 coefficients per half -> one chunk of 7; 10 -> two of 5; 11 -> two of 6
-        if (fb.cw < 4) fb.cw = 4;
-        fb.cph_pad = (fb.cph + fb.cw - 1) / fb.cw * fb.cw;
-        const int chunks_per_half = fb.cph_pad / fb.cw;
-        f_dct.assign(size_t(2) * chunks_per_half * nm * 8, 0.f);
-        if (cfg->use_mfcc)
-            for (int c = 0; c < nc; ++c) {
-                const int half = c >= fb.cph, r = half ? c - fb.cph : c;
-                for (int m = 0; m < nm; ++m)
-                    f_dct[((size_t(half) * chunks_per_half + r / fb.cw) * nm + m) * 8 + r % fb.cw] = dct[m * nc + c];
+// Every featurize_kernel instantiation, one per (PRE_EMPH, STEM, FULL, TALL, PCS, GEO) a plan can launch: launch_featurize picks
+// its kernel here and cough_featurizer_create gives the FULL entries their 80 KB dynamic-LDS attribute.
+using K1Fn = decltype(&featurize_kernel<false, 0>);
+struct K1Entry {
+    bool pe;
+    int stem;
+    bool full, tall, pcs, geo;
+    K1Fn fn;
+};
+#define K1(PE, STEM, FULL, TALL, PCS, GEO) {PE, STEM, FULL, TALL, PCS, GEO, featurize_kernel<PE, STEM, FULL, TALL, PCS, GEO>}
+#define K1_X3(FULL, PCS) K1(false, 2, FULL, false, PCS, false), K1(false, 2, FULL, true, PCS, false), \
+                        K1(true, 2, FULL, false, PCS, false), K1(true, 2, FULL, true, PCS, false)
+const K1Entry K1_TABLE[] = {   // (in the order of the device code: the FULL entries first)
+    K1(false, 0, true, false, false, false), K1(true, 0, true, false, false, false),   // full-band
+    K1_X3(true, false), K1_X3(true, true),                                             // full-band, split-bf16 stem: 90 / 103 rows
+    K1(false, 0, true, false, false, true), K1(true, 0, true, false, false, true),     // run-time STFT geometry
+    K1_X3(false, false), K1_X3(false, true),                                           // shipped, split-bf16 stem
+    K1(false, 1, false, false, false, false),   // shipped, single-bf16 stem: 90 rows, no pre-emphasis / PCEN
+    K1(true, 0, false, false, false, false), K1(false, 0, false, false, false, false),   // shipped
+};
+#undef K1_X3
+#undef K1
+static_assert(sizeof(K1_TABLE) / sizeof(K1_TABLE[0]) == 23, "one entry per instantiation");
+K1Fn k1_kernel(bool pe, int stem, bool full, bool tall, bool pcs, bool geo) {
+    for (const K1Entry& k : K1_TABLE)
+        if (k.pe == pe && k.stem == stem && k.full == full && k.tall == tall && k.pcs == pcs && k.geo == geo) return k.fn;
+    return nullptr;
+}
+
+// The shipped STFT geometry of the fixed-geometry instantiations and the persistent STFT kernel (16 kHz, n_fft 512, hop 160,
+// window 400, 1 s).  The sample rate only shapes the filterbank, which arrives as a table: 2 s at 8 kHz are the same STFT.
+bool shipped_stft(const cough_feat_config& c) {
+    return c.n_fft == NFFT && c.hop_length == HOP && c.win_length == WIN && c.segment_samples == NS;
+}
+struct Band {
+    int first, last;   // first / last non-zero bin of a mel band; first = -1: an empty band
+};
+std::vector<Band> scan_bands(const cough_feat_config& c, const float* mel_fb) {   // mel_fb: [257][n_mels] at n_fft 512
+    std::vector<Band> bands(c.n_fft == NFFT && c.n_mels > 0 ? c.n_mels : 0, Band{-1, -1});
+    for (int k = 0; !bands.empty() && k <= NFFT / 2; ++k)
+        for (int m = 0; m < c.n_mels; ++m)
+            if (mel_fb[k * c.n_mels + m] != 0.f) {
+                if (bands[m].first < 0) bands[m].first = k;
+                bands[m].last = k;
             }
-        fb.n_samples = cfg->segment_samples;
-        fb.hop = cfg->hop_length;
-    }
-    bool fixed_full = !tuned && basic && stft_ok && cfg->n_mels % 2 == 0 && (!cfg->use_mfcc || cfg->n_mfcc <= FULL_MAX_MFCC) &&
-                      (!cfg->use_pcen || cfg->n_mels == NMEL) &&
-                      full_lds_bytes(cfg->n_mels, fb.n_taps, NFRAMES) <= 80 * 1024;   // at least two workgroups per CU
-    if (cfg->use_spectral_contrast) {
-        COUGH_REQUIRE(cfg->n_contrast_bands >= 1 && cfg->n_contrast_bands <= COUGH_MAX_CONTRAST_BANDS, COUGH_EUNSUPPORTED,
-                      "n_contrast_bands = %d: the HIP path takes 1..%d", cfg->n_contrast_bands, COUGH_MAX_CONTRAST_BANDS);
-        for (int i = 0; i <= cfg->n_contrast_bands; ++i) {
-            const int lo = cfg->contrast_edges[i], hi = cfg->contrast_edges[i + 1];
-            COUGH_REQUIRE(lo >= 0 && lo < cfg->n_fft / 2 + 1 && (i == cfg->n_contrast_bands || hi - lo <= 1024),
-                          COUGH_EUNSUPPORTED, "spectral-contrast band %d = bins [%d, %d): the HIP path takes bands of <= 1024 bins "
-                          "inside the spectrum", i, lo, hi);
-            // the contrast kernel behind the persistent STFT passes (shipped geometry) selects out of bands of <= 128 bins
-            if (i < cfg->n_contrast_bands && hi - lo > 128 && stft_ok) tuned = fixed_full = false;
-        }
-    }
-    const bool geo_seg = !tuned && !fixed_full && basic && geo_fits(*cfg, fb.n_taps, cfg->segment_samples);
-    fb.n_frames = geo_seg ? geo_frames : NFRAMES;
-    std::vector<FeatTables> host(1);
-    FeatTables& t = host[0];
-    std::memset(&t, 0, sizeof(t));
+    return bands;
+}
+
+// The kernels that serve the segment (cough_featurizer_path).  TUNED: the shipped 64-mel / 13-MFCC layout at the shipped STFT with
+// a filterbank of <= 8 taps per band below bin 128 (any f_max <= sample_rate / 4) -- taps in registers, half the spectrum formed.
+// TUNED_FULLBAND: every other filterbank at that geometry (f_max up to the Nyquist bin, an even number of mel bands <= 128, up to 20
+// MFCCs, PCEN at 64 bands) -- all 257 bins, CSR filterbank in LDS.  TUNED_GEOMETRY: the full-band kernel with a run-time STFT
+// geometry at n_fft 512 (geo_basic / geo_fits) -- other sample rates / hops / windows / segment lengths, and what the fixed-geometry
+// full-band kernels do not take at the shipped STFT.  A contrast band wider than 128 bins leaves the shipped STFT (the contrast kernel
+// behind the persistent STFT passes selects out of <= 128 bins).  Everything else: the generic kernel chain (featurize_generic.hip).
+int segment_path(const cough_feat_config& c, const std::vector<Band>& bands, int n_taps) {
+    bool stft = shipped_stft(c);
+    for (int i = 0; c.use_spectral_contrast && i < c.n_contrast_bands; ++i)
+        stft = stft && c.contrast_edges[i + 1] - c.contrast_edges[i] <= 128;
+    bool regs = stft && c.n_mels == NMEL && c.n_mfcc == NMFCC;
+    for (const Band& b : bands) regs = regs && (b.first < 0 || (b.last < NBIN && b.last - b.first < MAXW));
+    if (regs) return COUGH_PATH_TUNED;
+    const bool basic = geo_basic(c);
+    if (stft && basic && c.n_mels % 2 == 0 && (!c.use_mfcc || c.n_mfcc <= FULL_MAX_MFCC) && (!c.use_pcen || c.n_mels == NMEL) &&
+        full_lds_bytes(c.n_mels, n_taps, NFRAMES) <= 80 * 1024)   // at least two workgroups per CU
+        return COUGH_PATH_TUNED_FULLBAND;
+    return basic && geo_fits(c, n_taps, c.segment_samples) ? COUGH_PATH_TUNED_GEOMETRY : COUGH_PATH_GENERIC;
+}
+
+// The STFT tables of the one-launch kernels and of the persistent STFT kernel (spectrogram.hip); TUNED: register taps and DCT rows
+FeatTables shipped_tables(const cough_feat_config& c, const float* window, const float* mel_fb, const float* dct,
+                          const std::vector<Band>& bands, int path) {
+    FeatTables t{};
     const double PI = 3.14159265358979323846;
-    if (stft_ok || basic) {   // the STFT tables of the one-launch kernels and of the persistent STFT kernel (spectrogram.hip)
-        const int left = (NFFT - cfg->win_length) / 2;   // torch.stft centres a short window in the frame
-        for (int n = 0; n < cfg->win_length; ++n) t.win[left + n] = window[n];
+    if (shipped_stft(c) || geo_basic(c)) {
+        const int left = (NFFT - c.win_length) / 2;   // torch.stft centres a short window in the frame
+        for (int n = 0; n < c.win_length; ++n) t.win[left + n] = window[n];
         for (int jj = 0; jj < 16; ++jj)
             for (int k1 = 0; k1 < 16; ++k1) {
                 const double a = -2.0 * PI * double(jj * k1) / 256.0;
@@ -1236,87 +1216,133 @@ extern "C" int cough_featurizer_create(cough_featurizer** out, const cough_feat_
             t.tw512[k] = make_float2(float(std::cos(a)), float(std::sin(a)));
         }
     }
-    if (tuned) {
-        const int nfreq = NFFT / 2 + 1;
+    if (path == COUGH_PATH_TUNED) {
         for (int m = 0; m < NMEL; ++m) {
-            int first = -1;
-            for (int k = 0; k < nfreq && first < 0; ++k)
-                if (mel_fb[k * NMEL + m] != 0.f) first = k;
-            if (first < 0) first = 0;   // empty band: all-zero taps
-            if (first > NBIN - MAXW) first = NBIN - MAXW;   // keep start+8 inside the power buffer
+            int first = bands[m].first < 0 ? 0 : bands[m].first;   // empty band: all-zero taps
+            if (first > NBIN - MAXW) first = NBIN - MAXW;          // keep start+8 inside the power buffer
             t.mel_start[m] = first;
             for (int q = 0; q < MAXW; ++q) t.mel_w[m][q] = 0.25f * mel_fb[(first + q) * NMEL + m];   // |2X|^2 / 4
         }
-        for (int c = 0; c < NMFCC; ++c)
-            for (int m = 0; m < NMEL; ++m) t.dct_t[c][m] = dct[m * NMFCC + c];
-        for (int m = 0; m < NMEL; ++m) t.dct_t[NMFCC][m] = 0.f;
+        for (int c2 = 0; c2 < NMFCC; ++c2)
+            for (int m = 0; m < NMEL; ++m) t.dct_t[c2][m] = dct[m * NMFCC + c2];
     }
+    return t;
+}
+
+// The CSR filterbank and DCT chunks of the full-band / run-time-geometry kernels, on the host (upload packs them into one blob)
+struct HostBank {
+    FullBank fb{};
+    std::vector<int> lo, hi, off;
+    std::vector<float> taps, dct;
+};
+HostBank csr_bank(const cough_feat_config& c, const float* mel_fb, const float* dct, const std::vector<Band>& bands) {
+    HostBank h;
+    FullBank& fb = h.fb;
+    const int nm = c.n_mels, nc = c.use_mfcc ? c.n_mfcc : 1;
+    fb.n_mels = nm;
+    fb.n_mfcc = nc;
+    for (int m = 0; m < nm; ++m) {
+        const int first = bands[m].first < 0 ? 0 : bands[m].first, last = bands[m].first < 0 ? -1 : bands[m].last;   // empty: no taps
+        // the kernel reads taps and powers as aligned pairs: the band starts at an even bin and has an even number of taps
+        // (zero taps as padding; bin 257 of a power row is scratch of the frame's own finite transform, times 0)
+        const int lo2 = first & ~1, hi2 = last >= first ? (last + 2) & ~1 : lo2;
+        h.lo.push_back(lo2);
+        h.hi.push_back(hi2);
+        h.off.push_back(hi2 > lo2 ? int(h.taps.size()) : 0);   // an empty band points at a valid pair (weight 0 in the kernel)
+        for (int k = lo2; k < hi2; ++k) h.taps.push_back(k >= first && k <= last ? 0.25f * mel_fb[k * nm + m] : 0.f);   // |2X|^2 / 4
+        const int w = (hi2 - lo2 + 3) / 4 * 4;   // the kernel walks a band's taps four at a time
+        if (w > fb.maxw[m >> 6]) fb.maxw[m >> 6] = w;
+    }
+    if (h.taps.size() < 2) h.taps.assign(2, 0.f);
+    fb.n_taps = int(h.taps.size());
+    fb.cph = (nc + 1) / 2;
+    const int n_chunks = (fb.cph + 6) / 7;
+    fb.cw = (fb.cph + n_chunks - 1) / n_chunks;   // 7 coefficients per half -> one chunk of 7; 10 -> two of 5; 11 -> two of 6
+    if (fb.cw < 4) fb.cw = 4;
+    fb.cph_pad = (fb.cph + fb.cw - 1) / fb.cw * fb.cw;
+    const int chunks_per_half = fb.cph_pad / fb.cw;
+    h.dct.assign(size_t(2) * chunks_per_half * nm * 8, 0.f);
+    if (c.use_mfcc)
+        for (int k = 0; k < nc; ++k) {
+            const int half = k >= fb.cph, r = half ? k - fb.cph : k;
+            for (int m = 0; m < nm; ++m)
+                h.dct[((size_t(half) * chunks_per_half + r / fb.cw) * nm + m) * 8 + r % fb.cw] = dct[m * nc + k];
+        }
+    fb.hop = c.hop_length;
+    return h;
+}
+
+// Device copies of the tables and the per-device kernel attributes, on the creator's device
+hipError_t upload(cough_featurizer* f, const FeatTables& t, const HostBank* bank) {
+    std::vector<float> hann(NFFT);   // torch.hann_window(n_fft, periodic=True)
+    for (int n = 0; n < NFFT; ++n) hann[n] = float(0.5 - 0.5 * std::cos(2.0 * 3.14159265358979323846 * double(n) / double(NFFT)));
+    hipError_t e = hipMalloc(&f->d_tables, sizeof(FeatTables));
+    if (e == hipSuccess) e = hipMemcpy(f->d_tables, &t, sizeof(FeatTables), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&f->d_win_full, NFFT * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(f->d_win_full, hann.data(), NFFT * sizeof(float), hipMemcpyHostToDevice);
+    // the persistent STFT kernel's 162 KB of dynamic LDS
+    if (e == hipSuccess && stft_prepare_device(&f->n_cus) != COUGH_OK) e = hipErrorUnknown;
+    if (e != hipSuccess || !bank) return e;
+    // one blob: lo | hi | off (ints), taps, DCT rows; every piece 16-byte aligned
+    auto al = [](size_t v) { return (v + 15) & ~size_t(15); };
+    const size_t nm = bank->lo.size(), o_hi = al(nm * 4), o_off = o_hi + al(nm * 4), o_w = o_off + al(nm * 4),
+                 o_dct = o_w + al(bank->taps.size() * 4), total = o_dct + al(bank->dct.size() * 4);
+    std::vector<char> blob(total, 0);
+    std::memcpy(blob.data(), bank->lo.data(), nm * 4);
+    std::memcpy(blob.data() + o_hi, bank->hi.data(), nm * 4);
+    std::memcpy(blob.data() + o_off, bank->off.data(), nm * 4);
+    std::memcpy(blob.data() + o_w, bank->taps.data(), bank->taps.size() * 4);
+    std::memcpy(blob.data() + o_dct, bank->dct.data(), bank->dct.size() * 4);
+    e = hipMalloc(&f->d_full, total);
+    if (e == hipSuccess) e = hipMemcpy(f->d_full, blob.data(), total, hipMemcpyHostToDevice);
+    f->full.lo = reinterpret_cast<const int*>(f->d_full);
+    f->full.hi = reinterpret_cast<const int*>(f->d_full + o_hi);
+    f->full.off = reinterpret_cast<const int*>(f->d_full + o_off);
+    f->full.w = reinterpret_cast<const float*>(f->d_full + o_w);
+    f->full.dct = reinterpret_cast<const float*>(f->d_full + o_dct);
+    // more than 64 KB of dynamic LDS with many mel bands: per-device attribute, set here (not lazily at launch)
+    for (const K1Entry& k : K1_TABLE)
+        if (k.full && e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    return e;
+}
+}  // namespace
+}  // namespace cough
+
+extern "C" int cough_featurizer_create(cough_featurizer** out, const cough_feat_config* cfg,
+                                       const float* window, const float* mel_fb, const float* dct) {
+    using namespace cough;
+    COUGH_REQUIRE(out && cfg && window && mel_fb && dct, COUGH_EINVAL, "cough_featurizer_create: NULL argument");
+    if (cfg->use_spectral_contrast) {
+        COUGH_REQUIRE(cfg->n_contrast_bands >= 1 && cfg->n_contrast_bands <= COUGH_MAX_CONTRAST_BANDS, COUGH_EUNSUPPORTED,
+                      "n_contrast_bands = %d: the HIP path takes 1..%d", cfg->n_contrast_bands, COUGH_MAX_CONTRAST_BANDS);
+        for (int i = 0; i <= cfg->n_contrast_bands; ++i) {
+            const int lo = cfg->contrast_edges[i], hi = cfg->contrast_edges[i + 1];
+            COUGH_REQUIRE(lo >= 0 && lo < cfg->n_fft / 2 + 1 && (i == cfg->n_contrast_bands || hi - lo <= 1024),
+                          COUGH_EUNSUPPORTED, "spectral-contrast band %d = bins [%d, %d): the HIP path takes bands of <= 1024 bins "
+                          "inside the spectrum", i, lo, hi);
+        }
+    }
+    const std::vector<Band> bands = scan_bands(*cfg, mel_fb);
+    const bool basic = geo_basic(*cfg);   // the CSR tables: for the full-band paths, and for waveforms of other lengths on any path
+    const HostBank bank = basic ? csr_bank(*cfg, mel_fb, dct, bands) : HostBank{};
+    const int path = segment_path(*cfg, bands, bank.fb.n_taps);
+    const FeatTables t = shipped_tables(*cfg, window, mel_fb, dct, bands, path);
     GenFeat* gen = nullptr;
     if (int e = gen_feat_create(&gen, cfg, window, mel_fb, dct)) return e;
 
     cough_featurizer* f = new cough_featurizer();
     f->cfg = *cfg;
     f->gen = gen;
-    f->kind = tuned ? 1 : fixed_full ? 2 : geo_seg ? 3 : 0;
-    f->d_full = nullptr;
-    f->full = fb;
-    f->full_lds = fixed_full || geo_seg ? full_lds_bytes(fb.n_mels, fb.n_taps, fb.n_frames) : 0;
-    f->geo_any = basic;
+    f->path = path;
+    f->full = bank.fb;
     f->nbase = cfg->use_mfcc ? cfg->n_mels + 2 * cfg->n_mfcc + (cfg->use_delta_delta ? cfg->n_mfcc : 0) : cfg->n_mels;
     f->nfeat = f->nbase + (cfg->use_spectral_contrast ? cfg->n_contrast_bands + 1 : 0);
     f->contrast.n_bands = cfg->use_spectral_contrast ? cfg->n_contrast_bands : 0;
     for (int i = 0; i < 18; ++i) f->contrast.edges[i] = cfg->contrast_edges[i];
-    f->d_tables = nullptr;
-    f->d_win_full = nullptr;
-    std::vector<float> hann(NFFT);   // torch.hann_window(n_fft, periodic=True)
-    for (int n = 0; n < NFFT; ++n) hann[n] = float(0.5 - 0.5 * std::cos(2.0 * PI * double(n) / double(NFFT)));
-    hipError_t e = hipMalloc(&f->d_tables, sizeof(FeatTables));
-    if (e == hipSuccess) e = hipMemcpy(f->d_tables, &t, sizeof(FeatTables), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&f->d_win_full, NFFT * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(f->d_win_full, hann.data(), NFFT * sizeof(float), hipMemcpyHostToDevice);
-    // per-device kernel attributes (the persistent STFT kernel's 162 KB of dynamic LDS) on the creator's device
-    if (e == hipSuccess && stft_prepare_device(&f->n_cus) != COUGH_OK) e = hipErrorUnknown;
-    if (e == hipSuccess && basic) {
-        // one blob: lo | hi | off (ints), taps, DCT rows; every piece 16-byte aligned
-        auto al = [](size_t v) { return (v + 15) & ~size_t(15); };
-        const size_t nm = size_t(fb.n_mels), o_hi = al(nm * 4), o_off = o_hi + al(nm * 4), o_w = o_off + al(nm * 4),
-                     o_dct = o_w + al(f_taps.size() * 4), total = o_dct + al(f_dct.size() * 4);
-        std::vector<char> blob(total, 0);
-        std::memcpy(blob.data(), f_lo.data(), nm * 4);
-        std::memcpy(blob.data() + o_hi, f_hi.data(), nm * 4);
-        std::memcpy(blob.data() + o_off, f_off.data(), nm * 4);
-        std::memcpy(blob.data() + o_w, f_taps.data(), f_taps.size() * 4);
-        std::memcpy(blob.data() + o_dct, f_dct.data(), f_dct.size() * 4);
-        e = hipMalloc(&f->d_full, total);
-        if (e == hipSuccess) e = hipMemcpy(f->d_full, blob.data(), total, hipMemcpyHostToDevice);
-        f->full.lo = reinterpret_cast<const int*>(f->d_full);
-        f->full.hi = reinterpret_cast<const int*>(f->d_full + o_hi);
-        f->full.off = reinterpret_cast<const int*>(f->d_full + o_off);
-        f->full.w = reinterpret_cast<const float*>(f->d_full + o_w);
-        f->full.dct = reinterpret_cast<const float*>(f->d_full + o_dct);
-        // more than 64 KB of dynamic LDS with many mel bands: per-device attribute, set here (not lazily at launch)
-        const void* fns[] = {reinterpret_cast<const void*>(featurize_kernel<false, 0, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 0, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<false, 2, true, false>),
-                             reinterpret_cast<const void*>(featurize_kernel<false, 2, true, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 2, true, false>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 2, true, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<false, 2, true, false, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<false, 2, true, true, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 2, true, false, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 2, true, true, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<false, 0, true, false, false, true>),
-                             reinterpret_cast<const void*>(featurize_kernel<true, 0, true, false, false, true>)};
-        for (const void* fn : fns)
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    }
-    if (e != hipSuccess) {
+    if (const hipError_t e = upload(f, t, basic ? &bank : nullptr); e != hipSuccess) {
         set_error("cough_featurizer_create: %s", hipGetErrorString(e));
-        if (f->d_full) (void)hipFree(f->d_full);
-        if (f->d_tables) (void)hipFree(f->d_tables);
-        if (f->d_win_full) (void)hipFree(f->d_win_full);
-        gen_feat_destroy(f->gen);
-        delete f;
+        cough_featurizer_destroy(f);
         return COUGH_EHIP;
     }
     *out = f;
@@ -1339,7 +1365,7 @@ extern "C" void cough_featurizer_destroy(cough_featurizer* f) {
 }
 
 extern "C" int cough_featurizer_num_features(const cough_featurizer* f) { return f ? f->nfeat : -1; }
-extern "C" int cough_featurizer_path(const cough_featurizer* f) { return f ? f->kind : -1; }
+extern "C" int cough_featurizer_path(const cough_featurizer* f) { return f ? f->path : -1; }
 extern "C" int cough_featurizer_num_frames(const cough_featurizer* f) { return !f ? -1 : cough::gen_frames(f->gen, 0); }
 extern "C" int cough_featurizer_num_frames_for(const cough_featurizer* f, int n_samples) {
     return !f || n_samples < 0 ? -1 : cough::gen_frames(f->gen, n_samples);
@@ -1354,33 +1380,31 @@ StftView featurizer_stft_view(const cough_featurizer* f) {
 }
 int featurizer_num_features(const cough_featurizer* f) { return f->nfeat; }
 const GenFeat* featurizer_generic(const cough_featurizer* f) { return f->gen; }
-bool featurizer_tuned(const cough_featurizer* f, int n_samples) {
-    return f->kind != 0 && (n_samples <= 0 || n_samples == f->cfg.segment_samples);
-}
-// Which kernels featurise waveforms of n_samples (0: the segment): 1 the handle's own one-launch kernel (kind 1 / 2 / 3 at the segment
-// length), 3 the run-time-geometry instantiation at ANOTHER length that fits its limits, 0 the generic kernel chain.
-static int featurizer_route(const cough_featurizer* f, int n_samples) {
-    if (n_samples <= 0 || n_samples == f->cfg.segment_samples) return f->kind != 0 ? 1 : 0;
-    return f->geo_any && geo_fits(f->cfg, f->full.n_taps, n_samples) ? 3 : 0;
-}
-bool featurizer_shipped_stft(const cough_featurizer* f, int n_samples) {   // the persistent STFT kernel's geometry
-    return (f->kind == 1 || f->kind == 2) && (n_samples <= 0 || n_samples == NS);
-}
-bool featurizer_stem_fusable(const cough_featurizer* f, bool x3) {
-    // a one-launch kernel writing the whole image (no contrast rows), 64 mel + 13 MFCC rows
-    if (f->kind == 0 || f->kind == 3 || f->cfg.n_mels != NMEL || f->cfg.n_mfcc != NMFCC || !f->cfg.use_mfcc || f->nfeat != f->nbase)
-        return false;
-    // split-bf16 stem: the 90-row layout, or the 103-row layout of the delta-delta flag (two halves); shipped or full-band
-    // filterbank, with or without pre-emphasis / PCEN.  The approximate single-bf16 stem exists for the shipped 90-row set only.
-    if (x3) return f->nfeat == ST_H || (f->nfeat == ST_H + NMFCC && f->cfg.use_delta_delta);
-    return f->nfeat == ST_H && f->kind == 1 && !f->cfg.use_pre_emphasis && !f->cfg.use_pcen;
-}
-size_t featurizer_workspace_bytes(const cough_featurizer* f, int n_clips, int n_samples) {
-    const int route = featurizer_route(f, n_samples);
-    if (route == 0) return gen_workspace_bytes(f->gen, f->cfg, n_samples, n_clips);
-    if (f->contrast.n_bands == 0 || n_clips <= 0) return 0;
-    // contrast rows: behind the persistent STFT passes (shipped geometry), else by the generic chain's kernels
-    return route == 3 || f->kind == 3 ? gen_workspace_bytes(f->gen, f->cfg, n_samples, n_clips) : contrast_workspace_bytes(n_clips);
+
+FeatPlan plan_featurize(const cough_featurizer* f, int n_samples, int n_clips) {
+    const cough_feat_config& c = f->cfg;
+    const bool segment = n_samples <= 0 || n_samples == c.segment_samples;
+    FeatPlan p{};
+    // another length: the run-time-geometry kernel when it fits its limits (the CSR tables exist), else the generic chain
+    p.path = segment ? f->path
+             : f->d_full && geo_fits(c, f->full.n_taps, n_samples) ? COUGH_PATH_TUNED_GEOMETRY : COUGH_PATH_GENERIC;
+    p.n_samples = segment ? c.segment_samples : n_samples;
+    p.n_frames = gen_frames(f->gen, p.n_samples);
+    p.shipped_stft = p.path == COUGH_PATH_TUNED || p.path == COUGH_PATH_TUNED_FULLBAND;
+    p.lds = p.path == COUGH_PATH_TUNED    ? LDS_TOTAL
+            : p.path == COUGH_PATH_GENERIC ? 0
+                                           : full_lds_bytes(f->full.n_mels, f->full.n_taps, p.n_frames);
+    p.contrast = f->contrast.n_bands == 0 ? FEAT_CONTRAST_NONE : p.shipped_stft ? FEAT_CONTRAST_STFT : FEAT_CONTRAST_GENERIC;
+    if (n_clips > 0 && (p.path == COUGH_PATH_GENERIC || p.contrast == FEAT_CONTRAST_GENERIC))
+        p.workspace = gen_workspace_bytes(f->gen, c, n_samples, n_clips);
+    else if (n_clips > 0 && p.contrast == FEAT_CONTRAST_STFT)
+        p.workspace = contrast_workspace_bytes(n_clips);
+    // the fused stem: a fixed-geometry kernel writing the whole image (no contrast rows) of 64 mel + 13 MFCC rows -- the 90-row
+    // layout, or the 103-row one of the delta-delta flag (split-bf16 only, in two halves); the single-bf16 stem for the shipped
+    // 90-row set only
+    p.stem_x3 = p.shipped_stft && p.contrast == FEAT_CONTRAST_NONE && c.n_mels == NMEL && c.use_mfcc && c.n_mfcc == NMFCC;
+    p.stem_bf16 = p.stem_x3 && p.path == COUGH_PATH_TUNED && !c.use_delta_delta && !c.use_pre_emphasis && !c.use_pcen;
+    return p;
 }
 
 int launch_featurize(const cough_featurizer* f, const float* d_wav, long long wav_stride, float* d_feat, int n_clips,
@@ -1388,96 +1412,61 @@ int launch_featurize(const cough_featurizer* f, const float* d_wav, long long wa
                      int n_samples) {
     COUGH_REQUIRE(f && d_wav && (d_feat || stem), COUGH_EINVAL, "cough_featurize: NULL argument");
     COUGH_REQUIRE(n_clips >= 0 && n_samples >= 0, COUGH_EINVAL, "cough_featurize: n_clips < 0 or n_samples < 0");
-    const int route = featurizer_route(f, n_samples);
-    const bool geo_launch = route == 3 || (route == 1 && f->kind == 3);   // the run-time-geometry instantiation runs
-    if (route == 0) {
+    const FeatPlan p = plan_featurize(f, n_samples, n_clips);
+    const int norm = (flags & COUGH_FEAT_NORMALIZE) ? 1 : 0;
+    if (p.path == COUGH_PATH_GENERIC) {   // the chain checks its geometry, stride and workspace before its first launch
         COUGH_REQUIRE(!stem, COUGH_EUNSUPPORTED, "the fused stem needs the shipped 90-row feature layout");
         if (n_clips == 0) return COUGH_OK;
-        return gen_featurize(f->gen, f->cfg, f->contrast, d_wav, wav_stride, n_samples, d_feat, f->nfeat, f->nbase, n_clips,
-                             (flags & COUGH_FEAT_NORMALIZE) ? 1 : 0, d_workspace, workspace_bytes, stream);
+        return gen_featurize(f->gen, f->cfg, f->contrast, d_wav, wav_stride, n_samples, d_feat, f->nfeat, f->nbase, n_clips, norm,
+                             d_workspace, workspace_bytes, stream);
     }
-    const int n_wave = route == 3 ? n_samples : f->cfg.segment_samples;   // samples per clip of this launch
-    if (geo_launch)
-        COUGH_REQUIRE(wav_stride >= n_wave, COUGH_EINVAL, "cough_featurize: row stride %lld < %d samples", wav_stride, n_wave);
-    else
+    if (p.shipped_stft)
         COUGH_REQUIRE(wav_stride >= NS && (wav_stride & 3) == 0 && (reinterpret_cast<size_t>(d_wav) & 15) == 0,
                       COUGH_EINVAL, "cough_featurize: d_wav must be 16-byte aligned with a row stride >= 16000, multiple of 4");
-    COUGH_REQUIRE(!stem || (route == 1 && featurizer_stem_fusable(f, stem->x3 != 0)), COUGH_EUNSUPPORTED,
+    else
+        COUGH_REQUIRE(wav_stride >= p.n_samples, COUGH_EINVAL, "cough_featurize: row stride %lld < %d samples", wav_stride, p.n_samples);
+    COUGH_REQUIRE(!stem || (stem->x3 ? p.stem_x3 : p.stem_bf16), COUGH_EUNSUPPORTED,
                   "the fused stem needs the shipped 90-row feature layout");
     if (n_clips == 0) return COUGH_OK;
-    const int norm = (flags & COUGH_FEAT_NORMALIZE) ? 1 : 0;
-    const int rows = (f->cfg.use_mfcc ? (f->cfg.use_delta_delta ? 1 : 0) : 2);   // kernel row selector
-    const dim3 grid(n_clips), block(THREADS);
-    const StemFuse none{nullptr, nullptr, nullptr, 0, nullptr};
-    const FullBank nofb{};
-    // spectral-contrast rows under the fused normalise: the featurise kernel leaves every clip's peak for the contrast path
-    float* peak_out = nullptr;
-    if (f->contrast.n_bands > 0 && norm && !geo_launch) {
-        COUGH_REQUIRE(d_workspace && workspace_bytes >= contrast_workspace_bytes(n_clips), COUGH_EWORKSPACE,
-                      "spectral contrast needs a workspace of cough_featurizer_workspace_bytes() bytes (cough_featurize_ws)");
-        peak_out = contrast_peaks(d_workspace, n_clips);
-    } else if (f->contrast.n_bands > 0 && norm) {   // run-time geometry: the generic chain's layout, peaks of the call at its head
-        COUGH_REQUIRE(d_workspace && workspace_bytes >= gen_workspace_bytes(f->gen, f->cfg, n_samples, n_clips) &&
-                          (reinterpret_cast<size_t>(d_workspace) & 255) == 0,
-                      COUGH_EWORKSPACE, "spectral contrast needs a 256-byte aligned workspace of "
-                      "cough_featurizer_workspace_bytes() bytes (cough_featurize_ws)");
-        peak_out = static_cast<float*>(d_workspace);
+    // the contrast rows' workspace, whatever the normalize flag: nothing is launched before it is known to be usable
+    COUGH_REQUIRE(!p.workspace || (d_workspace && workspace_bytes >= p.workspace), COUGH_EWORKSPACE,
+                  "spectral contrast needs a workspace of cough_featurizer_workspace_bytes() bytes (cough_featurize_ws)");
+    COUGH_REQUIRE(!p.workspace || (reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL,
+                  "workspace must be 256-byte aligned");
+    const bool full = p.path != COUGH_PATH_TUNED, pe = f->cfg.use_pre_emphasis != 0;
+    const K1Fn kernel = k1_kernel(pe, stem ? (stem->x3 ? 2 : 1) : 0, full, stem && f->cfg.use_delta_delta, stem && f->cfg.use_pcen,
+                                  p.path == COUGH_PATH_TUNED_GEOMETRY);
+    COUGH_REQUIRE(kernel, COUGH_EUNSUPPORTED, "cough_featurize: no featurize_kernel instantiation for this configuration");
+    FullBank bank{};   // TUNED: the register taps of d_tables instead
+    if (full) {
+        bank = f->full;
+        bank.n_samples = p.n_samples;
+        bank.n_frames = p.n_frames;
     }
-    // one instantiation per (pre-emphasis, stem, full-band filterbank, 103-row stem); everything else is a run-time argument
-    const bool full = f->kind >= 2 || geo_launch, pe = f->cfg.use_pre_emphasis != 0;
-    FullBank geo_bank = f->full;   // another waveform length: the same tables, its own frame count
-    if (route == 3) {
-        geo_bank.n_samples = n_samples;
-        geo_bank.n_frames = n_samples / f->cfg.hop_length + 1;
-    }
-    const size_t lds = route == 3 ? full_lds_bytes(geo_bank.n_mels, geo_bank.n_taps, geo_bank.n_frames) : full ? f->full_lds : LDS_TOTAL;
-    const FullBank& fbk = route == 3 ? geo_bank : full ? f->full : nofb;
-    const float* fdct = full ? f->full.dct : nullptr;
-    auto go = [&](auto kernel, const StemFuse& sf, int pcen) {
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, d_wav, wav_stride, d_feat, f->nfeat, f->d_tables, norm,
-                           f->cfg.pre_emphasis_coef, rows, pcen, sf, fbk, fdct, peak_out);
-    };
-    if (stem && stem->x3) {   // split-bf16 stem fused (90-row image, or the 103-row image of the delta-delta flag in two halves)
-        const bool tall = f->cfg.use_delta_delta != 0;
-        const int sel = (f->cfg.use_pcen ? 8 : 0) | (pe ? 4 : 0) | (full ? 2 : 0) | (tall ? 1 : 0);
-        switch (sel) {
-#define K1_CASE(N, PE, FU, TA, PC) case N: go(featurize_kernel<PE, 2, FU, TA, PC>, *stem, PC ? 1 : 0); break;
-            K1_CASE(0, false, false, false, false) K1_CASE(1, false, false, true, false) K1_CASE(2, false, true, false, false)
-            K1_CASE(3, false, true, true, false) K1_CASE(4, true, false, false, false) K1_CASE(5, true, false, true, false)
-            K1_CASE(6, true, true, false, false) K1_CASE(7, true, true, true, false) K1_CASE(8, false, false, false, true)
-            K1_CASE(9, false, false, true, true) K1_CASE(10, false, true, false, true) K1_CASE(11, false, true, true, true)
-            K1_CASE(12, true, false, false, true) K1_CASE(13, true, false, true, true) K1_CASE(14, true, true, false, true)
-            default: go(featurize_kernel<true, 2, true, true, true>, *stem, 1); break;
-#undef K1_CASE
-        }
-    } else if (stem) {        // approximate single-bf16 stem: shipped filterbank, no pre-emphasis (featurizer_stem_fusable)
-        go(featurize_kernel<false, 1>, *stem, 0);
-    } else if (geo_launch) {   // run-time STFT geometry
-        if (pe) go(featurize_kernel<true, 0, true, false, false, true>, none, f->cfg.use_pcen);
-        else go(featurize_kernel<false, 0, true, false, false, true>, none, f->cfg.use_pcen);
-    } else if (full) {
-        if (pe) go(featurize_kernel<true, 0, true>, none, f->cfg.use_pcen);
-        else go(featurize_kernel<false, 0, true>, none, f->cfg.use_pcen);
-    } else {
-        if (pe) go(featurize_kernel<true, 0>, none, f->cfg.use_pcen);
-        else go(featurize_kernel<false, 0>, none, f->cfg.use_pcen);
-    }
+    // under the fused normalise the kernel leaves every clip's peak where the contrast rows' strategy reads it
+    float* peaks = !norm || p.contrast == FEAT_CONTRAST_NONE ? nullptr
+                   : p.contrast == FEAT_CONTRAST_STFT        ? contrast_peaks(d_workspace, n_clips)
+                                                             : gen_peaks(d_workspace);
+    const int rows = f->cfg.use_mfcc ? (f->cfg.use_delta_delta ? 1 : 0) : 2;   // kernel row selector
+    hipLaunchKernelGGL(kernel, dim3(n_clips), dim3(THREADS), p.lds, stream, d_wav, wav_stride, d_feat, f->nfeat, f->d_tables, norm,
+                       f->cfg.pre_emphasis_coef, rows, f->cfg.use_pcen, stem ? *stem : StemFuse{}, bank, bank.dct, peaks);
     COUGH_HIP_CHECK(hipGetLastError());
-    if (f->contrast.n_bands > 0 && geo_launch)   // run-time geometry: the generic chain's STFT + contrast kernels add the rows
-        return gen_featurize(f->gen, f->cfg, f->contrast, d_wav, wav_stride, n_samples, d_feat, f->nfeat, f->nbase, n_clips, norm,
-                             d_workspace, workspace_bytes, stream, /*contrast_rows_only=*/true);
-    if (f->contrast.n_bands > 0)   // rows [nbase, nfeat): from the un-emphasised signal (preprocessing.py:476-478)
-        return launch_contrast(featurizer_stft_view(f), f->contrast, d_wav, wav_stride, d_feat, f->nfeat, f->nbase,
-                               n_clips, norm, d_workspace, workspace_bytes, stream);
+    // rows [nbase, nfeat): from the un-emphasised signal (preprocessing.py:476-478)
+    if (p.contrast == FEAT_CONTRAST_GENERIC)
+        return gen_contrast(f->gen, f->contrast, d_wav, wav_stride, n_samples, d_feat, f->nfeat, f->nbase, n_clips, norm, d_workspace,
+                            workspace_bytes, stream);
+    if (p.contrast == FEAT_CONTRAST_STFT)
+        return launch_contrast(featurizer_stft_view(f), f->contrast, d_wav, wav_stride, d_feat, f->nfeat, f->nbase, n_clips, norm,
+                               d_workspace, workspace_bytes, stream);
     return COUGH_OK;
 }
 }  // namespace cough
 
 extern "C" size_t cough_featurizer_workspace_bytes(const cough_featurizer* f, int n_clips) {
-    return f ? cough::featurizer_workspace_bytes(f, n_clips) : 0;
+    return f ? cough::plan_featurize(f, 0, n_clips).workspace : 0;
 }
 extern "C" size_t cough_featurizer_workspace_bytes_for(const cough_featurizer* f, int n_samples, int n_clips) {
-    return f && n_samples >= 0 ? cough::featurizer_workspace_bytes(f, n_clips, n_samples) : 0;
+    return f && n_samples >= 0 ? cough::plan_featurize(f, n_samples, n_clips).workspace : 0;
 }
 extern "C" int cough_featurize_any(const cough_featurizer* f, const float* d_wav, long long wav_stride, int n_samples,
                                    float* d_feat, int n_clips, int flags, void* d_workspace, size_t workspace_bytes, void* stream) {

@@ -1003,7 +1003,6 @@ void gen_feat_destroy(GenFeat* g) {
     delete g;
 }
 
-int gen_segment_samples(const GenFeat* g) { return g->N; }
 // frames of torch.stft(center=True) for a waveform of n_samples (0: the constructor's segment): n / hop + 1 for an even n_fft
 // (get_expected_time_frames(), :532-534), one sample less of signal for an odd one
 int gen_frames(const GenFeat* g, int n_samples) {
@@ -1020,7 +1019,7 @@ bool contrast_in_stft(const GenFeat* g, int n_bands, const int* edges) {
 }
 struct GenCarve {
     int sub;                 // clips per sub-batch
-    size_t o_peaks, o_stat, o_P, o_M, o_mel, total;
+    size_t o_stat, o_P, o_M, o_mel, total;
 };
 GenCarve gen_carve(const GenFeat* g, bool contrast, int T, int n_clips) {
     GenCarve c;
@@ -1031,8 +1030,7 @@ GenCarve gen_carve(const GenFeat* g, bool contrast, int T, int n_clips) {
     if (sub > 32768) sub = 32768;   // grid.y
     if (sub > size_t(n_clips)) sub = size_t(n_clips);
     c.sub = int(sub);
-    c.o_peaks = 0;   // one peak per clip of the CALL (the one-launch kernel leaves them for the contrast rows of a run-time geometry)
-    c.o_stat = c.o_peaks + align256g(size_t(n_clips) * 4);
+    c.o_stat = align256g(size_t(n_clips) * 4);   // behind one peak per clip of the CALL (gen_peaks)
     c.o_P = c.o_stat + align256g(sub * 16);
     c.o_M = c.o_P + (contrast ? align256g(sub * spec) : 0);
     c.o_mel = c.o_M + (contrast ? align256g(sub * spec) : 0);
@@ -1061,9 +1059,20 @@ int gen_spectrogram(const GenFeat* g, const float* d_wav, long long wav_stride, 
     return COUGH_OK;
 }
 
-int gen_featurize(const GenFeat* g, const cough_feat_config& cfg, const ContrastCfg& contrast, const float* d_wav,
-                  long long wav_stride, int n_samples, float* d_feat, int nfeat, int nbase, int n_clips, int normalize,
-                  void* d_workspace, size_t workspace_bytes, hipStream_t stream, bool contrast_rows_only) {
+namespace {
+// One featurise call on the generic chain: geometry, workspace carve, stream.  gen_call checks the call before anything is launched.
+struct GenCall {
+    const GenFeat* g;
+    int N, T;                // samples / frames per clip
+    long long wav_stride;
+    int nfeat;
+    bool narrow;             // contrast rows straight out of the STFT workgroups' tiles (contrast_in_stft)
+    GenCarve c;
+    char* ws;
+    hipStream_t stream;
+};
+int gen_call(GenCall& k, const GenFeat* g, const ContrastCfg& contrast, long long wav_stride, int n_samples, int nfeat, int n_clips,
+             void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
     const int N = n_samples > 0 ? n_samples : g->N, T = gen_frames(g, N);
     COUGH_REQUIRE(N > g->nfft / 2, COUGH_EINVAL, "cough_featurize: %d samples: the reflect padding of torch.stft(center=True) needs "
                   "more than n_fft / 2 = %d", N, g->nfft / 2);
@@ -1075,59 +1084,92 @@ int gen_featurize(const GenFeat* g, const cough_feat_config& cfg, const Contrast
                   "this featuriser geometry runs on the generic kernel chain and needs a workspace of "
                   "cough_featurizer_workspace_bytes() = %zu bytes (cough_featurize_ws)", c.total);
     COUGH_REQUIRE((reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL, "workspace must be 256-byte aligned");
-    char* ws = static_cast<char*>(d_workspace);
-    float* peaks = reinterpret_cast<float*>(ws + c.o_peaks);
-    float* stat = reinterpret_cast<float*>(ws + c.o_stat);
-    float* P = reinterpret_cast<float*>(ws + c.o_P);
-    float* M = reinterpret_cast<float*>(ws + c.o_M);
-    float* mel = reinterpret_cast<float*>(ws + c.o_mel);
-    const int n_mels = g->n_mels, n_mfcc = g->n_mfcc;
-    for (int c0 = 0; c0 < n_clips; c0 += c.sub) {
-        const int nc = n_clips - c0 < c.sub ? n_clips - c0 : c.sub;
+    k = GenCall{g, N, T, wav_stride, nfeat, narrow, c, static_cast<char*>(d_workspace), stream};
+    return COUGH_OK;
+}
+
+// rows [0, nbase) of the sub-batch's nc clips (waveforms from w, image from feat); pk: their peaks, nullptr without normalise
+void gen_base_rows(const GenCall& k, const cough_feat_config& cfg, const float* w, int nc, float* feat, const float* pk) {
+    const GenFeat* g = k.g;
+    const int T = k.T, n_mels = g->n_mels, n_mfcc = g->n_mfcc;
+    float* stat = reinterpret_cast<float*>(k.ws + k.c.o_stat);
+    float* mel = reinterpret_cast<float*>(k.ws + k.c.o_mel);
+    const dim3 gt((T + G_TT - 1) / G_TT, nc);
+    // STFT + mel projection in one kernel: the power spectrogram of the (pre-emphasised) signal is never materialised
+    const GenMel gm{n_mels, g->mel_lo, g->mel_hi, g->mel_off, g->mel_w, g->n_taps};
+    gen_launch_stft<false, true>(g, k.N, T, w, k.wav_stride, nc, g->win, pk, cfg.use_pre_emphasis, cfg.pre_emphasis_coef, mel, gm,
+                                 k.stream);
+    hipLaunchKernelGGL(gen_dbstat_kernel, dim3(nc), dim3(256), 0, k.stream, mel, T, n_mels, cfg.use_pcen, stat);
+    hipLaunchKernelGGL(gen_rows_kernel, gt, dim3(256), size_t(n_mels) * G_TT * sizeof(float), k.stream, mel, T, n_mels,
+                       cfg.use_mfcc ? n_mfcc : 0, cfg.use_pcen, stat, g->dct_t, feat, k.nfeat);
+    if (cfg.use_mfcc) {
+        hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, k.stream, feat, k.nfeat, T, n_mels, n_mfcc);
+        hipLaunchKernelGGL(gen_delta_kernel, dim3((n_mfcc * T + 255) / 256, nc), dim3(256), 0, k.stream, feat, k.nfeat, T, n_mels,
+                           n_mfcc, cfg.use_delta_delta);
+    }
+}
+
+// rows [nbase, nfeat) of the sub-batch: spectral contrast + centroid from the un-emphasised (normalised) signal (:476-478).  pk: the
+// clips' peaks (a NaN sample is not in them -- v_max drops NaNs -- but poisons its frames, and the joint z-score of the rows spreads
+// that over the clip)
+void gen_contrast_rows(const GenCall& k, const ContrastCfg& contrast, const float* w, int nc, float* feat, int nbase, const float* pk) {
+    const GenFeat* g = k.g;
+    const int T = k.T;
+    const GenMel none{0, nullptr, nullptr, nullptr, nullptr, 0};
+    if (k.narrow) {   // n_fft = 512: rows straight out of the STFT workgroups' tiles
+        const long long n_rows = (long long)nc * T;
+        const dim3 gs((unsigned)((n_rows + G_FPB * G_CHUNK - 1) / (G_FPB * G_CHUNK)));
+        const GenTail tail{contrast, g->freqs, float(g->sample_rate) / 2.0f, k.nfeat, nbase};
+        hipLaunchKernelGGL((gen_stft_kernel<false, false, 1>), gs, dim3(256), 0, k.stream, w, k.wav_stride, k.N, g->hop, T, g->win,
+                           g->tw256, g->tw512, pk, 0.f, feat, none, n_rows, tail);
+        hipLaunchKernelGGL((gen_stft_kernel<true, false, 2>), gs, dim3(256), 0, k.stream, w, k.wav_stride, k.N, g->hop, T, g->win_full,
+                           g->tw256, g->tw512, pk, 0.f, feat, none, n_rows, tail);
+        hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, k.stream, feat, k.nfeat, T, nbase, contrast.n_bands + 1);
+        return;
+    }
+    float* P = reinterpret_cast<float*>(k.ws + k.c.o_P);
+    float* M = reinterpret_cast<float*>(k.ws + k.c.o_M);
+    gen_launch_stft<false, false>(g, k.N, T, w, k.wav_stride, nc, g->win, pk, 0, 0.f, P, none, k.stream);
+    gen_launch_stft<true, false>(g, k.N, T, w, k.wav_stride, nc, g->win_full, pk, 0, 0.f, M, none, k.stream);
+    bool wide = false;   // a band of more than 128 bins (n_fft = 2048 only) ranks its bins out of LDS
+    for (int i = 0; i < contrast.n_bands; ++i) wide |= contrast.edges[i + 1] - contrast.edges[i] > G_CT_BINS;
+    const dim3 gt((T + G_TT - 1) / G_TT, nc);
+    hipLaunchKernelGGL(gen_contrast_kernel, dim3(gt.x, gt.y, contrast.n_bands + 1), dim3(64),
+                       wide ? size_t(G_CT_BINS / 4 * G_TT) * sizeof(float4) : 0, k.stream, P, M, T, g->nfreq, contrast, g->freqs,
+                       float(g->sample_rate) / 2.0f, feat, k.nfeat, nbase);
+    hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, k.stream, feat, k.nfeat, T, nbase, contrast.n_bands + 1);
+}
+}  // namespace
+
+float* gen_peaks(void* d_workspace) { return static_cast<float*>(d_workspace); }   // the head of the carve: [n_clips] of the call
+
+int gen_featurize(const GenFeat* g, const cough_feat_config& cfg, const ContrastCfg& contrast, const float* d_wav,
+                  long long wav_stride, int n_samples, float* d_feat, int nfeat, int nbase, int n_clips, int normalize,
+                  void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+    GenCall k;
+    if (int e = gen_call(k, g, contrast, wav_stride, n_samples, nfeat, n_clips, d_workspace, workspace_bytes, stream)) return e;
+    float* peaks = normalize ? gen_peaks(d_workspace) : nullptr;   // the sub-batch's clips
+    for (int c0 = 0; c0 < n_clips; c0 += k.c.sub) {
+        const int nc = n_clips - c0 < k.c.sub ? n_clips - c0 : k.c.sub;
         const float* w = d_wav + (long long)c0 * wav_stride;
-        float* feat = d_feat + (long long)c0 * nfeat * T;
-        // contrast_rows_only: the featurise kernel has left every clip's peak at the head of the workspace (a NaN sample is not in
-        // it -- v_max drops NaNs -- but poisons its frames, and the joint z-score of the rows spreads that over the clip)
-        const float* pk = normalize ? (contrast_rows_only ? peaks + c0 : peaks) : nullptr;
-        if (normalize && !contrast_rows_only)
-            hipLaunchKernelGGL(gen_peak_kernel, dim3(nc), dim3(256), 0, stream, w, wav_stride, N, peaks);
-        const dim3 gt((T + G_TT - 1) / G_TT, nc);
-        // STFT + mel projection in one kernel: the power spectrogram of the (pre-emphasised) signal is never materialised
-        const GenMel gm{n_mels, g->mel_lo, g->mel_hi, g->mel_off, g->mel_w, g->n_taps}, none{0, nullptr, nullptr, nullptr, nullptr, 0};
-        if (!contrast_rows_only) {   // (else the one-launch kernel has written rows [0, nbase): featurize.hip, run-time geometry)
-        gen_launch_stft<false, true>(g, N, T, w, wav_stride, nc, g->win, pk, cfg.use_pre_emphasis, cfg.pre_emphasis_coef, mel, gm, stream);
-        hipLaunchKernelGGL(gen_dbstat_kernel, dim3(nc), dim3(256), 0, stream, mel, T, n_mels, cfg.use_pcen, stat);
-        hipLaunchKernelGGL(gen_rows_kernel, gt, dim3(256), size_t(n_mels) * G_TT * sizeof(float), stream, mel, T, n_mels, cfg.use_mfcc ? n_mfcc : 0, cfg.use_pcen, stat,
-                           g->dct_t, feat, nfeat);
-        if (cfg.use_mfcc) {
-            hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, stream, feat, nfeat, T, n_mels, n_mfcc);
-            hipLaunchKernelGGL(gen_delta_kernel, dim3((n_mfcc * T + 255) / 256, nc), dim3(256), 0, stream, feat, nfeat, T, n_mels,
-                               n_mfcc, cfg.use_delta_delta);
-        }
-        }
-        if (want_contrast) {
-            // from the un-emphasised (normalised) signal (:476-478)
-            if (narrow) {   // n_fft = 512: rows straight out of the STFT workgroups' tiles
-                const long long n_rows = (long long)nc * T;
-                const dim3 gs((unsigned)((n_rows + G_FPB * G_CHUNK - 1) / (G_FPB * G_CHUNK)));
-                const GenTail tail{contrast, g->freqs, float(g->sample_rate) / 2.0f, nfeat, nbase};
-                hipLaunchKernelGGL((gen_stft_kernel<false, false, 1>), gs, dim3(256), 0, stream, w, wav_stride, N, g->hop, T, g->win,
-                                   g->tw256, g->tw512, pk, 0.f, feat, none, n_rows, tail);
-                hipLaunchKernelGGL((gen_stft_kernel<true, false, 2>), gs, dim3(256), 0, stream, w, wav_stride, N, g->hop, T, g->win_full,
-                                   g->tw256, g->tw512, pk, 0.f, feat, none, n_rows, tail);
-                hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, stream, feat, nfeat, T, nbase, contrast.n_bands + 1);
-                COUGH_HIP_CHECK(hipGetLastError());
-                continue;
-            }
-            gen_launch_stft<false, false>(g, N, T, w, wav_stride, nc, g->win, pk, 0, 0.f, P, none, stream);
-            gen_launch_stft<true, false>(g, N, T, w, wav_stride, nc, g->win_full, pk, 0, 0.f, M, none, stream);
-            bool wide = false;   // a band of more than 128 bins (n_fft = 2048 only) ranks its bins out of LDS
-            for (int i = 0; i < contrast.n_bands; ++i) wide |= contrast.edges[i + 1] - contrast.edges[i] > G_CT_BINS;
-            hipLaunchKernelGGL(gen_contrast_kernel, dim3(gt.x, gt.y, contrast.n_bands + 1), dim3(64),
-                               wide ? size_t(G_CT_BINS / 4 * G_TT) * sizeof(float4) : 0, stream, P, M, T, g->nfreq, contrast, g->freqs,
-                               float(g->sample_rate) / 2.0f, feat, nfeat, nbase);
-            hipLaunchKernelGGL(gen_zscore_kernel, dim3(nc), dim3(256), 0, stream, feat, nfeat, T, nbase, contrast.n_bands + 1);
-        }
+        float* feat = d_feat + (long long)c0 * nfeat * k.T;
+        if (peaks) hipLaunchKernelGGL(gen_peak_kernel, dim3(nc), dim3(256), 0, stream, w, wav_stride, k.N, peaks);
+        gen_base_rows(k, cfg, w, nc, feat, peaks);
+        if (contrast.n_bands > 0) gen_contrast_rows(k, contrast, w, nc, feat, nbase, peaks);
+        COUGH_HIP_CHECK(hipGetLastError());
+    }
+    return COUGH_OK;
+}
+
+int gen_contrast(const GenFeat* g, const ContrastCfg& contrast, const float* d_wav, long long wav_stride, int n_samples, float* d_feat,
+                 int nfeat, int nbase, int n_clips, int normalize, void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+    GenCall k;
+    if (int e = gen_call(k, g, contrast, wav_stride, n_samples, nfeat, n_clips, d_workspace, workspace_bytes, stream)) return e;
+    const float* peaks = normalize ? gen_peaks(d_workspace) : nullptr;   // every clip of the call, left by the one-launch kernel
+    for (int c0 = 0; c0 < n_clips; c0 += k.c.sub) {
+        const int nc = n_clips - c0 < k.c.sub ? n_clips - c0 : k.c.sub;
+        gen_contrast_rows(k, contrast, d_wav + (long long)c0 * wav_stride, nc, d_feat + (long long)c0 * nfeat * k.T, nbase,
+                          peaks ? peaks + c0 : nullptr);
         COUGH_HIP_CHECK(hipGetLastError());
     }
     return COUGH_OK;

@@ -19,14 +19,27 @@ struct StemFuse {
     int* nanflag;            // [n]: 1 = the clip holds a non-finite sample -- the reference's image, and so its logits, are NaN
 };
 
-// featurize.hip: d_feat may be nullptr when `stem` is given (features not materialised)
-// n_samples: length of every waveform row (0 = the constructor's segment; another length runs on the generic chain)
+// featurize.hip: what one featurise call of waveforms of n_samples (0: the constructor's segment) runs.  plan_featurize alone
+// decides it; launch_featurize, the workspace queries, cough_spectrogram_any and the fused pipeline (resnet.hip) read it.
+enum { FEAT_CONTRAST_NONE, FEAT_CONTRAST_STFT, FEAT_CONTRAST_GENERIC };
+struct FeatPlan {
+    int path;                // COUGH_PATH_*: the kernels that write rows [0, nbase)
+    int contrast;            // rows [nbase, nfeat): none / launch_contrast behind the persistent STFT passes / the generic chain's
+                             // kernels (gen_contrast behind the one-launch kernel; gen_featurize itself on COUGH_PATH_GENERIC)
+    int n_samples, n_frames; // per clip of this call
+    size_t lds;              // dynamic LDS of the one-launch kernel
+    size_t workspace;        // bytes the call needs (0: none)
+    bool shipped_stft;       // the fixed-geometry kernels (TUNED / TUNED_FULLBAND): 16-byte aligned rows, stride a multiple of 4
+                             // and >= 16000; the persistent STFT kernel serves the spectrogram
+    bool stem_x3, stem_bf16; // the classifier's stem can be fused: split-bf16 / single-bf16 operands
+};
+FeatPlan plan_featurize(const cough_featurizer* f, int n_samples = 0, int n_clips = 0);
+// d_feat may be nullptr when `stem` is given (features not materialised).  Every argument, the workspace included, is checked before
+// the first launch.
 int launch_featurize(const cough_featurizer* f, const float* d_wav, long long wav_stride, float* d_feat, int n_clips,
                      int flags, const StemFuse* stem, hipStream_t stream, void* d_workspace = nullptr,
                      size_t workspace_bytes = 0, int n_samples = 0);
-size_t featurizer_workspace_bytes(const cough_featurizer* f, int n_clips, int n_samples = 0);
 int featurizer_num_features(const cough_featurizer* f);
-bool featurizer_stem_fusable(const cough_featurizer* f, bool x3);   // 90-row layout on a one-launch kernel, no pre-emphasis / PCEN
 
 // Device tables of a featuriser that the stand-alone STFT (spectrogram.hip) shares.
 struct StftView {
@@ -50,22 +63,24 @@ int launch_contrast(const StftView& v, const ContrastCfg& cfg, const float* d_wa
 // spectrogram.hip: per-device set-up of the persistent STFT kernel (its 162 KB dynamic-LDS attribute) on the CURRENT
 // device + that device's CU count; cough_featurizer_create calls it
 int stft_prepare_device(int* n_cus);
-// featurize_generic.hip: the kernel chain for every geometry the tuned featurise kernel does not cover (n_fft = 512)
+// featurize_generic.hip: the kernel chain for every call the one-launch kernel does not serve (COUGH_PATH_GENERIC), and the
+// contrast rows behind the run-time-geometry kernel
 struct GenFeat;
 int gen_feat_create(GenFeat** out, const cough_feat_config* cfg, const float* window, const float* mel_fb, const float* dct);
 void gen_feat_destroy(GenFeat* g);
 // the tables hold for waveforms of ANY length: n_samples is a launch parameter (0 = the constructor's segment)
 int gen_frames(const GenFeat* g, int n_samples);
-int gen_segment_samples(const GenFeat* g);
 size_t gen_workspace_bytes(const GenFeat* g, const cough_feat_config& cfg, int n_samples, int n_clips);
 int gen_spectrogram(const GenFeat* g, const float* d_wav, long long wav_stride, int n_samples, float* d_spec, int n_clips, int flags,
                     hipStream_t stream);
 int gen_featurize(const GenFeat* g, const cough_feat_config& cfg, const ContrastCfg& contrast, const float* d_wav,
                   long long wav_stride, int n_samples, float* d_feat, int nfeat, int nbase, int n_clips, int normalize,
-                  void* d_workspace, size_t workspace_bytes, hipStream_t stream, bool contrast_rows_only = false);
+                  void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+// rows [nbase, nfeat) alone, behind the one-launch kernel, which leaves the peaks under normalise at gen_peaks(d_workspace)
+int gen_contrast(const GenFeat* g, const ContrastCfg& contrast, const float* d_wav, long long wav_stride, int n_samples, float* d_feat,
+                 int nfeat, int nbase, int n_clips, int normalize, void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+float* gen_peaks(void* d_workspace);   // [n_clips] inside a gen_workspace_bytes() workspace: per-clip max |sample|
 const GenFeat* featurizer_generic(const cough_featurizer* f);   // every featuriser has the generic chain's tables
-bool featurizer_tuned(const cough_featurizer* f, int n_samples = 0);   // the one-launch kernel serves waveforms of this length
-bool featurizer_shipped_stft(const cough_featurizer* f, int n_samples = 0);   // ... at the shipped STFT geometry (persistent STFT kernel)
 int launch_stft(const StftView& v, const float* d_wav, long long wav_stride, float* d_spec, int n_clips, int flags,
                 hipStream_t stream);
 

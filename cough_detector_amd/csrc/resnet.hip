@@ -1419,8 +1419,8 @@ extern "C" int cough_resnet_read_activation(const cough_resnet* m, const void* d
 namespace cough {
 namespace {
 bool can_fuse_stem(const cough_featurizer* f, const cough_resnet* m) {
-    return !m->gen && (m->dtype == COUGH_DTYPE_BF16 || m->dtype == COUGH_DTYPE_BF16X3) && featurizer_stem_fusable(f, m->dtype == COUGH_DTYPE_BF16X3) &&
-           cough_featurizer_num_frames(f) == 101;
+    const FeatPlan p = plan_featurize(f);
+    return !m->gen && (m->dtype == COUGH_DTYPE_BF16X3 ? p.stem_x3 : m->dtype == COUGH_DTYPE_BF16 && p.stem_bf16);
 }
 }  // namespace
 }  // namespace cough
@@ -1431,7 +1431,7 @@ extern "C" size_t cough_pipeline_workspace_bytes(const cough_featurizer* f, cons
     const int H = featurizer_num_features(f), W = cough_featurizer_num_frames(f);
     size_t b = cough_resnet_workspace_bytes(m, n_clips, H, W);
     if (!can_fuse_stem(f, m)) b += align256(size_t(n_clips) * H * W * sizeof(float));   // feature scratch
-    return b + align256(featurizer_workspace_bytes(f, n_clips));                          // spectral-contrast scratch
+    return b + align256(plan_featurize(f, 0, n_clips).workspace);                         // spectral-contrast scratch
 }
 
 extern "C" int cough_pipeline_forward(const cough_featurizer* f, const cough_resnet* m, const float* d_wav,
@@ -1463,7 +1463,7 @@ extern "C" int cough_pipeline_forward(const cough_featurizer* f, const cough_res
     const size_t feat_bytes = align256(size_t(n_clips) * H * W * sizeof(float));
     float* feat = d_feat ? d_feat : reinterpret_cast<float*>(ws + net_bytes);
     if (int e = launch_featurize(f, d_wav, wav_stride, feat, n_clips, flags, nullptr, st, ws + net_bytes + feat_bytes,
-                                 featurizer_workspace_bytes(f, n_clips)))
+                                 plan_featurize(f, 0, n_clips).workspace))
         return e;
     if (ev_featurize_end) COUGH_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev_featurize_end), st));
     if (m->gen) return gen_forward(m->gen, feat, n_clips, H, W, d_logits, d_probs, d_preds, ws, st);

@@ -240,10 +240,31 @@ def test_runtime_geometry_more_clips_than_one_sub_batch():
     assert (f[32990:].cpu() - ref).abs().max().item() < 2e-4
 
 
+SENTINEL = -7.0
+
+
+def _bad_workspaces(base, need):
+    """Missing, one byte short, not 256-byte aligned."""
+    return (dict(wsp=None, wsb=0), dict(wsb=need - 1), dict(wsp=base + 4))
+
+
+def _fails_untouched(call, out, match, **kw):
+    """The call returns an error code whose message names `match` and leaves `out` as it was: nothing was launched."""
+    from cough_detector_amd import _lib
+    out.fill_(SENTINEL)
+    rc = call(**kw)
+    torch.cuda.synchronize()
+    assert rc != _lib.OK and match.encode() in _lib.load().cough_amd_last_error(), (kw, rc)
+    with pytest.raises((RuntimeError, ValueError), match=match):
+        _lib.check(rc, "cough_featurize_any")
+    assert torch.all(out == SENTINEL), f"{kw}: rows written before the error"
+    return rc
+
+
 def test_raw_c_abi_argument_errors_on_the_runtime_geometry_path():
-    """cough_featurize_any on a run-time-geometry handle with contrast rows: a missing / short / misaligned workspace and a row
-    stride below the segment length come back as error codes with a message (ValueError / RuntimeError through _lib.check),
-    never as a launch."""
+    """cough_featurize_any on a run-time-geometry handle with contrast rows: a missing / short / misaligned workspace (with or
+    without normalize) and a row stride below the segment length come back as error codes with a message (ValueError /
+    RuntimeError through _lib.check), never as a launch."""
     from cough_detector_amd import _lib
     flags = {**SHIPPED, "use_spectral_contrast": True, "n_contrast_bands": 2}
     pre = cda.AudioPreprocessor(device="cuda", segment_duration=0.5, **BASE, **flags)
@@ -262,15 +283,38 @@ def test_raw_c_abi_argument_errors_on_the_runtime_geometry_path():
         return lib.cough_featurize_any(h, w.data_ptr(), stride, n, out.data_ptr(), b, flags_, wsp, wsb, st)
     assert call() == _lib.OK
     good = out.clone()
-    for kw in (dict(wsp=None, wsb=0), dict(wsb=need - 1), dict(wsp=base + 4)):
-        rc = call(**kw)
-        assert rc != _lib.OK and b"workspace" in lib.cough_amd_last_error()
-        with pytest.raises((RuntimeError, ValueError), match="workspace"):
-            _lib.check(rc, "cough_featurize_any")
-    rc = call(stride=n - 1)
-    assert rc == _lib.EINVAL and b"stride" in lib.cough_amd_last_error()
+    for flags_ in (_lib.FEAT_NORMALIZE, 0):                               # the contrast rows need the workspace either way
+        for kw in _bad_workspaces(base, need):
+            _fails_untouched(call, out, "workspace", flags_=flags_, **kw)
+    assert _fails_untouched(call, out, "stride", stride=n - 1) == _lib.EINVAL
     assert call(flags_=0) == _lib.OK                                      # without normalize the peaks are not needed: still fine
     assert call() == _lib.OK and torch.equal(out, good)                   # and the handle is unharmed
+
+
+def test_raw_c_abi_workspace_errors_on_the_shipped_geometry_path_launch_nothing():
+    """The same on a shipped-geometry handle with contrast rows (the persistent STFT kernel's contrast path): a missing / short /
+    misaligned workspace fails before the featurise kernel writes a row, with normalize on or off."""
+    from cough_detector_amd import _lib
+    pre = cda.AudioPreprocessor(device="cuda", **BASE, **{**SHIPPED, "use_spectral_contrast": True, "n_contrast_bands": 2})
+    assert pre.kernel_path() == "tuned"
+    lib, h = _lib.load(), pre._native()
+    b, n = 6, 16000
+    w = torch.randn(b, n, device="cuda")
+    out = torch.empty(b, pre.get_num_features(), 101, device="cuda")
+    need = lib.cough_featurizer_workspace_bytes_for(h, n, b)
+    assert need > 0
+    ws = torch.empty(need + 512, dtype=torch.uint8, device="cuda")
+    base = ws.data_ptr() + (-ws.data_ptr()) % 256
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(wsp=base, wsb=need, flags_=_lib.FEAT_NORMALIZE):
+        return lib.cough_featurize_any(h, w.data_ptr(), n, n, out.data_ptr(), b, flags_, wsp, wsb, st)
+    for flags_ in (_lib.FEAT_NORMALIZE, 0):
+        assert call(flags_=flags_) == _lib.OK
+        good = out.clone()
+        for kw in _bad_workspaces(base, need):
+            _fails_untouched(call, out, "workspace", flags_=flags_, **kw)
+        assert call(flags_=flags_) == _lib.OK and torch.equal(out, good)
 
 
 def test_other_waveform_lengths_through_one_handle_take_the_one_launch_kernel_too():
