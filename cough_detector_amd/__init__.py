@@ -6,8 +6,9 @@ from .model import (CoughDetector, CoughDetectorResidual, CoughDetectorSmall, Co
                     count_parameters)
 from .inference import CoughDetectorInference, RealtimeQueueDetector
 from .pipeline import CoughPipeline
+from .augmentation import AudioAugmentor, MixUp, SpecAugment, create_augmentation_pipeline
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
            "ResidualBlock", "create_model", "count_parameters", "CoughDetectorInference", "RealtimeQueueDetector",
-           "CoughPipeline"]
+           "CoughPipeline", "AudioAugmentor", "MixUp", "SpecAugment", "create_augmentation_pipeline"]

@@ -49,6 +49,7 @@ SYMBOLS = (
     "cough_pipeline_workspace_bytes", "cough_pipeline_forward",
     "cough_mask_axes", "cough_prepare_clip", "cough_resample", "cough_ring_write", "cough_window_gather",
     "cough_synth_clips", "cough_pre_emphasis", "cough_compute_deltas", "cough_pcen",
+    "cough_augment_workspace_bytes", "cough_augment_waveforms", "cough_mix_rows",
 )
 
 
@@ -86,6 +87,12 @@ class CnnBlock(C.Structure):
 class CnnWeights(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("blocks", C.POINTER(CnnBlock)), ("hidden", C.c_int), ("fc1_w", _FP),
                 ("fc1_b", _FP), ("fc2_w", _FP), ("fc2_b", _FP), ("bn_eps", C.c_float)]
+
+
+class CoughAugClip(C.Structure):
+    """cough_aug_clip: one clip's draws of AudioAugmentor.augment."""
+    _fields_ = [("shift", C.c_int), ("gain", C.c_float), ("gaussian", C.c_int), ("bank_index", C.c_int),
+                ("gaussian_snr_db", C.c_double), ("bank_snr_db", C.c_double), ("bank_start", C.c_longlong)]
 
 
 _lib = None
@@ -161,6 +168,11 @@ def load() -> C.CDLL:
         lib.cough_pre_emphasis.argtypes = [vp, ll, vp, ll, i, i, C.c_float, vp]
         lib.cough_compute_deltas.argtypes = [vp, vp, ll, i, vp]
         lib.cough_pcen.argtypes = [vp, vp, ll, i, C.c_float, C.c_float, C.c_float, C.c_float, vp]
+        lib.cough_augment_workspace_bytes.argtypes = [i]
+        lib.cough_augment_workspace_bytes.restype = C.c_size_t
+        lib.cough_augment_waveforms.argtypes = [vp, ll, vp, i, i, C.POINTER(i), C.POINTER(CoughAugClip), vp, ll,
+                                                C.POINTER(ll), C.POINTER(i), i, vp, C.c_ulonglong, vp, C.c_size_t, vp]
+        lib.cough_mix_rows.argtypes = [vp, vp, vp, vp, ll, ll, vp, vp]
         if lib.cough_amd_abi_version() != 5:
             raise RuntimeError("libcough_amd.so ABI version mismatch; rebuild it")
         _lib = lib

@@ -1,22 +1,35 @@
-"""SpecAugment on the MI355X, with the reference's interface (``/root/reference/src/augmentation.py:271-331``).
+"""The reference's augmentation module (``/root/reference/src/augmentation.py``) on the MI355X, with its interface.
 
-Same constructor arguments and call convention as the reference class; the random draws happen on the host in the
-reference's order -- ``random.random()`` for the coin, then per mask two ``torch.rand(1)`` as torchaudio's
-``mask_along_axis`` draws them -- so a seeded run masks the same rows / columns as the reference.  The masking itself
-is one pass of ``cough_mask_axes`` over the whole batch (all frequency and time masks at once) instead of one
-``masked_fill`` pass per mask.  Waveform-domain augmentation (``AudioAugmentor``, ``MixUp``) belongs to the training
-loop and is not part of this build.
+* ``AudioAugmentor`` (:19-268): the waveform chain ``time_shift -> speed_perturbation -> volume_perturbation ->
+  add_gaussian_noise -> add_noise`` runs in ``cough_augment_waveforms`` (``csrc/augment.hip``).  Every coin and uniform is
+  drawn on the host with Python ``random``, per clip, in the reference's order, so a seeded run draws what the reference
+  draws.  ``augment`` and the single methods take one ``(1, N)`` clip and draw their gaussian noise with
+  ``torch.randn_like`` on the CPU generator as the reference does; ``augment_batch`` runs a whole ``(B, N)`` batch
+  (ragged lengths allowed) in one launch, with the noise drawn on the device (counter-based, seeded) or on the host.
+* ``SpecAugment`` (:271-331): random draws on the host in the reference's order -- ``random.random()`` for the coin, then
+  per mask two ``torch.rand(1)`` as torchaudio's ``mask_along_axis`` draws them -- so a seeded run masks the same rows /
+  columns as the reference.  The masking itself is one pass of ``cough_mask_axes`` over the whole batch (all frequency and
+  time masks at once) instead of one ``masked_fill`` pass per mask.
+* ``MixUp`` (:334-369) and ``create_augmentation_pipeline`` (:372-398); the mixing runs in ``cough_mix_rows``.
+
+Differences a caller can observe: results come back where the input lives, as float32.  ``pitch_shift`` draws its coin
+and semitones as the reference does and returns its input unchanged -- the reference's own result when sox is absent
+(its ``except`` branch); ``augment`` never calls it.  The noise bank decodes WAVE files only (``load_wave``); other files
+are skipped like the reference's undecodable ones.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import random
-from typing import List, Tuple
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
-from . import _lib
-from .preprocessing import _cuda_device
+from . import _lib, _tables
+from .preprocessing import _cuda_device, load_wave
 
 
 class SpecAugment:
@@ -64,3 +77,311 @@ class SpecAugment:
                                                    arr(0), arr(1), arr(2), torch.cuda.current_stream(dev).cuda_stream),
                        "cough_mask_axes")
         return out.to(spectrogram.device) if spectrogram.device.type == "cpu" else out
+
+
+# ---------------------------------------------------------------------------------------------- waveform augmentation
+_SHIFT_LIMIT, _GAIN_RANGE, _GAUSS_SNR, _BANK_SNR = 0.2, (0.7, 1.3), (10, 30), (5, 20)
+
+
+def _repeated_length(entry_len: int, target_len: int) -> int:
+    """Length of a noise entry after the reference's ``repeat`` (augmentation.py:143-147)."""
+    return entry_len * (target_len // entry_len + 1) if entry_len < target_len else entry_len
+
+
+class AudioAugmentor:
+    def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5):
+        self.sample_rate = sample_rate
+        self.p_augment = p_augment
+        self.noise_samples: List[torch.Tensor] = []      # (1, L) float32 on the host, as the reference keeps them
+        self._bank_host = torch.zeros(0, dtype=torch.float32)
+        self._bank_offsets: List[int] = []
+        self._bank_lengths: List[int] = []
+        self._bank_dev = None
+        if noise_dir and Path(noise_dir).exists():
+            self._load_noise_samples(noise_dir)
+
+    # ------------------------------------------------------------------ noise bank
+    def _resample(self, waveform: torch.Tensor, orig_sr: int) -> torch.Tensor:
+        """T.Resample(orig_sr, sample_rate) of a (C, N) host tensor on the GPU (``cough_resample``); back on the host."""
+        dev = _cuda_device()
+        kern, width, orig, new = _tables.sinc_resample_kernel(orig_sr, self.sample_rate)
+        x = waveform.to(device=dev, dtype=torch.float32).contiguous()
+        rows, n = x.shape
+        out_len = int(math.ceil(new * n / orig))
+        out = torch.empty((rows, out_len), dtype=torch.float32, device=dev)
+        kern = kern.to(dev)
+        if rows and out_len:
+            _lib.check(_lib.load().cough_resample(x.data_ptr(), n, rows, n, kern.data_ptr(), orig, new, width, out.data_ptr(),
+                                                  out_len, out_len, torch.cuda.current_stream(dev).cuda_stream), "cough_resample")
+        return out.cpu()
+
+    def _load_noise_samples(self, noise_dir: str, max_samples: int = 100):
+        """Load background noise samples from directory (reference :57-75): the first ``max_samples`` of the ``.wav``,
+        ``.mp3``, ``.flac``, ``.ogg`` files in that order, each resampled to ``sample_rate`` and averaged to mono.  Files
+        that do not decode (or hold no samples) are skipped.  The bank is then packed into one buffer, on the device."""
+        noise_path = Path(noise_dir)
+        noise_files = []
+        for ext in ['.wav', '.mp3', '.flac', '.ogg']:
+            noise_files.extend(noise_path.glob(f'*{ext}'))
+        for f in noise_files[:max_samples]:
+            try:
+                waveform, sr = load_wave(str(f))
+            except ValueError:
+                continue
+            if waveform.shape[1] == 0:
+                continue
+            if sr != self.sample_rate:
+                waveform = self._resample(waveform, sr)
+            if waveform.shape[0] > 1:
+                waveform = waveform.mean(dim=0, keepdim=True)
+            self.noise_samples.append(waveform)
+        self._pack_bank()
+
+    def _pack_bank(self) -> None:
+        lengths = [int(w.shape[1]) for w in self.noise_samples]
+        self._bank_lengths = lengths
+        self._bank_offsets = [sum(lengths[:k]) for k in range(len(lengths))]
+        self._bank_host = (torch.cat([w.reshape(-1).float() for w in self.noise_samples]) if lengths
+                           else torch.zeros(0, dtype=torch.float32))
+        self._bank_dev = None
+        if lengths and torch.cuda.is_available():
+            self._bank_dev = self._bank_host.to(_cuda_device())
+
+    def _bank_device(self, dev: torch.device) -> torch.Tensor:
+        if self._bank_dev is None or self._bank_dev.device != dev:
+            self._bank_dev = self._bank_host.to(dev)
+        return self._bank_dev
+
+    # ------------------------------------------------------------------ host draws (the reference's order)
+    def _coin(self) -> bool:
+        return not (random.random() > self.p_augment)
+
+    def _draw_shift(self, n: int, shift_limit: float = _SHIFT_LIMIT) -> int:
+        return int(n * random.uniform(-shift_limit, shift_limit)) if self._coin() else 0
+
+    def _draw_gain(self, gain_range=_GAIN_RANGE) -> Optional[float]:
+        return random.uniform(*gain_range) if self._coin() else None
+
+    def _draw_gauss(self, snr_range=_GAUSS_SNR) -> Optional[float]:
+        return random.uniform(*snr_range) if self._coin() else None
+
+    def _draw_bank(self, n: int, snr_range=_BANK_SNR) -> Optional[Tuple[int, int, float]]:
+        """add_noise's draws: coin, ``random.choice``, ``random.randint`` over the repeated entry, SNR."""
+        if random.random() > self.p_augment or len(self.noise_samples) == 0:
+            return None
+        k = random.choice(range(len(self.noise_samples)))      # the same draw as random.choice(self.noise_samples)
+        start = random.randint(0, _repeated_length(self._bank_lengths[k], n) - n)
+        return k, start, random.uniform(*snr_range)
+
+    def draw_clip(self, n: int) -> _lib.CoughAugClip:
+        """One ``augment`` call's draws for a clip of ``n`` samples (reference :249-268)."""
+        c = _lib.CoughAugClip(shift=0, gain=1.0, gaussian=0, bank_index=-1, gaussian_snr_db=0.0, bank_snr_db=0.0,
+                              bank_start=0)
+        c.shift = self._draw_shift(n)
+        gain = self._draw_gain()                                  # speed_perturbation draws nothing
+        if gain is not None:
+            c.gain = gain
+        snr = self._draw_gauss()
+        if snr is not None:
+            c.gaussian, c.gaussian_snr_db = 1, snr
+        if len(self.noise_samples) > 0:
+            d = self._draw_bank(n)
+            if d is not None:
+                c.bank_index, c.bank_start, c.bank_snr_db = d
+        return c
+
+    def draw_batch(self, lengths: Sequence[int]) -> List[_lib.CoughAugClip]:
+        """The draws of ``augment_batch``: ``draw_clip`` for each clip in order, as a Dataset calls ``augment`` per item."""
+        return [self.draw_clip(int(n)) for n in lengths]
+
+    # ------------------------------------------------------------------ the kernel
+    def _run(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
+             gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
+        """One cough_augment_waveforms launch over the rows of the 2-D ``x``; the result where ``x`` lives."""
+        dev = _cuda_device()
+        src = x.detach().to(device=dev, dtype=torch.float32)
+        if src.stride(-1) != 1 or src.stride(0) < src.shape[1]:
+            src = src.contiguous()
+        b, n = src.shape
+        out = torch.empty((b, n), dtype=torch.float32, device=dev)
+        if b == 0:
+            return out.to(x.device)
+        lib = _lib.load()
+        arr = (_lib.CoughAugClip * b)(*clips)
+        lens = (C.c_int * b)(*[int(v) for v in lengths]) if lengths is not None else None
+        nb = len(self._bank_lengths)
+        bank = self._bank_device(dev) if nb else None
+        offs = (C.c_longlong * nb)(*self._bank_offsets) if nb else None
+        blen = (C.c_int * nb)(*self._bank_lengths) if nb else None
+        z = gaussian.to(device=dev, dtype=torch.float32).contiguous() if gaussian is not None else None
+        ws = torch.empty(max(int(lib.cough_augment_workspace_bytes(b)), 1), dtype=torch.uint8, device=dev)
+        stride = src.stride(0) if b > 1 else n
+        _lib.check(lib.cough_augment_waveforms(src.data_ptr(), stride, out.data_ptr(), b, n, lens, arr,
+                                               bank.data_ptr() if bank is not None else None,
+                                               bank.numel() if bank is not None else 0, offs, blen, nb,
+                                               z.data_ptr() if z is not None else None, seed & (2**64 - 1),
+                                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                   "cough_augment_waveforms")
+        return out.to(x.device)
+
+    @staticmethod
+    def _one_clip(waveform: torch.Tensor, who: str) -> None:
+        if not isinstance(waveform, torch.Tensor) or not waveform.dtype.is_floating_point:
+            raise TypeError(f"{who}: expected a floating-point torch.Tensor")
+        if waveform.dim() != 2 or waveform.shape[0] != 1 or waveform.shape[1] < 1:
+            raise ValueError(f"{who}: expected one (1, N) clip, got {tuple(waveform.shape)}")
+
+    def _single(self, waveform: torch.Tensor, c: _lib.CoughAugClip) -> torch.Tensor:
+        gaussian = torch.randn_like(waveform, dtype=torch.float32, device="cpu") if c.gaussian else None
+        return self._run(waveform, [c], None, gaussian, 0).to(waveform.dtype)
+
+    @staticmethod
+    def _blank() -> _lib.CoughAugClip:
+        return _lib.CoughAugClip(shift=0, gain=1.0, gaussian=0, bank_index=-1, gaussian_snr_db=0.0, bank_snr_db=0.0,
+                                 bank_start=0)
+
+    # ------------------------------------------------------------------ the reference's methods (one (1, N) clip)
+    def time_shift(self, waveform: torch.Tensor, shift_limit: float = _SHIFT_LIMIT) -> torch.Tensor:
+        if random.random() > self.p_augment:
+            return waveform
+        self._one_clip(waveform, "time_shift")
+        c = self._blank()
+        c.shift = int(waveform.shape[1] * random.uniform(-shift_limit, shift_limit))
+        return waveform if c.shift == 0 else self._single(waveform, c)
+
+    def speed_perturbation(self, waveform: torch.Tensor, speed_range: Tuple[float, float] = (0.9, 1.1)) -> torch.Tensor:
+        """The identity, as in the reference (:107-117)."""
+        return waveform
+
+    def add_noise(self, waveform: torch.Tensor, snr_range: Tuple[float, float] = _BANK_SNR) -> torch.Tensor:
+        self._one_clip(waveform, "add_noise")
+        d = self._draw_bank(waveform.shape[1], snr_range)
+        if d is None:
+            return waveform
+        c = self._blank()
+        c.bank_index, c.bank_start, c.bank_snr_db = d
+        return self._single(waveform, c)
+
+    def add_gaussian_noise(self, waveform: torch.Tensor, snr_range: Tuple[float, float] = _GAUSS_SNR) -> torch.Tensor:
+        self._one_clip(waveform, "add_gaussian_noise")
+        snr = self._draw_gauss(snr_range)
+        if snr is None:
+            return waveform
+        c = self._blank()
+        c.gaussian, c.gaussian_snr_db = 1, snr
+        return self._single(waveform, c)
+
+    def volume_perturbation(self, waveform: torch.Tensor, gain_range: Tuple[float, float] = _GAIN_RANGE) -> torch.Tensor:
+        self._one_clip(waveform, "volume_perturbation")
+        gain = self._draw_gain(gain_range)
+        if gain is None:
+            return waveform
+        c = self._blank()
+        c.gain = gain
+        return self._single(waveform, c)
+
+    def pitch_shift(self, waveform: torch.Tensor, shift_range: Tuple[int, int] = (-2, 2)) -> torch.Tensor:
+        """Draws the reference's coin and semitones (:215-247), then returns the input unchanged: what the reference
+        returns when sox is not available.  ``augment`` does not call it; a real pitch shifter is not part of this build."""
+        if random.random() > self.p_augment:
+            return waveform
+        random.randint(*shift_range)
+        return waveform
+
+    def augment(self, waveform: torch.Tensor) -> torch.Tensor:
+        """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
+        self._one_clip(waveform, "augment")
+        c = self.draw_clip(waveform.shape[1])
+        if c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
+            return waveform
+        return self._single(waveform, c)
+
+    def augment_batch(self, waveforms: torch.Tensor, lengths=None, noise: str = "device",
+                      seed: Optional[int] = None) -> torch.Tensor:
+        """``augment`` of every row of a (B, N) batch in ONE launch: clip b is its first ``lengths[b]`` samples (all N
+        when ``lengths`` is None), gets its own draws (in row order, as a Dataset calls ``augment`` per item) and its tail
+        is written as 0.  ``noise="device"``: the gaussian noise comes from the seeded counter-based generator on the GPU
+        (``seed``: 64-bit; None draws one from torch's CPU generator); ``noise="host"``: ``torch.randn`` on the CPU
+        generator, one clip after the other, as the reference's ``randn_like``.  Returns (B, N) where the input lives."""
+        if noise not in ("device", "host"):
+            raise ValueError(f"augment_batch: noise must be 'device' or 'host', got {noise!r}")
+        if not isinstance(waveforms, torch.Tensor) or not waveforms.dtype.is_floating_point:
+            raise TypeError("augment_batch: expected a floating-point torch.Tensor")
+        if waveforms.dim() != 2 or waveforms.shape[1] < 1:
+            raise ValueError(f"augment_batch: expected (B, N), got {tuple(waveforms.shape)}")
+        b, n = waveforms.shape
+        if lengths is not None:
+            lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            if len(lengths) != b or any(v < 1 or v > n for v in lengths):
+                raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
+        clips = self.draw_batch(lengths if lengths is not None else [n] * b)
+        gaussian = None
+        if noise == "host":
+            gaussian = torch.zeros((b, n), dtype=torch.float32)
+            for i, c in enumerate(clips):
+                if c.gaussian:
+                    li = lengths[i] if lengths is not None else n
+                    gaussian[i, :li] = torch.randn(li)
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
+        return self._run(waveforms, clips, lengths, gaussian, int(seed))
+
+
+def _mix(x1: torch.Tensor, x2: torch.Tensor, lam: np.ndarray, index: Optional[torch.Tensor], who: str) -> torch.Tensor:
+    """rows of x1 (B rows, or one row of everything) mixed with rows of x2: one ``cough_mix_rows`` launch."""
+    dev = _cuda_device()
+    a = x1.detach().to(device=dev, dtype=torch.float32).contiguous()
+    b = x2.detach().to(device=dev, dtype=torch.float32).contiguous()
+    rows = len(lam)
+    if a.numel() % rows or b.numel() != a.numel():
+        raise ValueError(f"{who}: shapes {tuple(x1.shape)} and {tuple(x2.shape)} do not mix")
+    out = torch.empty_like(a)
+    lam64 = np.asarray(lam, dtype=np.float64)
+    coef = torch.from_numpy(np.stack([lam64, 1.0 - lam64], axis=1).astype(np.float32)).to(dev)
+    idx = index.to(device=dev, dtype=torch.int32).contiguous() if index is not None else None
+    if out.numel():
+        _lib.check(_lib.load().cough_mix_rows(a.data_ptr(), b.data_ptr(), idx.data_ptr() if idx is not None else None,
+                                              out.data_ptr(), rows, a.numel() // rows, coef.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream), "cough_mix_rows")
+    return out.to(x1.device)
+
+
+class MixUp:
+    def __init__(self, alpha: float = 0.2):
+        self.alpha = alpha
+        self.last_lam: Optional[np.ndarray] = None
+
+    def __call__(self, x1: torch.Tensor, y1: torch.Tensor, x2: torch.Tensor,
+                 y2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's pair call (:353-369): one ``lam = np.random.beta(alpha, alpha)``, x and y mixed with it."""
+        lam = np.random.beta(self.alpha, self.alpha)
+        self.last_lam = np.array([lam])
+        if x1.shape != x2.shape or y1.shape != y2.shape:
+            raise ValueError(f"MixUp: shapes differ: {tuple(x1.shape)} / {tuple(x2.shape)}, {tuple(y1.shape)} / {tuple(y2.shape)}")
+        return _mix(x1, x2, self.last_lam, None, "MixUp"), _mix(y1, y2, self.last_lam, None, "MixUp")
+
+    def mix_batch(self, x: torch.Tensor, y: torch.Tensor,
+                  perm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """MixUp of a batch with a permutation of itself, one λ per row (``np.random.beta(alpha, alpha, size=B)``):
+        x[b] <- lam[b] x[b] + (1 - lam[b]) x[perm[b]], the same for the labels y (B, ...).  ``perm`` defaults to
+        ``torch.randperm(B)``; the λ of the last call are ``last_lam``."""
+        bsz = x.shape[0]
+        if y.shape[0] != bsz:
+            raise ValueError(f"MixUp.mix_batch: {bsz} inputs but {y.shape[0]} labels")
+        perm = torch.randperm(bsz) if perm is None else torch.as_tensor(perm)
+        perm = perm.detach().to("cpu", torch.int64).reshape(-1)
+        if perm.numel() != bsz or (bsz and (int(perm.min()) < 0 or int(perm.max()) >= bsz)):
+            raise ValueError(f"MixUp.mix_batch: perm must hold {bsz} row indices in 0..{bsz - 1}")
+        lam = np.random.beta(self.alpha, self.alpha, size=bsz)
+        self.last_lam = lam
+        if bsz == 0:
+            return x, y
+        return _mix(x, x, lam, perm, "MixUp.mix_batch"), _mix(y, y, lam, perm, "MixUp.mix_batch")
+
+
+def create_augmentation_pipeline(sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
+                                 use_spec_augment: bool = True) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
+    """(AudioAugmentor, SpecAugment or None), reference :372-398."""
+    audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment)
+    spec_aug = SpecAugment(p=p_augment) if use_spec_augment else None
+    return audio_aug, spec_aug

@@ -311,6 +311,50 @@ int cough_pipeline_forward(const cough_featurizer* f, const cough_resnet* m, con
 int cough_mask_axes(const float* d_in, float* d_out, long long n_images, int height, int width, int n_masks,
                     const int* axis, const int* start, const int* end, void* stream);
 
+/* ------------------------------------------------------------------ waveform augmentation (training-side, before featurisation)
+ * Replaces AudioAugmentor.augment (/root/reference/src/augmentation.py:249-268) for a batch: clip b of d_in (row b at
+ * d_in + b*in_stride, its first len_b = lengths[b] samples, or n_samples when lengths is NULL) gets its own draws,
+ * applied in the reference's order:
+ *   time_shift (:77-105)           y[i] = x[i - shift] for 0 <= i - shift < len_b, else 0 (|shift| < len_b)
+ *   speed_perturbation (:107-117)  the identity, as in the reference
+ *   volume_perturbation (:194-213) y *= gain
+ *   add_gaussian_noise (:165-192)  P = mean(y^2), Pz = mean(z^2) of the noise drawn, y += sqrt(P / (10^(snr/10) Pz)) z
+ *   add_noise (:119-163)           P = mean(y^2) again; the crop n[i] = entry[(bank_start + i) % entry_len] (the reference's
+ *                                  repeat + crop); y += sqrt(P / (10^(snr/10) Pn)) n when Pn = mean(n^2) > 0
+ * The caller draws every coin and uniform (host RNG, as the reference).  Every mean is an fp32 reduction over the clip's
+ * len_b samples in a fixed order (results are the same from run to run); a NaN / Inf sample stays local through shift and
+ * gain and spreads to the whole clip through a noise step that fired.  d_out: [n_clips][n_samples], samples [len_b,
+ * n_samples) written as 0; d_out must not alias d_in.
+ * z: d_gaussian ([n_clips][n_samples], the first len_b of row b used) or, when d_gaussian is NULL, a counter-based
+ * generator on the device (Philox4x32-10 keyed by `seed`, counter (sample / 4, clip); Box-Muller): the same seed and
+ * batch give a bit-identical output.
+ * The noise bank is one device buffer d_bank of bank_numel float32; entry k is bank_lengths[k] >= 1 samples at
+ * d_bank + bank_offsets[k] (both HOST arrays).  lengths and clips are HOST arrays; every one of them is checked before
+ * the first launch.  d_workspace: device memory, 256-byte aligned, >= cough_augment_workspace_bytes(n_clips) (receives
+ * the resolved per-clip records, stream-ordered). */
+typedef struct cough_aug_clip {
+    int shift;              /* time_shift samples: > 0 right (zeros on the left), < 0 left; 0 = not fired */
+    float gain;             /* volume_perturbation: 1 = not fired */
+    int gaussian;           /* add_gaussian_noise fired: 1 / 0 */
+    int bank_index;         /* add_noise: bank entry, -1 = not fired */
+    double gaussian_snr_db;
+    double bank_snr_db;
+    long long bank_start;   /* start of the crop in the repeated entry: 0 .. L_rep - len_b, L_rep = entry_len if
+                             * entry_len >= len_b, else (len_b / entry_len + 1) * entry_len */
+} cough_aug_clip;
+size_t cough_augment_workspace_bytes(int n_clips);
+int cough_augment_waveforms(const float* d_in, long long in_stride, float* d_out, int n_clips, int n_samples,
+                            const int* lengths, const cough_aug_clip* clips, const float* d_bank, long long bank_numel,
+                            const long long* bank_offsets, const int* bank_lengths, int n_bank, const float* d_gaussian,
+                            unsigned long long seed, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* MixUp (/root/reference/src/augmentation.py:334-369) for rows: d_out[r] = coef[r][0] * d_x1[r] + coef[r][1] * d_x2[s]
+ * with s = d_index2[r] (device int32, may be NULL: s = r), rows of row_len float32, each product rounded on its own
+ * as torch's `lam * x1 + (1 - lam) * x2` (coef = (lam, 1 - lam) rounded to float by the caller).  d_coef: device
+ * [n_rows][2] float32.  An index outside [0, n_rows) yields a NaN row (callers check indices first). */
+int cough_mix_rows(const float* d_x1, const float* d_x2, const int* d_index2, float* d_out, long long n_rows,
+                   long long row_len, const float* d_coef, void* stream);
+
 /* ------------------------------------------------------------------ resampler (front of process())
  * Replaces T.Resample(orig, 16000)(waveform) (/root/reference/src/preprocessing.py:146-183): polyphase
  * windowed-sinc FIR.  d_kernel: device [new][K] float32, K = 2*width + orig, built by the caller the way
