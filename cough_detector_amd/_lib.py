@@ -50,10 +50,12 @@ SYMBOLS = (
     "cough_mask_axes", "cough_prepare_clip", "cough_resample", "cough_ring_write", "cough_window_gather",
     "cough_synth_clips", "cough_pre_emphasis", "cough_compute_deltas", "cough_pcen",
     "cough_augment_workspace_bytes", "cough_augment_waveforms", "cough_mix_rows",
+    "cough_train_workspace_bytes", "cough_train_forward_backward", "cough_adamw_step",
 )
 
 
 MAX_CONTRAST_BANDS = 16
+TRAIN_NUM_PARAMS, TRAIN_NUM_RUNNING = 290370, 1216   # COUGH_TRAIN_NUM_PARAMS / COUGH_TRAIN_NUM_RUNNING
 
 
 class FeatConfig(C.Structure):
@@ -173,6 +175,12 @@ def load() -> C.CDLL:
         lib.cough_augment_waveforms.argtypes = [vp, ll, vp, i, i, C.POINTER(i), C.POINTER(CoughAugClip), vp, ll,
                                                 C.POINTER(ll), C.POINTER(i), i, vp, C.c_ulonglong, vp, C.c_size_t, vp]
         lib.cough_mix_rows.argtypes = [vp, vp, vp, vp, ll, ll, vp, vp]
+        f, ull = C.c_float, C.c_ulonglong
+        lib.cough_train_workspace_bytes.argtypes = [i, i, i]
+        lib.cough_train_workspace_bytes.restype = C.c_size_t
+        lib.cough_train_forward_backward.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, vp, vp, vp, vp, f, f, vp, vp,
+                                                     vp, vp, C.c_size_t, vp]
+        lib.cough_adamw_step.argtypes = [vp, vp, vp, vp, ll, f, f, f, f, f, f, C.c_double, C.c_double, vp, vp]
         if lib.cough_amd_abi_version() != 5:
             raise RuntimeError("libcough_amd.so ABI version mismatch; rebuild it")
         _lib = lib

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "philox.h"
 
 namespace cough {
 namespace {
@@ -32,18 +33,6 @@ struct AugRec {
     unsigned bank_start;  // crop start reduced modulo bank_len: sample i of the crop is entry[(bank_start + i) % bank_len]
     int pad;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11): counter (sample group, clip, 0, 0), key = the 64-bit seed.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u;
-        k.y += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // Four standard normals for samples 4g .. 4g+3 of clip b (two Box-Muller pairs, 24-bit uniforms, u1 in (0, 1]).
 __device__ __forceinline__ float4 gauss4(unsigned long long seed, int b, int g) {

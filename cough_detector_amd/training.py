@@ -1,0 +1,260 @@
+"""Training of ``CoughDetectorResidual`` on the MI355X: one optimisation step as the reference's ``train_epoch`` takes it
+(``/root/reference/src/train.py:54-112``, built at :420-455)::
+
+    optimizer.zero_grad(); outputs = model(inputs)            # train mode: batch-statistics BN, Dropout(p)
+    loss = CrossEntropyLoss(weight=class_weights)(outputs, targets); loss.backward()
+    clip_grad_norm_(model.parameters(), max_norm); AdamW(lr, betas, eps, weight_decay).step()
+
+The forward, backward and optimizer arithmetic runs in ``csrc/train.hip`` (``cough_train_forward_backward``,
+``cough_adamw_step``); torch only allocates memory and supplies the stream.  The trainer makes the module's parameters,
+gradients (``p.grad``) and BatchNorm buffers views of flat device buffers that the kernels update in place, so
+``model.state_dict()`` holds the trained state after every step and ``model.eval()(x)`` runs the inference kernels on it.
+``model.train()(x)`` still refuses: training goes through the trainer.
+
+Non-finite input gives a NaN loss; the step then leaves NaN gradients and parameters (as torch's own step does: the clip
+coefficient of a NaN norm does not rescue them).  Shipped channels ``(32, 64, 128)`` only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Iterable, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .model import CoughDetectorResidual
+
+SHIPPED_CHANNELS = (32, 64, 128)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+class HipAdamW(torch.optim.Optimizer):
+    """``torch.optim.AdamW`` with the gradient clip of ``train_epoch`` fused in, on ``cough_adamw_step``.
+
+    ``param_groups`` / ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.AdamW``'s layout (per parameter index:
+    ``step``, ``exp_avg``, ``exp_avg_sq``), so a state moves between the two and torch LR schedulers drive ``lr``.  One
+    parameter group; its ``lr``, ``betas``, ``eps`` and ``weight_decay`` are read on every ``step()``.  The moments are
+    views of two flat device buffers laid out like the parameters."""
+
+    def __init__(self, params: Sequence[torch.nn.Parameter], flat_params: torch.Tensor, flat_grads: torch.Tensor,
+                 lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 1.0):
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+        super().__init__(list(params), defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("HipAdamW: one parameter group")
+        self._flat, self._flat_grads = flat_params, flat_grads
+        self._exp_avg = torch.zeros_like(flat_params)
+        self._exp_avg_sq = torch.zeros_like(flat_params)
+        self._total_norm = torch.zeros(1, dtype=torch.float32, device=flat_params.device)
+        self._n_steps = 0
+        self.max_norm = float(max_norm)
+        self._bind_state()
+
+    def _slices(self):
+        off = 0
+        for p in self.param_groups[0]["params"]:
+            yield p, off, p.numel()
+            off += p.numel()
+
+    def _bind_state(self):
+        for p, off, n in self._slices():
+            self.state[p] = {"step": torch.tensor(float(self._n_steps)),
+                             "exp_avg": self._exp_avg[off:off + n].view_as(p),
+                             "exp_avg_sq": self._exp_avg_sq[off:off + n].view_as(p)}
+
+    @property
+    def total_norm(self) -> torch.Tensor:
+        """The gradient norm of the last step (before clipping), a 1-element device tensor."""
+        return self._total_norm
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise ValueError("HipAdamW.step: closures are not supported")
+        g = self.param_groups[0]
+        beta1, beta2 = g["betas"]
+        self._n_steps += 1
+        bc1 = 1.0 - float(beta1) ** self._n_steps
+        bc2 = 1.0 - float(beta2) ** self._n_steps
+        dev = self._flat.device
+        _lib.check(_lib.load().cough_adamw_step(
+            self._flat.data_ptr(), self._flat_grads.data_ptr(), self._exp_avg.data_ptr(), self._exp_avg_sq.data_ptr(),
+            self._flat.numel(), float(g["lr"]), float(beta1), float(beta2), float(g["eps"]), float(g["weight_decay"]),
+            self.max_norm, bc1, bc2, self._total_norm.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+            "cough_adamw_step")
+        return None
+
+    def state_dict(self):
+        for p, _, _ in self._slices():
+            self.state[p]["step"].fill_(float(self._n_steps))
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        steps = set()
+        with torch.no_grad():
+            for p, off, n in self._slices():
+                st = self.state.get(p, {})
+                if "exp_avg" in st:
+                    self._exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
+                    self._exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
+                    steps.add(int(float(st["step"])))
+                else:
+                    self._exp_avg[off:off + n].zero_()
+                    self._exp_avg_sq[off:off + n].zero_()
+                    steps.add(0)
+        if len(steps) != 1:
+            raise ValueError(f"HipAdamW.load_state_dict: parameters at different steps {sorted(steps)}")
+        self._n_steps = steps.pop()
+        self._bind_state()
+
+
+class ResidualTrainer:
+    """Trains a ``CoughDetectorResidual`` (``channels=(32, 64, 128)``) with the reference's ``train_epoch`` step.
+
+    ``step(inputs, targets, dropout_mask=None) -> (loss, logits)``: ``inputs`` (B, 1, F, T) float32, ``targets`` (B,)
+    int64 class indices; ``dropout_mask`` (B, 128) of 0 / 1 keeps, or ``None`` for the device generator (Philox keyed by
+    ``seed``, one new draw per step).  ``loss`` is a 0-d device tensor, ``logits`` the train-mode outputs; both are
+    buffers of the trainer, overwritten by the next step at the same shape (read them, e.g. ``loss.item()``, first).
+    No host synchronisation; no allocation after the first step at a given (B, F, T)."""
+
+    def __init__(self, model: CoughDetectorResidual, lr: float = 1e-3, weight_decay: float = 0.01,
+                 betas=(0.9, 0.999), eps: float = 1e-8, class_weights=None, max_norm: float = 1.0, seed: int = 0):
+        if not isinstance(model, CoughDetectorResidual):
+            raise TypeError("ResidualTrainer trains a CoughDetectorResidual")
+        if tuple(model.channels) != SHIPPED_CHANNELS:
+            raise ValueError(f"ResidualTrainer: channels={tuple(model.channels)}; the training kernels are built for "
+                             f"{SHIPPED_CHANNELS}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950); there is no CPU fallback")
+        if max_norm <= 0:
+            raise ValueError("ResidualTrainer: max_norm must be > 0")
+        bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
+        if len(bns) != 7 or any(b.momentum is None or not b.track_running_stats or not b.affine for b in bns):
+            raise ValueError("ResidualTrainer: every BatchNorm needs affine=True, track_running_stats=True and a momentum")
+        if len({(float(b.momentum), float(b.eps)) for b in bns}) != 1:
+            raise ValueError("ResidualTrainer: all BatchNorm layers must share momentum and eps")
+        self.model = model
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        dev = self.device
+        model.to(dev)
+        params = list(model.parameters())
+        n = sum(p.numel() for p in params)
+        if len(params) != 30 or n != _lib.TRAIN_NUM_PARAMS:
+            raise ValueError(f"ResidualTrainer: {len(params)} parameter tensors / {n} values, expected 30 / "
+                             f"{_lib.TRAIN_NUM_PARAMS}")
+        self._params = torch.empty(n, dtype=torch.float32, device=dev)
+        self._grads = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._running = torch.empty(_lib.TRAIN_NUM_RUNNING, dtype=torch.float32, device=dev)
+        self._nbt = torch.empty(len(bns), dtype=torch.int64, device=dev)
+        with torch.no_grad():
+            off = 0
+            for p in params:
+                k = p.numel()
+                self._params[off:off + k].copy_(p.detach().reshape(-1))
+                p.data = self._params[off:off + k].view_as(p)
+                p.grad = self._grads[off:off + k].view_as(p)
+                off += k
+            off = 0
+            for i, bn in enumerate(bns):
+                c = bn.num_features
+                self._running[off:off + c].copy_(bn.running_mean)
+                self._running[off + c:off + 2 * c].copy_(bn.running_var)
+                self._nbt[i].copy_(bn.num_batches_tracked)
+                bn.running_mean = self._running[off:off + c]
+                bn.running_var = self._running[off + c:off + 2 * c]
+                bn.num_batches_tracked = self._nbt[i]
+                off += 2 * c
+        model._tensors = None
+        self._momentum, self._bn_eps = float(bns[0].momentum), float(bns[0].eps)
+        self.class_weights = None
+        if class_weights is not None:
+            cw = torch.as_tensor(class_weights, dtype=torch.float32).to(dev).reshape(-1).contiguous()
+            if cw.numel() != 2:
+                raise ValueError("ResidualTrainer: class_weights needs one weight per class (2)")
+            self.class_weights = cw
+        self.optimizer = HipAdamW(params, self._params, self._grads, lr=lr, betas=betas, eps=eps,
+                                  weight_decay=weight_decay, max_norm=max_norm)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self._draws = 0                      # device dropout draws so far: the Philox counter offset of the next one
+        self._shape = None
+        self._ws = self._loss = self._logits = None
+
+    # ------------------------------------------------------------------ step
+    def _prepare(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask):
+        dev = self.device
+        if inputs.dim() != 4 or inputs.shape[1] != 1:
+            raise ValueError(f"expected inputs (B, 1, F, T), got {tuple(inputs.shape)}")
+        x = inputs.detach().to(device=dev, dtype=torch.float32).contiguous()
+        b, _, hgt, wid = x.shape
+        t = torch.as_tensor(targets).detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if t.numel() != b:
+            raise ValueError(f"targets: {t.numel()} values for a batch of {b}")
+        mask = None
+        if dropout_mask is not None:
+            mask = torch.as_tensor(dropout_mask).detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(mask.shape) != (b, 128):
+                raise ValueError(f"dropout_mask must be ({b}, 128), got {tuple(mask.shape)}")
+        if self._shape != (b, hgt, wid):
+            need = _lib.load().cough_train_workspace_bytes(b, hgt, wid)
+            if need == 0:
+                raise ValueError(f"ResidualTrainer: a batch of {b} images of {hgt}x{wid} is not trainable (image too "
+                                 "small for the network, or a BatchNorm would see one value per channel)")
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._loss = torch.empty((), dtype=torch.float32, device=dev)
+            self._logits = torch.empty((b, 2), dtype=torch.float32, device=dev)
+            self._shape = (b, hgt, wid)
+        return x, t, mask
+
+    def forward_backward(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask=None, mask_out=None):
+        """The forward and backward half of ``step``: writes ``p.grad`` of every parameter (unclipped), the BN running
+        statistics and counters; returns ``(loss, logits)``.  ``mask_out`` (B, 128) float32 device tensor, optional,
+        receives the keep mask used."""
+        x, t, mask = self._prepare(inputs, targets, dropout_mask)
+        b, _, hgt, wid = x.shape
+        p = float(self.model.fc[1].p)
+        offset = self._draws
+        if mask is None:
+            self._draws += 1
+        dev = self.device
+        _lib.check(_lib.load().cough_train_forward_backward(
+            x.data_ptr(), b, hgt, wid, t.data_ptr(), _ptr(self.class_weights), _ptr(mask), self.seed, offset, p,
+            self._params.data_ptr(), self._grads.data_ptr(), self._running.data_ptr(), self._nbt.data_ptr(),
+            self._momentum, self._bn_eps, self._loss.data_ptr(), self._logits.data_ptr(), _ptr(mask_out),
+            self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+            "cough_train_forward_backward")
+        self._invalidate()
+        return self._loss, self._logits
+
+    def step(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask=None):
+        loss, logits = self.forward_backward(inputs, targets, dropout_mask)
+        self.optimizer.step()
+        self._invalidate()
+        return loss, logits
+
+    def _invalidate(self):
+        # the kernels wrote the parameters / buffers behind torch's back (no _version bump): drop the inference handles
+        # so the next eval-mode call re-reads them
+        self.model._handle_key = None
+        for blk in self.model.res_blocks:
+            blk._handle_key = None
+
+
+def train_epoch(trainer: ResidualTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:
+    """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer``: ``{'loss', 'accuracy'}``,
+    the mean batch loss and the percentage of train-mode predictions equal to the target."""
+    trainer.model.train()
+    running_loss, correct, total, n_batches = 0.0, 0, 0, 0
+    for inputs, targets in train_loader:
+        loss, outputs = trainer.step(inputs, targets)
+        running_loss += loss.item()
+        predicted = outputs.argmax(1)
+        total += int(targets.shape[0])
+        correct += int(predicted.eq(torch.as_tensor(targets).to(outputs.device)).sum().item())
+        n_batches += 1
+    return {"loss": running_loss / max(n_batches, 1), "accuracy": 100.0 * correct / max(total, 1)}

@@ -28,7 +28,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* The library is built with -fvisibility=hidden: exactly the entry points declared in this header are exported
+/* The library is built with -fvisibility=hidden: exactly the 49 entry points declared in this header are exported
  * (tests/test_host_logic.py compares `nm -D` of the built library with this list). */
 #pragma GCC visibility push(default)
 
@@ -354,6 +354,42 @@ int cough_augment_waveforms(const float* d_in, long long in_stride, float* d_out
  * [n_rows][2] float32.  An index outside [0, n_rows) yields a NaN row (callers check indices first). */
 int cough_mix_rows(const float* d_x1, const float* d_x2, const int* d_index2, float* d_out, long long n_rows,
                    long long row_len, const float* d_coef, void* stream);
+
+/* ------------------------------------------------------------------ training step (CoughDetectorResidual, channels (32, 64, 128))
+ * One optimisation step as the reference's train_epoch takes it (/root/reference/src/train.py:54-112, built at :420-455):
+ * train-mode forward (BatchNorm on batch statistics, Dropout(p) before the Linear head), CrossEntropyLoss(weight),
+ * backward, clip_grad_norm_(max_norm) and AdamW.  Split in two calls so that the gradients can be read before the
+ * optimizer touches them.  Exact f32; every cross-workgroup reduction runs in a fixed order, so the same inputs and state
+ * give bit-identical losses, gradients and parameters.  Parameters, gradients and the BN state live in caller buffers
+ * (handles stay immutable; nothing here owns state):
+ *   d_params / d_grads  COUGH_TRAIN_NUM_PARAMS float32 in model.parameters() order (30 tensors, PyTorch layouts)
+ *   d_running           COUGH_TRAIN_NUM_RUNNING float32: running_mean then running_var of each BN in model.buffers() order
+ *                       (conv1.1, then per block bn1, bn2, skip.1); d_num_batches: the 7 num_batches_tracked counters
+ * cough_train_forward_backward: d_x [n_clips][height][width] float32 (any image the inference path accepts, and every
+ * BN must see more than one value per channel), d_targets [n_clips] int64 (a target outside {0, 1} makes the loss NaN),
+ * d_class_weights [2] or NULL, dropout keep mask d_dropout_mask [n_clips][128] float32 of 0 / 1 or NULL: drawn on the
+ * device (Philox4x32-10 keyed by seed, counter (channel / 4, clip, offset); keep where u >= p), out = x * mask / (1 - p),
+ * p = 1 gives zeros.  Writes the whole of d_grads (conv biases as the honest sum of dz), the running statistics
+ * (momentum, unbiased variance) and counters, d_loss [1] (weighted mean; NaN when the input holds a non-finite value),
+ * d_logits [n_clips][2] (train-mode outputs), d_mask_out [n_clips][128] (nullable: the keep mask used).
+ * d_workspace: 256-byte aligned, >= cough_train_workspace_bytes(n_clips, height, width) (0 = shape not accepted).
+ * cough_adamw_step: the global L2 norm of d_grads goes to d_total_norm (device float), then one launch scales the
+ * gradients by min(max_norm / (norm + 1e-6), 1) (written back, as clip_grad_norm_ leaves them) and applies
+ * torch.optim.AdamW's update: p *= 1 - lr * wd; m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g^2;
+ * p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps), bc1 = 1 - beta1^step, bc2 = 1 - beta2^step computed by the caller in
+ * double.  The host never waits for the norm.  Every argument is checked before the first launch of either call. */
+#define COUGH_TRAIN_NUM_PARAMS 290370
+#define COUGH_TRAIN_NUM_RUNNING 1216
+size_t cough_train_workspace_bytes(int n_clips, int height, int width);
+int cough_train_forward_backward(const float* d_x, int n_clips, int height, int width, const long long* d_targets,
+                                 const float* d_class_weights, const float* d_dropout_mask, unsigned long long seed,
+                                 unsigned long long offset, float p, const float* d_params, float* d_grads,
+                                 float* d_running, long long* d_num_batches, float momentum, float eps, float* d_loss,
+                                 float* d_logits, float* d_mask_out, void* d_workspace, size_t workspace_bytes,
+                                 void* stream);
+int cough_adamw_step(float* d_params, float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, long long n, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, float max_norm, double bias_correction1,
+                     double bias_correction2, float* d_total_norm, void* stream);
 
 /* ------------------------------------------------------------------ resampler (front of process())
  * Replaces T.Resample(orig, 16000)(waveform) (/root/reference/src/preprocessing.py:146-183): polyphase
