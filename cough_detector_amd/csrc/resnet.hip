@@ -797,8 +797,8 @@ struct cough_resnet {
     float* d_stem_b;       // [32]
     void* d_w[4];          // packed [N][Ktot]: b0.conv1, b0.conv2+skip, b1.conv1, b1.conv2+skip
     cough::bf16_t* d_wfrag[4];   // bf16 mode: the same weights as MFMA fragments [K/16][N/32][64][8] (fused block kernels)
-    cough::bf16_t* d_wx3[2];     // bf16x3 mode: split-bf16 fragments of block i (conv1, projection, conv2; resblock_x3.h)
-    cough::bf16_t* d_wx3t[2];    //   ... and the 16x16x32 fragments of the 16-row tail tile (block 0)
+    cough::bf16_t* d_wx3[2];     // bf16x3 mode: split-bf16 32x32x16 fragments of block i (conv1, projection, conv2; RbxArgs::wf)
+    cough::bf16_t* d_wx3t16;     //   ... and block 0's 16x16x32 fragments (the heights rbx_t16 picks that body for)
     float* d_b[4];
     int ktot[4];
     float* d_fcw;          // [2][128]
@@ -829,12 +829,12 @@ int upload(void** dst, const std::vector<T>& v) {
 }
 
 int upload_x3(cough_resnet* m, int blk, const FoldedConv& c1, const FoldedConv& c2, const FoldedConv& sk) {
-    std::vector<bf16_t> wf, wt;
+    std::vector<bf16_t> wf;
     pack_x3_fragments(wf, c1.w, 9 * c1.C, sk.w, sk.C, c2.w, 9 * c2.C, c1.N);
     if (int e = upload(reinterpret_cast<void**>(&m->d_wx3[blk]), wf)) return e;
-    if ((9 * c1.C) % 32 != 0 || sk.C % 32 != 0) return COUGH_OK;   // no 32-wide k-steps: the kernel has no tail tile
-    pack_x3_tail_fragments(wt, c1.w, 9 * c1.C, sk.w, sk.C, c2.w, 9 * c2.C, c1.N);
-    return upload(reinterpret_cast<void**>(&m->d_wx3t[blk]), wt);
+    if (blk != 0 || !rbx_t16_shape(c1.C, c1.N)) return COUGH_OK;
+    pack_x3_t16_fragments(wf, c1.w, 9 * c1.C, sk.w, sk.C, c2.w, 9 * c2.C, c1.N);
+    return upload(reinterpret_cast<void**>(&m->d_wx3t16), wf);
 }
 
 int upload_packed(cough_resnet* m, int slot, const FoldedConv& main, const FoldedConv* skip) {
@@ -1069,8 +1069,7 @@ int forward_impl(const cough_resnet* m, const float* d_feat, int n, const Shapes
                 RbxArgs ra{};
                 ra.x = reinterpret_cast<const float*>(k.x);
                 ra.n_clips = n;
-                ra.wf = m->d_wx3[i];
-                ra.wt = m->d_wx3t[i];
+                ra.wf = rbx_t16(k.cin, k.cout, k.xh) ? m->d_wx3t16 : m->d_wx3[i];
                 ra.b1 = m->d_b[k.s1];
                 ra.b2 = m->d_b[k.s2];
                 ra.out = reinterpret_cast<float*>(k.out);
@@ -1337,8 +1336,7 @@ extern "C" void cough_resnet_destroy(cough_resnet* m) {
     }
     (void)hipFree(m->d_wx3[0]);
     (void)hipFree(m->d_wx3[1]);
-    (void)hipFree(m->d_wx3t[0]);
-    (void)hipFree(m->d_wx3t[1]);
+    (void)hipFree(m->d_wx3t16);
     (void)hipFree(m->d_fcw);
     (void)hipFree(m->d_fcb);
     delete m;
