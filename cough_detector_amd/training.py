@@ -38,7 +38,7 @@ class HipAdamW(torch.optim.Optimizer):
     ``param_groups`` / ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.AdamW``'s layout (per parameter index:
     ``step``, ``exp_avg``, ``exp_avg_sq``), so a state moves between the two and torch LR schedulers drive ``lr``.  One
     parameter group; its ``lr``, ``betas``, ``eps`` and ``weight_decay`` are read on every ``step()``.  The moments are
-    views of two flat device buffers laid out like the parameters."""
+    views of two flat device buffers laid out like the parameters, and so is every ``p.grad`` (of ``flat_grads``)."""
 
     def __init__(self, params: Sequence[torch.nn.Parameter], flat_params: torch.Tensor, flat_grads: torch.Tensor,
                  lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01, max_norm: float = 1.0):
@@ -54,6 +54,8 @@ class HipAdamW(torch.optim.Optimizer):
         self._n_steps = 0
         self.max_norm = float(max_norm)
         self._bind_state()
+        self._grad_views = [flat_grads[off:off + n].view_as(p) for p, off, n in self._slices()]
+        self.bind_grads()
 
     def _slices(self):
         off = 0
@@ -71,6 +73,19 @@ class HipAdamW(torch.optim.Optimizer):
     def total_norm(self) -> torch.Tensor:
         """The gradient norm of the last step (before clipping), a 1-element device tensor."""
         return self._total_norm
+
+    def zero_grad(self, set_to_none: bool = True):
+        """Zeroes the flat gradient buffer in place.  ``p.grad`` stays its view whatever ``set_to_none`` says: the kernels
+        write the flat buffer, and a ``p.grad`` of ``None`` would hide every later gradient from the caller."""
+        with torch.no_grad():
+            self._flat_grads.zero_()
+        self.bind_grads()
+
+    def bind_grads(self):
+        """Make every ``p.grad`` the view of the flat gradient buffer again (``Module.zero_grad()`` sets it to ``None``)."""
+        for p, g in zip(self.param_groups[0]["params"], self._grad_views):
+            if p.grad is not g:
+                p.grad = g
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -158,7 +173,6 @@ class ResidualTrainer:
                 k = p.numel()
                 self._params[off:off + k].copy_(p.detach().reshape(-1))
                 p.data = self._params[off:off + k].view_as(p)
-                p.grad = self._grads[off:off + k].view_as(p)
                 off += k
             off = 0
             for i, bn in enumerate(bns):
@@ -216,6 +230,7 @@ class ResidualTrainer:
         statistics and counters; returns ``(loss, logits)``.  ``mask_out`` (B, 128) float32 device tensor, optional,
         receives the keep mask used."""
         x, t, mask = self._prepare(inputs, targets, dropout_mask)
+        self.optimizer.bind_grads()          # after a torch-style zero_grad(set_to_none=True) on the module
         b, _, hgt, wid = x.shape
         p = float(self.model.fc[1].p)
         offset = self._draws

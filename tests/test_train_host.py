@@ -11,12 +11,9 @@ import torch
 
 from cough_detector_amd import _lib
 from cough_detector_amd.training import HipAdamW
-from train_ref import PARAM_NAMES, RefStep, golden_sample
+from train_ref import BN_FED_BIASES, PARAM_NAMES, RefStep, golden_sample
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the conv biases that feed a BatchNorm: true gradient 0, the reference's is rounding noise that AdamW turns into
-# updates of up to lr per step -- bounded, never compared
-BN_FED_BIASES = ["conv1.0.bias"] + [f"res_blocks.{i}.{c}.bias" for i in range(2) for c in ("conv1", "conv2", "skip.0")]
 
 
 def load_train_golden():
@@ -149,3 +146,59 @@ def test_training_exports():
     assert cda.ResidualTrainer is not None and callable(cda.train_epoch)
     for s in ("cough_train_workspace_bytes", "cough_train_forward_backward", "cough_adamw_step"):
         assert s in _lib.SYMBOLS
+
+
+def test_trainable_shapes_are_the_ones_torch_accepts(resnet_golden):
+    """cough_train_workspace_bytes / cough_train_forward_backward refuse exactly the (B, H, W) on which the reference's
+    train-mode forward raises (an image too small for the pools, or a BatchNorm with one value per channel).  Only
+    shapes that must be refused reach cough_train_forward_backward (fake pointers: an accepted call would launch)."""
+    lib = _lib.load()
+    sd, _ = resnet_golden
+    ref = RefStep(sd)
+    fake = 1 << 20
+    seen = set()
+    for b in (1, 2, 3):
+        for h in range(1, 13):
+            for w in range(1, 13):
+                x = torch.zeros(b, 1, h, w)
+                try:
+                    with torch.no_grad():
+                        ref.forward(x.double(), torch.ones(b, 128), 0.5)
+                    torch_ok = True
+                except (RuntimeError, ValueError):          # max_pool2d: RuntimeError, batch_norm: ValueError
+                    torch_ok = False
+                wsb = lib.cough_train_workspace_bytes(b, h, w)
+                seen.add((torch_ok, wsb > 0))
+                if torch_ok:
+                    assert wsb > 0, (b, h, w)
+                elif wsb > 0:
+                    rc = lib.cough_train_forward_backward(fake, b, h, w, fake, None, None, 0, 0, 0.5, fake, fake, fake,
+                                                          fake, 0.1, 1e-5, fake, fake, None, 1 << 24, wsb, None)
+                    assert rc == _lib.EINVAL, (b, h, w)
+    assert seen == {(True, True), (False, False), (False, True)}       # all three outcomes occur in this range
+
+
+@pytest.mark.parametrize("set_to_none", [True, False])
+def test_zero_grad_keeps_p_grad_a_view_of_the_flat_buffer(set_to_none):
+    shapes = [(4, 3), (5,), (2, 2, 3)]
+    n = sum(int(np.prod(s)) for s in shapes)
+    flat, grads = torch.randn(n), torch.randn(n)
+    params, off = [], 0
+    for s in shapes:
+        k = int(np.prod(s))
+        params.append(torch.nn.Parameter(flat[off:off + k].view(s)))
+        off += k
+    opt = HipAdamW(params, flat, grads)
+    for p in params:
+        assert p.grad is not None and p.grad.untyped_storage().data_ptr() == grads.untyped_storage().data_ptr()
+    opt.zero_grad(set_to_none=set_to_none)
+    assert torch.count_nonzero(grads) == 0
+    grads.fill_(2.0)
+    for p in params:
+        assert p.grad is not None and torch.equal(p.grad, torch.full(p.shape, 2.0))
+    # Module.zero_grad(set_to_none=True) drops p.grad; the next forward_backward re-binds it (bind_grads)
+    torch.nn.ParameterList(params).zero_grad()
+    assert all(p.grad is None for p in params)
+    opt.bind_grads()
+    assert all(p.grad is not None and p.grad.data_ptr() == grads.data_ptr() + 4 * o
+               for p, o in zip(params, np.cumsum([0] + [int(np.prod(s)) for s in shapes])[:-1]))
