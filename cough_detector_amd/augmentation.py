@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib, _tables
-from .preprocessing import _cuda_device, load_wave
+from ._native import cuda_device
+from .preprocessing import load_wave
 
 
 class SpecAugment:
@@ -66,7 +67,7 @@ class SpecAugment:
         masks = self.draw_masks(spectrogram.shape[-2], spectrogram.shape[-1])
         if not masks:
             return spectrogram
-        dev = _cuda_device()
+        dev = cuda_device()
         src = spectrogram.to(device=dev, dtype=torch.float32).contiguous()
         out = torch.empty_like(src)
         n = len(masks)
@@ -103,7 +104,7 @@ class AudioAugmentor:
     # ------------------------------------------------------------------ noise bank
     def _resample(self, waveform: torch.Tensor, orig_sr: int) -> torch.Tensor:
         """T.Resample(orig_sr, sample_rate) of a (C, N) host tensor on the GPU (``cough_resample``); back on the host."""
-        dev = _cuda_device()
+        dev = cuda_device()
         kern, width, orig, new = _tables.sinc_resample_kernel(orig_sr, self.sample_rate)
         x = waveform.to(device=dev, dtype=torch.float32).contiguous()
         rows, n = x.shape
@@ -145,7 +146,7 @@ class AudioAugmentor:
                            else torch.zeros(0, dtype=torch.float32))
         self._bank_dev = None
         if lengths and torch.cuda.is_available():
-            self._bank_dev = self._bank_host.to(_cuda_device())
+            self._bank_dev = self._bank_host.to(cuda_device())
 
     def _bank_device(self, dev: torch.device) -> torch.Tensor:
         if self._bank_dev is None or self._bank_dev.device != dev:
@@ -198,7 +199,7 @@ class AudioAugmentor:
     def _run(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
              gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
         """One cough_augment_waveforms launch over the rows of the 2-D ``x``; the result where ``x`` lives."""
-        dev = _cuda_device()
+        dev = cuda_device()
         src = x.detach().to(device=dev, dtype=torch.float32)
         if src.stride(-1) != 1 or src.stride(0) < src.shape[1]:
             src = src.contiguous()
@@ -329,7 +330,7 @@ class AudioAugmentor:
 
 def _mix(x1: torch.Tensor, x2: torch.Tensor, lam: np.ndarray, index: Optional[torch.Tensor], who: str) -> torch.Tensor:
     """rows of x1 (B rows, or one row of everything) mixed with rows of x2: one ``cough_mix_rows`` launch."""
-    dev = _cuda_device()
+    dev = cuda_device()
     a = x1.detach().to(device=dev, dtype=torch.float32).contiguous()
     b = x2.detach().to(device=dev, dtype=torch.float32).contiguous()
     rows = len(lam)

@@ -13,15 +13,16 @@ from __future__ import annotations
 
 import warnings
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import NativeModule, conv_bn, cuda_device
 
 
-class ResidualBlock(nn.Module):
+class ResidualBlock(NativeModule):
     """The reference block (``src/model.py:268-293``): conv1/bn1 (3x3, stride s), conv2/bn2 (3x3, stride 1) and ``skip`` --
     a 1x1 stride-s conv + BN when ``stride != 1 or in_channels != out_channels``, ``nn.Identity()`` otherwise (:280-283).
 
@@ -30,7 +31,7 @@ class ResidualBlock(nn.Module):
     conv kernels, eval-mode BatchNorm folded."""
 
     def __init__(self, in_channels: int, out_channels: int, stride: int = 2):
-        super().__init__()
+        super().__init__("cough_resblock_destroy")
         if not 1 <= int(stride) <= 4 or in_channels < 1 or out_channels < 1:
             raise ValueError(f"ResidualBlock: in_channels={in_channels}, out_channels={out_channels}, stride={stride}")
         self.in_channels, self.out_channels, self.stride = int(in_channels), int(out_channels), int(stride)
@@ -40,57 +41,22 @@ class ResidualBlock(nn.Module):
         self.bn2 = nn.BatchNorm2d(out_channels)
         self.skip = nn.Sequential(nn.Conv2d(in_channels, out_channels, 1, stride=stride),
                                   nn.BatchNorm2d(out_channels)) if in_channels != out_channels or stride != 1 else nn.Identity()
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_key = None
-        self._workspace: Optional[torch.Tensor] = None
         self.eval()
 
-    def _release(self):
-        h = self.__dict__.get("_handle")
-        self.__dict__["_handle"] = None
-        if h is not None:
-            try:
-                _lib.load().cough_resblock_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _native(self) -> C.c_void_p:
-        key = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        self._release()
-        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}
-
-        def cb(conv: str, bn: str) -> _lib.ConvBN:
-            return _lib.ConvBN(_lib.fptr(sd[conv + ".weight"]), _lib.fptr(sd[conv + ".bias"]),
-                               _lib.fptr(sd[bn + ".weight"]), _lib.fptr(sd[bn + ".bias"]),
-                               _lib.fptr(sd[bn + ".running_mean"]), _lib.fptr(sd[bn + ".running_var"]))
-
-        c1, c2 = cb("conv1", "bn1"), cb("conv2", "bn2")
-        sk = cb("skip.0", "skip.1") if isinstance(self.skip, nn.Sequential) else None
+    def _create(self) -> C.c_void_p:
+        sd = self._host_weights()
+        c1, c2 = conv_bn(sd, "conv1", "bn1"), conv_bn(sd, "conv2", "bn2")
+        sk = conv_bn(sd, "skip.0", "skip.1") if isinstance(self.skip, nn.Sequential) else None
         h = C.c_void_p()
         _lib.check(_lib.load().cough_resblock_create(C.byref(h), self.in_channels, self.out_channels, self.stride,
                                                       C.byref(c1), C.byref(c2), C.byref(sk) if sk is not None else None,
                                                       float(self.bn1.eps)), "cough_resblock_create")
-        self._handle, self._handle_key = h, key
         return h
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self.training:
-            raise RuntimeError("ResidualBlock on the MI355X path is inference-only: call .eval()")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"expected input (B, {self.in_channels}, H, W), got {tuple(x.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device())
         src_dev = x.device
-        xf = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        xf = self._gpu_input(x, self.in_channels)
+        dev = xf.device
         b, _, hgt, wid = xf.shape
         lib, h = _lib.load(), self._native()
         oh, ow = C.c_int(), C.c_int()
@@ -98,16 +64,13 @@ class ResidualBlock(nn.Module):
         y = torch.empty((b, self.out_channels, oh.value, ow.value), dtype=torch.float32, device=dev)
         if b == 0:
             return y.to(src_dev)
-        need = lib.cough_resblock_workspace_bytes(h, b, hgt, wid)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(lib.cough_resblock_forward(h, xf.data_ptr(), b, hgt, wid, y.data_ptr(), self._workspace.data_ptr(),
-                                              self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream),
-                   "cough_resblock_forward")
+        ws = self._ws.get(max(lib.cough_resblock_workspace_bytes(h, b, hgt, wid), 256), dev)
+        _lib.check(lib.cough_resblock_forward(h, xf.data_ptr(), b, hgt, wid, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream(dev).cuda_stream), "cough_resblock_forward")
         return y.to(src_dev)
 
 
-class CoughDetectorResidual(nn.Module):
+class CoughDetectorResidual(NativeModule):
     """Residual CNN, (B, 1, F, T) float32 -> (B, 2) logits, executed by hand-written gfx950 kernels.
 
     ``compute_dtype``:
@@ -124,7 +87,7 @@ class CoughDetectorResidual(nn.Module):
 
     def __init__(self, n_mels: int = 64, num_classes: int = 2, in_channels: int = 1,
                  channels: Tuple[int, ...] = (32, 64, 128), dropout: float = 0.5, compute_dtype: str = "fp32"):
-        super().__init__()
+        super().__init__("cough_resnet_destroy")
         channels = tuple(int(c) for c in channels)
         if num_classes != 2 or in_channels != 1:
             raise ValueError("CoughDetectorResidual: the MI355X path implements num_classes=2, in_channels=1")
@@ -143,64 +106,22 @@ class CoughDetectorResidual(nn.Module):
             in_ch = out_ch
         self.global_pool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Sequential(nn.Flatten(), nn.Dropout(dropout), nn.Linear(channels[-1], num_classes))
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_key = None
-        self._tensors = None
-        self._workspace: Optional[torch.Tensor] = None
         self.eval()
 
     def _make_res_block(self, in_ch: int, out_ch: int) -> nn.Module:
         return ResidualBlock(in_ch, out_ch)
 
-    # ------------------------------------------------------------------ native handle
-    def _weights_key(self):
-        # cheap per-call staleness check: identity + in-place version counter of every weight tensor
-        # (load_state_dict copies in place and bumps _version; .to()/.cuda() replace .data)
-        if self._tensors is None:
-            self._tensors = list(self.parameters()) + list(self.buffers())
-        return (self.compute_dtype,) + tuple((t.data_ptr(), t._version) for t in self._tensors)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._tensors = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def _release(self):
-        h = self.__dict__.get("_handle")
-        self.__dict__["_handle"] = None          # bypass nn.Module.__setattr__ (safe during interpreter teardown)
-        if h is not None:
-            try:
-                _lib.load().cough_resnet_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _native(self) -> C.c_void_p:
-        key = self._weights_key()
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        self._release()
-        lib = _lib.load()
-        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}
-
-        def cb(conv: str, bn: str) -> _lib.ConvBN:
-            return _lib.ConvBN(_lib.fptr(sd[conv + ".weight"]), _lib.fptr(sd[conv + ".bias"]),
-                               _lib.fptr(sd[bn + ".weight"]), _lib.fptr(sd[bn + ".bias"]),
-                               _lib.fptr(sd[bn + ".running_mean"]), _lib.fptr(sd[bn + ".running_var"]))
-
+    def _create(self) -> C.c_void_p:
+        lib, sd = _lib.load(), self._host_weights()
         h = C.c_void_p()
         if self.channels == (32, 64, 128):
             w = _lib.ResNetWeights()
-            w.stem = cb("conv1.0", "conv1.1")
+            w.stem = conv_bn(sd, "conv1.0", "conv1.1")
             for i in range(2):
                 p = f"res_blocks.{i}"
-                w.block[i].conv1 = cb(p + ".conv1", p + ".bn1")
-                w.block[i].conv2 = cb(p + ".conv2", p + ".bn2")
-                w.block[i].skip = cb(p + ".skip.0", p + ".skip.1")
+                w.block[i].conv1 = conv_bn(sd, p + ".conv1", p + ".bn1")
+                w.block[i].conv2 = conv_bn(sd, p + ".conv2", p + ".bn2")
+                w.block[i].skip = conv_bn(sd, p + ".skip.0", p + ".skip.1")
             w.fc_w = _lib.fptr(sd["fc.2.weight"])
             w.fc_b = _lib.fptr(sd["fc.2.bias"])
             w.bn_eps = float(self.conv1[1].eps)
@@ -211,16 +132,15 @@ class CoughDetectorResidual(nn.Module):
             blocks = (_lib.ResBlockWeights * nb)()
             for i in range(nb):
                 p = f"res_blocks.{i}"
-                blocks[i].conv1 = cb(p + ".conv1", p + ".bn1")
-                blocks[i].conv2 = cb(p + ".conv2", p + ".bn2")
-                blocks[i].skip = cb(p + ".skip.0", p + ".skip.1")
-            stem = cb("conv1.0", "conv1.1")
+                blocks[i].conv1 = conv_bn(sd, p + ".conv1", p + ".bn1")
+                blocks[i].conv2 = conv_bn(sd, p + ".conv2", p + ".bn2")
+                blocks[i].skip = conv_bn(sd, p + ".skip.0", p + ".skip.1")
+            stem = conv_bn(sd, "conv1.0", "conv1.1")
             chans = (C.c_int * (nb + 1))(*self.channels)
             dtype = _lib.DTYPES[self.compute_dtype]
             _lib.check(lib.cough_resnet_create_ex(C.byref(h), nb, chans, C.byref(stem), blocks, _lib.fptr(sd["fc.2.weight"]),
                                                   _lib.fptr(sd["fc.2.bias"]), float(self.conv1[1].eps), dtype),
                        "cough_resnet_create_ex")
-        self._handle, self._handle_key = h, key
         return h
 
     # ------------------------------------------------------------------ forward
@@ -258,24 +178,16 @@ class CoughDetectorResidual(nn.Module):
                           f"See effective_dtype().", UserWarning, stacklevel=4)
 
     def _run(self, x: torch.Tensor, want_probs: bool):
-        if self.training:
-            raise RuntimeError("CoughDetectorResidual on the MI355X path is inference-only: call .eval()")
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise ValueError(f"expected input (B, 1, F, T), got {tuple(x.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device())
         src_dev = x.device
-        xf = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        xf = self._gpu_input(x)
+        dev = xf.device
         b, _, hgt, wid = xf.shape
         if b == 0:
             z = torch.empty((0, 2), dtype=torch.float32, device=src_dev)
             return (z, z.clone(), torch.empty((0,), dtype=torch.int32, device=src_dev)) if want_probs else z
         self._warn_fallback(hgt, wid)
         lib, h = _lib.load(), self._native()
-        need = lib.cough_resnet_workspace_bytes(h, b, hgt, wid)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        ws = self._ws.get(max(lib.cough_resnet_workspace_bytes(h, b, hgt, wid), 256), dev, note=(b, hgt, wid))
         logits = torch.empty((b, 2), dtype=torch.float32, device=dev)
         probs = torch.empty((b, 2), dtype=torch.float32, device=dev) if want_probs else None
         preds = torch.empty((b,), dtype=torch.int32, device=dev) if want_probs else None
@@ -283,9 +195,8 @@ class CoughDetectorResidual(nn.Module):
         _lib.check(lib.cough_resnet_forward(h, xf.data_ptr(), b, hgt, wid, logits.data_ptr(),
                                             probs.data_ptr() if want_probs else None,
                                             preds.data_ptr() if want_probs else None,
-                                            self._workspace.data_ptr(), self._workspace.numel(), stream),
+                                            ws.data_ptr(), ws.numel(), stream),
                    "cough_resnet_forward")
-        self._last_shape = (b, hgt, wid)
         if want_probs:
             return logits.to(src_dev), probs.to(src_dev), preds.to(src_dev)
         return logits.to(src_dev)
@@ -298,18 +209,22 @@ class CoughDetectorResidual(nn.Module):
         return preds.to(torch.int64), probs
 
     def read_activation(self, which: int) -> torch.Tensor:
-        """Parity tap: activation after the stem (1), block 0 (2), block 1 (3), ... of the last forward, NCHW f32."""
-        b, hgt, wid = self._last_shape
+        """Parity tap: activation after the stem (1), block 0 (2), block 1 (3), ... of the last forward on the current
+        stream, NCHW f32."""
         if not 1 <= which <= len(self.channels):
             raise ValueError(f"which must be 1..{len(self.channels)}")
+        dev = cuda_device()
+        last = self._ws.lookup(dev)
+        if last is None:
+            raise RuntimeError("read_activation: no forward of this model has run on the current stream")
+        ws, (b, hgt, wid) = last
         c = self.channels[which - 1]
         oh, ow = ((hgt - 1) // 2 + 1) // 2, ((wid - 1) // 2 + 1) // 2
         for _ in range(which - 1):
             oh, ow = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
-        out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=self._workspace.device)
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        _lib.check(_lib.load().cough_resnet_read_activation(self._native(), self._workspace.data_ptr(), b, hgt, wid,
-                                                            which, out.data_ptr(), stream),
+        out = torch.empty((b, c, oh, ow), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().cough_resnet_read_activation(self._native(), ws.data_ptr(), b, hgt, wid, which,
+                                                            out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
                    "cough_resnet_read_activation")
         return out
 
@@ -331,57 +246,27 @@ class ConvBlock(nn.Module):
         raise RuntimeError("ConvBlock is executed inside CoughDetector.forward on the MI355X path")
 
 
-class _ConvStackNet(nn.Module):
-    """Shared host side of the two conv-stack classifiers: owns the ``cough_cnn`` handle and the workspace;
-    subclasses describe their blocks (``_describe``) in terms of their own state_dict keys."""
+class _ConvStackNet(NativeModule):
+    """Shared host side of the two conv-stack classifiers: builds the ``cough_cnn`` handle; subclasses describe their
+    blocks (``_describe``) in terms of their own state_dict keys."""
+
+    def __init__(self):
+        super().__init__("cough_cnn_destroy")
 
     def _init_native(self, compute_dtype: str):
         # "fp32" (exact-f32 MFMA) and "bf16x3" (split-bf16: hi + lo operands, three MFMAs per k-step, f32 activations
         # in HBM) are the parity-grade modes; the single-bf16 mode is approximate and has to be asked for by that name
         # ('bf16' = deprecated alias, warns)
         self.compute_dtype = _lib.normalize_dtype(compute_dtype, ("fp32", "bf16x3", "bf16_approx"))
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_key = None
-        self._tensors = None
-        self._workspace: Optional[torch.Tensor] = None
         self.eval()
-
-    def _weights_key(self):
-        if self._tensors is None:
-            self._tensors = list(self.parameters()) + list(self.buffers())
-        return (self.compute_dtype,) + tuple((t.data_ptr(), t._version) for t in self._tensors)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._tensors = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def _release(self):
-        h = self.__dict__.get("_handle")
-        self.__dict__["_handle"] = None
-        if h is not None:
-            try:
-                _lib.load().cough_cnn_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def _describe(self, sd: Dict[str, torch.Tensor]):
         """-> (blocks, fc1 prefix, fc2 prefix, bn eps); a block is (conv prefix, bn prefix, depthwise prefix | None,
         pool)."""
         raise NotImplementedError
 
-    def _native(self) -> C.c_void_p:
-        key = self._weights_key()
-        if self._handle is not None and key == self._handle_key:
-            return self._handle
-        self._release()
-        lib = _lib.load()
-        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}
+    def _create(self) -> C.c_void_p:
+        sd = self._host_weights()
         blocks, fc1, fc2, eps = self._describe(sd)
         arr = (_lib.CnnBlock * len(blocks))()
         for i, (conv, bn, dw, pool) in enumerate(blocks):
@@ -390,38 +275,31 @@ class _ConvStackNet(nn.Module):
             if dw is not None:
                 arr[i].cin = int(sd[dw + ".weight"].shape[0])
                 arr[i].dw_w, arr[i].dw_b = _lib.fptr(sd[dw + ".weight"]), _lib.fptr(sd[dw + ".bias"])
-            arr[i].conv = _lib.ConvBN(_lib.fptr(w), _lib.fptr(sd[conv + ".bias"]), _lib.fptr(sd[bn + ".weight"]),
-                                      _lib.fptr(sd[bn + ".bias"]), _lib.fptr(sd[bn + ".running_mean"]),
-                                      _lib.fptr(sd[bn + ".running_var"]))
+            arr[i].conv = conv_bn(sd, conv, bn)
         cw = _lib.CnnWeights(len(blocks), arr, int(sd[fc1 + ".weight"].shape[0]), _lib.fptr(sd[fc1 + ".weight"]),
                              _lib.fptr(sd[fc1 + ".bias"]), _lib.fptr(sd[fc2 + ".weight"]), _lib.fptr(sd[fc2 + ".bias"]),
                              float(eps))
         h = C.c_void_p()
-        _lib.check(lib.cough_cnn_create(C.byref(h), C.byref(cw), _lib.DTYPES[self.compute_dtype]), "cough_cnn_create")
-        self._handle, self._handle_key = h, key
+        _lib.check(_lib.load().cough_cnn_create(C.byref(h), C.byref(cw), _lib.DTYPES[self.compute_dtype]),
+                   "cough_cnn_create")
         return h
 
     def _prepare(self, x: torch.Tensor):
-        if self.training:
-            raise RuntimeError(f"{type(self).__name__} on the MI355X path is inference-only: call .eval()")
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise ValueError(f"expected input (B, 1, F, T), got {tuple(x.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950); there is no CPU fallback")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        xf = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        """-> (lib, handle, x on the GPU, workspace or None for an empty batch)"""
+        xf = self._gpu_input(x)
         b, _, hgt, wid = xf.shape
         lib, h = _lib.load(), self._native()
-        need = lib.cough_cnn_workspace_bytes(h, b, hgt, wid) if b else 0
-        if b and need == 0:
+        if not b:
+            return lib, h, xf, None
+        need = lib.cough_cnn_workspace_bytes(h, b, hgt, wid)
+        if need == 0:
             raise ValueError(f"input {hgt}x{wid} is too small for the network")
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-            self._workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        return lib, h, xf, dev
+        return lib, h, xf, self._ws.get(max(need, 256), xf.device)
 
     def _run(self, x: torch.Tensor, want_probs: bool):
         src_dev = x.device
-        lib, h, xf, dev = self._prepare(x)
+        lib, h, xf, ws = self._prepare(x)
+        dev = xf.device
         b, _, hgt, wid = xf.shape
         logits = torch.empty((b, 2), dtype=torch.float32, device=dev)
         probs = torch.empty((b, 2), dtype=torch.float32, device=dev) if want_probs else None
@@ -429,8 +307,8 @@ class _ConvStackNet(nn.Module):
         if b:
             _lib.check(lib.cough_cnn_forward(h, xf.data_ptr(), b, hgt, wid, logits.data_ptr(),
                                              probs.data_ptr() if want_probs else None,
-                                             preds.data_ptr() if want_probs else None, self._workspace.data_ptr(),
-                                             self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                                             preds.data_ptr() if want_probs else None, ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream(dev).cuda_stream),
                        "cough_cnn_forward")
         if want_probs:
             return logits.to(src_dev), probs.to(src_dev), preds.to(src_dev)
@@ -445,16 +323,16 @@ class _ConvStackNet(nn.Module):
 
     def conv_output(self, x: torch.Tensor) -> torch.Tensor:
         """Parity tap: output of the conv stack before the global mean, (B, C, h, w) float32."""
-        lib, h, xf, dev = self._prepare(x)
+        lib, h, xf, ws = self._prepare(x)
+        dev = xf.device
         b, _, hgt, wid = xf.shape
         oh, ow = hgt, wid
         for _ in range(self._n_pools):
             oh, ow = oh // 2, ow // 2
         out = torch.empty((b, self._out_channels, oh, ow), dtype=torch.float32, device=dev)
         if b:
-            _lib.check(lib.cough_cnn_conv_output(h, xf.data_ptr(), b, hgt, wid, out.data_ptr(), self._workspace.data_ptr(),
-                                                 self._workspace.numel(), torch.cuda.current_stream(dev).cuda_stream),
-                       "cough_cnn_conv_output")
+            _lib.check(lib.cough_cnn_conv_output(h, xf.data_ptr(), b, hgt, wid, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 torch.cuda.current_stream(dev).cuda_stream), "cough_cnn_conv_output")
         return out
 
 

@@ -12,14 +12,15 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._native import StreamScratch, cuda_device
 from .model import CoughDetectorResidual
-from .preprocessing import AudioPreprocessor, _cuda_device
+from .preprocessing import AudioPreprocessor
 
 
 class CoughPipeline:
     def __init__(self, preprocessor: AudioPreprocessor, model: torch.nn.Module):
         self.pre, self.model = preprocessor, model
-        self._ws = {}   # stream -> workspace: threads / streams sharing this pipeline never share scratch
+        self._ws = StreamScratch()   # per stream: threads / streams sharing this pipeline never share scratch
 
     def _run(self, waveforms: torch.Tensor, normalize: bool, want_probs: bool, return_features: bool,
              events: Optional[Tuple[torch.cuda.Event, torch.cuda.Event]] = None):
@@ -28,7 +29,7 @@ class CoughPipeline:
         n_samples = self.pre.segment_samples
         if waveforms.dim() != 2 or waveforms.shape[1] != n_samples:
             raise ValueError(f"expected (B, {n_samples}) waveforms, got {tuple(waveforms.shape)}")
-        dev = _cuda_device()
+        dev = cuda_device()
         w = waveforms.to(device=dev, dtype=torch.float32)
         if w.stride(1) != 1 or w.stride(0) % 4 != 0 or w.data_ptr() % 16 != 0:
             w = w.contiguous()
@@ -57,11 +58,7 @@ class CoughPipeline:
             lib, fh, mh = _lib.load(), self.pre._native(), self.model._native()
             need = lib.cough_pipeline_workspace_bytes(fh, mh, b)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = self._ws.get(stream)
-            if ws is None or ws.numel() < need or ws.device != dev:
-                if ws is None and len(self._ws) >= 8:
-                    self._ws.pop(next(iter(self._ws)))
-                ws = self._ws[stream] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+            ws = self._ws.get(max(need, 256), dev)
             _lib.check(lib.cough_pipeline_forward(
                 fh, mh, w.data_ptr(), w.stride(0) if b > 1 else n_samples, b, _lib.FEAT_NORMALIZE if normalize else 0,
                 feats.data_ptr() if return_features else None, logits.data_ptr(),

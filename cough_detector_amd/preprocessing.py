@@ -31,13 +31,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib, _tables
-
-
-def _cuda_device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950): torch.cuda.is_available() is False "
-                           "and there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+from ._native import NativeHandle, StreamScratch, cuda_device
 
 
 def _check_waveform(w, who: str) -> None:
@@ -148,9 +142,9 @@ class AudioPreprocessor:
         self._window = _tables.hann_window(win_length)
         self._mel_fb = _tables.mel_filterbank(n_fft // 2 + 1, f_min, f_max, n_mels, sample_rate)
         self._dct = _tables.dct_matrix(n_mfcc, n_mels)
-        self._handle: Optional[C.c_void_p] = None
-        self._handle_lock = threading.Lock()
-        self._ws = {}                               # stream -> scratch of the spectral-contrast rows / the generic kernel chain
+        self._handle = NativeHandle("cough_featurizer_destroy")
+        self._ws = StreamScratch()                  # per stream: scratch of the spectral-contrast rows / the generic kernel chain
+        self._plain_lock = threading.Lock()
         self._resamplers = {}
         self._plain: Optional["AudioPreprocessor"] = None   # helper methods: the same transforms without pre-emphasis / contrast
 
@@ -160,11 +154,7 @@ class AudioPreprocessor:
         ``extract_features`` takes a waveform of ANY length (T = 1 + N // hop_length, ``src/preprocessing.py:432-489``) -- so the
         length is a launch parameter (``cough_featurize_any``): the constructor's segment runs on the tuned kernel where there is
         one, every other length on the generic kernel chain, with the same tables."""
-        if self._handle is None:
-            with self._handle_lock:
-                if self._handle is None:
-                    self._handle = self._create_handle(self.segment_samples)
-        return self._handle
+        return self._handle.get(None, lambda: self._create_handle(self.segment_samples))
 
     def kernel_path(self) -> str:
         """Which kernels featurise ``segment_samples`` windows: "tuned" (one launch, the shipped sparse filterbank),
@@ -177,22 +167,9 @@ class AudioPreprocessor:
             raise ValueError(f"a waveform of {n_samples} samples is shorter than the reflect padding of "
                              f"torch.stft(center=True) (needs more than n_fft // 2 = {self.n_fft // 2})")
 
-    MAX_STREAM_WORKSPACES = 8
-
-    def _workspace(self, need: int, dev: torch.device, stream: int) -> torch.Tensor:
-        """Scratch for one launch on ``stream``.  One buffer per stream: two threads / streams sharing this preprocessor never
-        share scratch (``include/cough_amd.h``: "each with its own workspace and stream"), and a buffer that is replaced goes back
-        to torch's caching allocator, which hands it out again only in stream order."""
-        ws = self._ws.get(stream)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            if ws is None and len(self._ws) >= self.MAX_STREAM_WORKSPACES:
-                self._ws.pop(next(iter(self._ws)))
-            ws = self._ws[stream] = torch.empty(need, dtype=torch.uint8, device=dev)
-        return ws
-
     def _create_handle(self, n_samples: int) -> C.c_void_p:
         lib = _lib.load()
-        _cuda_device()
+        cuda_device()
         cfg = _lib.FeatConfig(self.sample_rate, self.n_fft, self.hop_length, self.win_length, self.n_mels,
                               self.n_mfcc, n_samples, int(bool(self.use_pre_emphasis)),
                               float(self.pre_emphasis_coef), int(bool(self.use_delta_delta)),
@@ -208,14 +185,6 @@ class AudioPreprocessor:
                    "cough_featurizer_create")
         return h
 
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h is not None:
-            try:
-                _lib.load().cough_featurizer_destroy(h)
-            except Exception:
-                pass
-
     # ------------------------------------------------------------------ reference helpers (host plumbing)
     def load_audio(self, path: str):
         """``torchaudio.load(path)`` for RIFF/WAVE files (src/preprocessing.py:155-166): (channels, samples) float32 in
@@ -229,7 +198,7 @@ class AudioPreprocessor:
         if orig_sr == self.sample_rate:
             return waveform
         import math
-        dev = _cuda_device()
+        dev = cuda_device()
         if orig_sr not in self._resamplers:          # kernel table cached per source rate, like the reference (:144-153)
             kern, width, orig, new = _tables.sinc_resample_kernel(orig_sr, self.sample_rate)
             self._resamplers[orig_sr] = (kern.to(dev), width, orig, new)
@@ -247,7 +216,7 @@ class AudioPreprocessor:
         return out
 
     def _prepare(self, waveform: torch.Tensor, out_len: int, normalize: bool) -> torch.Tensor:
-        dev = _cuda_device()
+        dev = cuda_device()
         w = waveform.to(device=dev, dtype=torch.float32)
         if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] < 1:
             raise ValueError(f"expected (channels, samples), got {tuple(waveform.shape)}")
@@ -275,7 +244,7 @@ class AudioPreprocessor:
 
     def _rows_op(self, x: torch.Tensor, launch) -> torch.Tensor:
         """Run a row-wise kernel over the last axis of ``x`` on the GPU; the result comes back where ``x`` lives."""
-        dev = _cuda_device()
+        dev = cuda_device()
         xin = x.detach().to(device=dev, dtype=torch.float32).contiguous()
         out = torch.empty_like(xin)
         if xin.numel():
@@ -344,7 +313,7 @@ class AudioPreprocessor:
 
     # ------------------------------------------------------------------ the hot path
     def _out_device(self, like: torch.Tensor) -> torch.device:
-        return torch.device("cpu") if str(self.device) == "cpu" else _cuda_device()
+        return torch.device("cpu") if str(self.device) == "cpu" else cuda_device()
 
     def featurize_batch(self, waveforms: torch.Tensor, normalize: bool = False,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -356,7 +325,7 @@ class AudioPreprocessor:
             raise ValueError(f"featurize_batch: expected (B, N), got {tuple(waveforms.shape)}")
         n_samples = waveforms.shape[1]
         self._check_length(n_samples)
-        dev = _cuda_device()
+        dev = cuda_device()
         w = waveforms.to(device=dev, dtype=torch.float32)
         if w.stride(1) != 1 or w.stride(0) % 4 != 0 or w.data_ptr() % 16 != 0:
             w = w.contiguous()
@@ -372,7 +341,7 @@ class AudioPreprocessor:
         stride = w.stride(0) if b > 1 else n_samples
         lib, h = _lib.load(), self._native()
         need = lib.cough_featurizer_workspace_bytes_for(h, n_samples, b)   # non-zero with spectral contrast / on the generic chain
-        ws = self._workspace(need, dev, stream) if need else None
+        ws = self._ws.get(need, dev) if need else None
         _lib.check(lib.cough_featurize_any(h, w.data_ptr(), stride, n_samples, out.data_ptr(), b,
                                            _lib.FEAT_NORMALIZE if normalize else 0,
                                            ws.data_ptr() if need else None, need, stream), "cough_featurize_any")
@@ -391,7 +360,7 @@ class AudioPreprocessor:
         self._check_length(n_samples)
         if power not in (1.0, 2.0):
             raise ValueError("spectrogram_batch: power must be 1.0 or 2.0")
-        dev = _cuda_device()
+        dev = cuda_device()
         w = waveforms.to(device=dev, dtype=torch.float32)
         if w.stride(1) != 1 or w.stride(0) % 4 != 0 or w.data_ptr() % 16 != 0:
             w = w.contiguous()
@@ -424,7 +393,7 @@ class AudioPreprocessor:
         pre-emphasis in extract_features only (src/preprocessing.py:455-459), not in these methods (:387-430)."""
         if not self.use_pre_emphasis:
             return self
-        with self._handle_lock:
+        with self._plain_lock:
             if self._plain is None:
                 self._plain = AudioPreprocessor(
                     sample_rate=self.sample_rate, n_mels=self.n_mels, n_fft=self.n_fft, hop_length=self.hop_length,

@@ -121,12 +121,15 @@ class MultiStreamDetector:
                 classify()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
+        # captured on the warm-up stream: the launches use the workspaces the warm-up allocated, which the record keeps alive
         g["write"], g["full"] = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g["write"]):
+        with torch.cuda.graph(g["write"], stream=side):
             write()
-        with torch.cuda.graph(g["full"]):
+        with torch.cuda.graph(g["full"], stream=side):
             write()
             classify()
+        with torch.cuda.stream(side):
+            g["workspaces"] = [s.lookup(dev) for s in (self.pipe._ws, self.pre._ws, self.model._ws)]
         self.rings.copy_(rings_before)             # the warm-up wrote h_chunks garbage at position 0
         g["done"] = torch.cuda.Event()
         g["done"].record()

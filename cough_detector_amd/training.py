@@ -184,7 +184,7 @@ class ResidualTrainer:
                 bn.running_var = self._running[off + c:off + 2 * c]
                 bn.num_batches_tracked = self._nbt[i]
                 off += 2 * c
-        model._tensors = None
+        model.invalidate()                   # the parameters and BN buffers are other tensors now
         self._momentum, self._bn_eps = float(bns[0].momentum), float(bns[0].eps)
         self.class_weights = None
         if class_weights is not None:
@@ -243,21 +243,16 @@ class ResidualTrainer:
             self._momentum, self._bn_eps, self._loss.data_ptr(), self._logits.data_ptr(), _ptr(mask_out),
             self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
             "cough_train_forward_backward")
-        self._invalidate()
+        # the kernels wrote the parameters / buffers behind torch's back (no _version bump): drop the inference handles
+        # so the next eval-mode call re-reads them
+        self.model.invalidate()
         return self._loss, self._logits
 
     def step(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask=None):
         loss, logits = self.forward_backward(inputs, targets, dropout_mask)
         self.optimizer.step()
-        self._invalidate()
+        self.model.invalidate()
         return loss, logits
-
-    def _invalidate(self):
-        # the kernels wrote the parameters / buffers behind torch's back (no _version bump): drop the inference handles
-        # so the next eval-mode call re-reads them
-        self.model._handle_key = None
-        for blk in self.model.res_blocks:
-            blk._handle_key = None
 
 
 def train_epoch(trainer: ResidualTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:

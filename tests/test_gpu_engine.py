@@ -144,7 +144,8 @@ def test_multi_stream_detector_matches_per_stream_oracles():
 
 def test_graph_replay_equals_eager_launches():
     """The captured steady state (two HIP graphs) must give the probabilities of the eager launch chain bit for bit,
-    including ticks that fall back to eager (a subset of streams, a longer chunk) in between."""
+    including ticks that fall back to eager (a subset of streams, a longer chunk) in between.  The graphs are captured on
+    the warm-up stream, so the pipeline keeps scratch for two streams only: the eager one and the warm-up one."""
     from cough_detector_amd.streaming import MultiStreamDetector
     sd = synth.random_state_dict(seed=5)
     S = 6
@@ -166,6 +167,9 @@ def test_graph_replay_equals_eager_launches():
                 events.append(det.push(streams[:, pos:pos + 1600]))
             pos += 1600
         runs.append(([list(p) for p in det.window_probs], events, det._g is not None))
+        if use_graphs:
+            assert len(det.pipe._ws) == 2 and det.pipe._ws.lookup(det.dev) is not None
+            assert det._g["workspaces"][0] is not None        # the warm-up stream's, held by the graphs
     (pg, eg, used), (pe, ee, unused) = runs
     assert used and not unused                            # the graph path really ran
     assert all(len(p) == 9 for p in pg)

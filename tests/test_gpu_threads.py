@@ -75,13 +75,9 @@ def test_consumer_thread_fed_by_a_queue_matches_the_engine_oracle(tmp_path):
     assert np.abs(np.array([c for _, c in hits]) - np.array([c for _, c in ref_hits])).max() < 1e-3
 
 
-def test_two_threads_share_immutable_handles_on_separate_streams():
-    sd = realistic_state_dict(11)
-    pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
-    model = cda.create_model("residual", n_mels=90, num_classes=2, in_channels=1, compute_dtype="bf16x3")
-    model.load_state_dict(sd)
-    model.cuda().eval()
-    batches = [synth_batch(7000 + 600 * k, 300 + 17 * k, peak_normalize=False).cuda() for k in range(2)]
+def _two_threads_agree(pre, model, batches):
+    """Two threads, each with its own CoughPipeline and stream, score their batch through the shared handles 40 times,
+    through the pipeline and through featurize_batch + model; every result must equal the serial run bit for bit."""
     serial = [cda.CoughPipeline(pre, model)(b, normalize=True).clone() for b in batches]     # also creates the handles
     torch.cuda.synchronize()
     results, errors = [None, None], []
@@ -97,7 +93,7 @@ def test_two_threads_share_immutable_handles_on_separate_streams():
                 for _ in range(40):                           # overlapping launches from both threads
                     ok &= bool(torch.equal(pipe(batches[k], normalize=True), serial[k]))
                     feats = pre.featurize_batch(batches[k], normalize=True)
-                    ok &= bool(torch.equal(model(feats.unsqueeze(1)), serial[k])) if k == 0 else True
+                    ok &= bool(torch.equal(model(feats.unsqueeze(1)), serial[k]))
             s.synchronize()
             results[k] = ok
         except Exception as e:
@@ -110,6 +106,28 @@ def test_two_threads_share_immutable_handles_on_separate_streams():
         t.join(timeout=300)
     assert not errors, errors
     assert results == [True, True]
+
+
+def test_two_threads_share_immutable_handles_on_separate_streams():
+    sd = realistic_state_dict(11)
+    pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
+    model = cda.create_model("residual", n_mels=90, num_classes=2, in_channels=1, compute_dtype="bf16x3")
+    model.load_state_dict(sd)
+    model.cuda().eval()
+    batches = [synth_batch(7000 + 600 * k, 300 + 17 * k, peak_normalize=False).cuda() for k in range(2)]
+    _two_threads_agree(pre, model, batches)
+
+
+def test_two_pipelines_share_a_conv_stack_model_on_separate_streams(cnn_golden):
+    """CoughPipeline runs a conv-stack classifier through the model's own launch, so the model's scratch is per stream
+    too: two pipelines sharing one CoughDetectorSmall from two threads must not share it."""
+    sd, _ = cnn_golden["small"]
+    pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
+    model = cda.create_model("small", n_mels=90, num_classes=2, in_channels=1, compute_dtype="bf16x3")
+    model.load_state_dict(sd)
+    model.cuda().eval()
+    batches = [synth_batch(7100 + 600 * k, 300 + 17 * k, peak_normalize=False).cuda() for k in range(2)]
+    _two_threads_agree(pre, model, batches)
 
 
 @pytest.mark.parametrize("kw", [dict(n_fft=400, n_mels=40), dict(hop_length=200, n_mels=40),
