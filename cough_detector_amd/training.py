@@ -1,4 +1,4 @@
-"""Training of ``CoughDetectorResidual`` on the MI355X: one optimisation step as the reference's ``train_epoch`` takes it
+"""Training of ``CoughDetectorResidual`` and ``CoughDetectorSmall`` on the MI355X: one optimisation step as the reference's ``train_epoch`` takes it
 (``/root/reference/src/train.py:54-112``, built at :420-455)::
 
     optimizer.zero_grad(); outputs = model(inputs)            # train mode: batch-statistics BN, Dropout(p)
@@ -6,13 +6,14 @@
     clip_grad_norm_(model.parameters(), max_norm); AdamW(lr, betas, eps, weight_decay).step()
 
 The forward, backward and optimizer arithmetic runs in ``csrc/train.hip`` (``cough_train_forward_backward``,
-``cough_adamw_step``); torch only allocates memory and supplies the stream.  The trainer makes the module's parameters,
+``cough_adamw_step``) and ``csrc/train_small.hip`` (``cough_train_small_forward_backward``); torch only allocates memory and supplies the stream.  The trainer makes the module's parameters,
 gradients (``p.grad``) and BatchNorm buffers views of flat device buffers that the kernels update in place, so
 ``model.state_dict()`` holds the trained state after every step and ``model.eval()(x)`` runs the inference kernels on it.
 ``model.train()(x)`` still refuses: training goes through the trainer.
 
 Non-finite input gives a NaN loss; the step then leaves NaN gradients and parameters (as torch's own step does: the clip
-coefficient of a NaN norm does not rescue them).  Shipped channels ``(32, 64, 128)`` only.
+coefficient of a NaN norm does not rescue them).  The residual net trains with its shipped channels ``(32, 64, 128)``
+only; ``create_trainer`` picks the trainer of a model.
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .model import CoughDetectorResidual
+from .model import CoughDetector, CoughDetectorResidual, CoughDetectorSmall
 
 SHIPPED_CHANNELS = (32, 64, 128)
 
@@ -129,43 +130,43 @@ class HipAdamW(torch.optim.Optimizer):
         self._bind_state()
 
 
-class ResidualTrainer:
-    """Trains a ``CoughDetectorResidual`` (``channels=(32, 64, 128)``) with the reference's ``train_epoch`` step.
+class _FlatTrainer:
+    """What the HIP trainers share: the module's parameters, gradients and BN buffers become views of flat device
+    buffers, a ``HipAdamW`` over them, and one forward / backward entry point of the C-ABI per model.  Subclasses set
+    the model class, the layout constants and the entry points, and check the model (``_check``)."""
 
-    ``step(inputs, targets, dropout_mask=None) -> (loss, logits)``: ``inputs`` (B, 1, F, T) float32, ``targets`` (B,)
-    int64 class indices; ``dropout_mask`` (B, 128) of 0 / 1 keeps, or ``None`` for the device generator (Philox keyed by
-    ``seed``, one new draw per step).  ``loss`` is a 0-d device tensor, ``logits`` the train-mode outputs; both are
-    buffers of the trainer, overwritten by the next step at the same shape (read them, e.g. ``loss.item()``, first).
-    No host synchronisation; no allocation after the first step at a given (B, F, T)."""
+    _model_cls = None
+    _name = ""
+    _n_tensors = _n_params = _n_running = _n_bns = _mask_width = 0
+    _ws_fn = _fb_fn = ""
 
-    def __init__(self, model: CoughDetectorResidual, lr: float = 1e-3, weight_decay: float = 0.01,
-                 betas=(0.9, 0.999), eps: float = 1e-8, class_weights=None, max_norm: float = 1.0, seed: int = 0):
-        if not isinstance(model, CoughDetectorResidual):
-            raise TypeError("ResidualTrainer trains a CoughDetectorResidual")
-        if tuple(model.channels) != SHIPPED_CHANNELS:
-            raise ValueError(f"ResidualTrainer: channels={tuple(model.channels)}; the training kernels are built for "
-                             f"{SHIPPED_CHANNELS}")
+    def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
+                 class_weights=None, max_norm: float = 1.0, seed: int = 0):
+        name = self._name
+        if not isinstance(model, self._model_cls):
+            raise TypeError(f"{name} trains a {self._model_cls.__name__}")
+        self._check(model)
         if not torch.cuda.is_available():
             raise RuntimeError("cough_detector_amd needs an AMD GPU (gfx950); there is no CPU fallback")
         if max_norm <= 0:
-            raise ValueError("ResidualTrainer: max_norm must be > 0")
+            raise ValueError(f"{name}: max_norm must be > 0")
         bns = [m for m in model.modules() if isinstance(m, nn.BatchNorm2d)]
-        if len(bns) != 7 or any(b.momentum is None or not b.track_running_stats or not b.affine for b in bns):
-            raise ValueError("ResidualTrainer: every BatchNorm needs affine=True, track_running_stats=True and a momentum")
+        if len(bns) != self._n_bns or any(b.momentum is None or not b.track_running_stats or not b.affine for b in bns):
+            raise ValueError(f"{name}: every BatchNorm needs affine=True, track_running_stats=True and a momentum")
         if len({(float(b.momentum), float(b.eps)) for b in bns}) != 1:
-            raise ValueError("ResidualTrainer: all BatchNorm layers must share momentum and eps")
+            raise ValueError(f"{name}: all BatchNorm layers must share momentum and eps")
         self.model = model
         self.device = torch.device("cuda", torch.cuda.current_device())
         dev = self.device
         model.to(dev)
         params = list(model.parameters())
         n = sum(p.numel() for p in params)
-        if len(params) != 30 or n != _lib.TRAIN_NUM_PARAMS:
-            raise ValueError(f"ResidualTrainer: {len(params)} parameter tensors / {n} values, expected 30 / "
-                             f"{_lib.TRAIN_NUM_PARAMS}")
+        if len(params) != self._n_tensors or n != self._n_params:
+            raise ValueError(f"{name}: {len(params)} parameter tensors / {n} values, expected {self._n_tensors} / "
+                             f"{self._n_params}")
         self._params = torch.empty(n, dtype=torch.float32, device=dev)
         self._grads = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._running = torch.empty(_lib.TRAIN_NUM_RUNNING, dtype=torch.float32, device=dev)
+        self._running = torch.empty(self._n_running, dtype=torch.float32, device=dev)
         self._nbt = torch.empty(len(bns), dtype=torch.int64, device=dev)
         with torch.no_grad():
             off = 0
@@ -190,7 +191,7 @@ class ResidualTrainer:
         if class_weights is not None:
             cw = torch.as_tensor(class_weights, dtype=torch.float32).to(dev).reshape(-1).contiguous()
             if cw.numel() != 2:
-                raise ValueError("ResidualTrainer: class_weights needs one weight per class (2)")
+                raise ValueError(f"{name}: class_weights needs one weight per class (2)")
             self.class_weights = cw
         self.optimizer = HipAdamW(params, self._params, self._grads, lr=lr, betas=betas, eps=eps,
                                   weight_decay=weight_decay, max_norm=max_norm)
@@ -198,6 +199,12 @@ class ResidualTrainer:
         self._draws = 0                      # device dropout draws so far: the Philox counter offset of the next one
         self._shape = None
         self._ws = self._loss = self._logits = None
+
+    def _check(self, model) -> None:
+        pass
+
+    def _dropout_p(self) -> float:
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ step
     def _prepare(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask):
@@ -212,12 +219,12 @@ class ResidualTrainer:
         mask = None
         if dropout_mask is not None:
             mask = torch.as_tensor(dropout_mask).detach().to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(mask.shape) != (b, 128):
-                raise ValueError(f"dropout_mask must be ({b}, 128), got {tuple(mask.shape)}")
+            if tuple(mask.shape) != (b, self._mask_width):
+                raise ValueError(f"dropout_mask must be ({b}, {self._mask_width}), got {tuple(mask.shape)}")
         if self._shape != (b, hgt, wid):
-            need = _lib.load().cough_train_workspace_bytes(b, hgt, wid)
+            need = getattr(_lib.load(), self._ws_fn)(b, hgt, wid)
             if need == 0:
-                raise ValueError(f"ResidualTrainer: a batch of {b} images of {hgt}x{wid} is not trainable (image too "
+                raise ValueError(f"{self._name}: a batch of {b} images of {hgt}x{wid} is not trainable (image too "
                                  "small for the network, or a BatchNorm would see one value per channel)")
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
             self._loss = torch.empty((), dtype=torch.float32, device=dev)
@@ -227,22 +234,22 @@ class ResidualTrainer:
 
     def forward_backward(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask=None, mask_out=None):
         """The forward and backward half of ``step``: writes ``p.grad`` of every parameter (unclipped), the BN running
-        statistics and counters; returns ``(loss, logits)``.  ``mask_out`` (B, 128) float32 device tensor, optional,
-        receives the keep mask used."""
+        statistics and counters; returns ``(loss, logits)``.  ``mask_out`` (B, mask width) float32 device tensor,
+        optional, receives the keep mask used."""
         x, t, mask = self._prepare(inputs, targets, dropout_mask)
         self.optimizer.bind_grads()          # after a torch-style zero_grad(set_to_none=True) on the module
         b, _, hgt, wid = x.shape
-        p = float(self.model.fc[1].p)
+        p = self._dropout_p()
         offset = self._draws
         if mask is None:
             self._draws += 1
         dev = self.device
-        _lib.check(_lib.load().cough_train_forward_backward(
+        _lib.check(getattr(_lib.load(), self._fb_fn)(
             x.data_ptr(), b, hgt, wid, t.data_ptr(), _ptr(self.class_weights), _ptr(mask), self.seed, offset, p,
             self._params.data_ptr(), self._grads.data_ptr(), self._running.data_ptr(), self._nbt.data_ptr(),
             self._momentum, self._bn_eps, self._loss.data_ptr(), self._logits.data_ptr(), _ptr(mask_out),
             self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
-            "cough_train_forward_backward")
+            self._fb_fn)
         # the kernels wrote the parameters / buffers behind torch's back (no _version bump): drop the inference handles
         # so the next eval-mode call re-reads them
         self.model.invalidate()
@@ -255,9 +262,60 @@ class ResidualTrainer:
         return loss, logits
 
 
-def train_epoch(trainer: ResidualTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:
-    """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer``: ``{'loss', 'accuracy'}``,
-    the mean batch loss and the percentage of train-mode predictions equal to the target."""
+class ResidualTrainer(_FlatTrainer):
+    """Trains a ``CoughDetectorResidual`` (``channels=(32, 64, 128)``) with the reference's ``train_epoch`` step.
+
+    ``step(inputs, targets, dropout_mask=None) -> (loss, logits)``: ``inputs`` (B, 1, F, T) float32, ``targets`` (B,)
+    int64 class indices; ``dropout_mask`` (B, 128) of 0 / 1 keeps, or ``None`` for the device generator (Philox keyed by
+    ``seed``, one new draw per step).  ``loss`` is a 0-d device tensor, ``logits`` the train-mode outputs; both are
+    buffers of the trainer, overwritten by the next step at the same shape (read them, e.g. ``loss.item()``, first).
+    No host synchronisation; no allocation after the first step at a given (B, F, T)."""
+
+    _model_cls = CoughDetectorResidual
+    _name = "ResidualTrainer"
+    _n_tensors, _n_params, _n_running, _n_bns, _mask_width = 30, _lib.TRAIN_NUM_PARAMS, _lib.TRAIN_NUM_RUNNING, 7, 128
+    _ws_fn, _fb_fn = "cough_train_workspace_bytes", "cough_train_forward_backward"
+
+    def _check(self, model) -> None:
+        if tuple(model.channels) != SHIPPED_CHANNELS:
+            raise ValueError(f"ResidualTrainer: channels={tuple(model.channels)}; the training kernels are built for "
+                             f"{SHIPPED_CHANNELS}")
+
+    def _dropout_p(self) -> float:
+        return float(self.model.fc[1].p)
+
+
+class SmallTrainer(_FlatTrainer):
+    """Trains a ``CoughDetectorSmall`` with the reference's ``train_epoch`` step (``csrc/train_small.hip``,
+    ``cough_train_small_forward_backward``): the contract of ``ResidualTrainer``, with the dropout keep mask of the
+    hidden layer (``classifier[3]``) ``(B, 64)``.  Trainable shapes: F, T >= 8 and B * (F // 8) * (T // 8) > 1."""
+
+    _model_cls = CoughDetectorSmall
+    _name = "SmallTrainer"
+    _n_tensors, _n_params, _n_running, _n_bns, _mask_width = (26, _lib.TRAIN_SMALL_NUM_PARAMS,
+                                                              _lib.TRAIN_SMALL_NUM_RUNNING, 4, 64)
+    _ws_fn, _fb_fn = "cough_train_small_workspace_bytes", "cough_train_small_forward_backward"
+
+    def _dropout_p(self) -> float:
+        return float(self.model.classifier[3].p)
+
+
+def create_trainer(model, **kwargs):
+    """The HIP trainer of ``model``: ``ResidualTrainer`` for a ``CoughDetectorResidual``, ``SmallTrainer`` for a
+    ``CoughDetectorSmall`` (keyword arguments as theirs).  ``CoughDetector`` ("standard") is not trainable yet."""
+    if isinstance(model, CoughDetectorResidual):
+        return ResidualTrainer(model, **kwargs)
+    if isinstance(model, CoughDetectorSmall):
+        return SmallTrainer(model, **kwargs)
+    if isinstance(model, CoughDetector):
+        raise TypeError("CoughDetector ('standard') is not trainable yet on the MI355X path: train a "
+                        "CoughDetectorSmall or a CoughDetectorResidual")
+    raise TypeError(f"no HIP trainer for {type(model).__name__}")
+
+
+def train_epoch(trainer: _FlatTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:
+    """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer`` or a ``SmallTrainer``
+    (``create_trainer``): ``{'loss', 'accuracy'}``, the mean batch loss and the percentage of train-mode predictions equal to the target."""
     trainer.model.train()
     running_loss, correct, total, n_batches = 0.0, 0, 0, 0
     for inputs, targets in train_loader:

@@ -391,6 +391,29 @@ int cough_adamw_step(float* d_params, float* d_grads, float* d_exp_avg, float* d
                      float beta1, float beta2, float eps, float weight_decay, float max_norm, double bias_correction1,
                      double bias_correction2, float* d_total_norm, void* stream);
 
+/* ------------------------------------------------------------------ training step (CoughDetectorSmall)
+ * The same step for the reference's CoughDetectorSmall (src/model.py:144-207): conv3x3(1->16), BN, ReLU, maxpool 2,
+ * three depthwise-separable blocks (dw3x3 -> pw1x1 -> BN -> ReLU, the first two with maxpool 2), global mean,
+ * Linear(128, 64), ReLU, Dropout(p), Linear(64, 2).  Same arguments and conventions as cough_train_forward_backward, with
+ *   d_params / d_grads  COUGH_TRAIN_SMALL_NUM_PARAMS float32 in model.parameters() order (26 tensors)
+ *   d_running           COUGH_TRAIN_SMALL_NUM_RUNNING float32: running_mean then running_var of each of the 4 BNs
+ *                       (features.1, .6, .11, .16); d_num_batches: their 4 num_batches_tracked counters
+ *   d_dropout_mask / d_mask_out  [n_clips][64]: the keep mask of the hidden layer (classifier[3]); the device draw
+ *                       counts (unit / 4, clip, offset) like the residual step's
+ * Trainable shapes: height >= 8, width >= 8 (three 2x2 pools) and n_clips * (height / 8) * (width / 8) > 1 (the last BN
+ * sees more than one value per channel), with n_clips * height * width <= 2^27.  The optimizer step is
+ * cough_adamw_step over the COUGH_TRAIN_SMALL_NUM_PARAMS values. */
+#define COUGH_TRAIN_SMALL_NUM_PARAMS 21122
+#define COUGH_TRAIN_SMALL_NUM_RUNNING 480
+size_t cough_train_small_workspace_bytes(int n_clips, int height, int width); /* 0 = shape not trainable */
+int cough_train_small_forward_backward(const float* d_x, int n_clips, int height, int width, const long long* d_targets,
+                                       const float* d_class_weights, const float* d_dropout_mask,
+                                       unsigned long long seed, unsigned long long offset, float p,
+                                       const float* d_params, float* d_grads, float* d_running,
+                                       long long* d_num_batches, float momentum, float eps, float* d_loss,
+                                       float* d_logits, float* d_mask_out, void* d_workspace, size_t workspace_bytes,
+                                       void* stream);
+
 /* ------------------------------------------------------------------ resampler (front of process())
  * Replaces T.Resample(orig, 16000)(waveform) (/root/reference/src/preprocessing.py:146-183): polyphase
  * windowed-sinc FIR.  d_kernel: device [new][K] float32, K = 2*width + orig, built by the caller the way

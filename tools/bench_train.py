@@ -1,8 +1,10 @@
-"""Time one CoughDetectorResidual training step (forward, backward, clip, AdamW): the HIP step of ResidualTrainer against
-a torch-eager fp32 step on the same GPU (a module of torch.nn layers with the reference's structure,
-torch.optim.AdamW, clip_grad_norm_).  The two paths alternate, `--rounds` times, each round timing `--steps` steps after
+"""Time one training step (forward, backward, clip, AdamW) of CoughDetectorResidual (``--model residual``, the default) or
+CoughDetectorSmall (``--model small``): the HIP step of ResidualTrainer / SmallTrainer against a torch-eager fp32 step on
+the same GPU (a module of torch.nn layers with the reference's structure, torch.optim.AdamW, clip_grad_norm_).  The two paths alternate, `--rounds` times, each round timing `--steps` steps after
 `--warmup` with device events.  Prints one line per batch size (median ms per step, clips/s, FLOP-based share of the
-f32 MFMA peak).  Usage: python tools/bench_train.py [--batches 32,256,1024] [--steps 20] [--warmup 5] [--rounds 3]
+f32 MFMA peak).  For Small, each line also carries the HBM bytes per step that the HIP step's kernels must move at least (every stored
+activation written once and read once per consumer, x read by each of its passes) and the achieved rate against it.
+Usage: python tools/bench_train.py [--model residual|small] [--batches 32,256,1024] [--steps 20] [--warmup 5] [--rounds 3]
 """
 import argparse
 import json
@@ -15,7 +17,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cough_detector_amd as cda                      # noqa: E402
-from cough_detector_amd.training import ResidualTrainer   # noqa: E402
+from cough_detector_amd.training import ResidualTrainer, SmallTrainer   # noqa: E402
 
 F32_MFMA_PEAK = 157.3e12
 H, W = 90, 101
@@ -56,6 +58,47 @@ class TorchResidual(nn.Module):
         return self.fc(F.adaptive_avg_pool2d(x, 1))
 
 
+def small_flops_per_clip(h=H, w=W):
+    """2 * MACs of a step of CoughDetectorSmall: forward, wgrad (same) and dgrad of every conv but conv1."""
+    conv1 = 2 * h * w * 16 * 9
+    blocks, ph, pw = 0, h // 2, w // 2
+    for cin, cout in ((16, 32), (32, 64), (64, 128)):
+        blocks += 2 * ph * pw * (9 * cin + cin * cout)
+        ph, pw = ph // 2, pw // 2
+    return 2 * (conv1 + blocks) + blocks
+
+
+def small_bytes_per_clip(h=H, w=W):
+    """HBM bytes of one HIP step of Small per clip (csrc/train_small.hip): x read by its 5 passes; per block k the dw
+    input p, dw output d and pw output z written once; read by the forward (z twice: statistics, pool / head; p, d once
+    more by dw / pw); backward writes dz, dd, dp and reads z (twice), dp of the next block, dz (wgrad), d (wgrad), dd
+    and p (dw backward), dp (BN partials and dz pass of the block before)."""
+    total = 5 * h * w * 4
+    ph, pw = h // 2, w // 2
+    for cin, cout in ((16, 32), (32, 64), (64, 128)):
+        n_in, n_out = ph * pw * cin * 4, ph * pw * cout * 4
+        fwd = (n_in + n_in + n_out) + (n_in + n_out * 2)          # p, d, z written; p read by dw, z by stats + pool
+        bwd = (n_out * 2 + n_out + n_in) + (n_out + n_in) + (n_in * 2 + n_in) + 2 * n_in
+        total += fwd + bwd
+        ph, pw = ph // 2, pw // 2
+    return total
+
+
+class TorchSmall(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.features = nn.Sequential(
+            nn.Conv2d(1, 16, 3, padding=1), nn.BatchNorm2d(16), nn.ReLU(), nn.MaxPool2d(2),
+            nn.Conv2d(16, 16, 3, padding=1, groups=16), nn.Conv2d(16, 32, 1), nn.BatchNorm2d(32), nn.ReLU(), nn.MaxPool2d(2),
+            nn.Conv2d(32, 32, 3, padding=1, groups=32), nn.Conv2d(32, 64, 1), nn.BatchNorm2d(64), nn.ReLU(), nn.MaxPool2d(2),
+            nn.Conv2d(64, 64, 3, padding=1, groups=64), nn.Conv2d(64, 128, 1), nn.BatchNorm2d(128), nn.ReLU(),
+            nn.AdaptiveAvgPool2d((1, 1)))
+        self.classifier = nn.Sequential(nn.Flatten(), nn.Linear(128, 64), nn.ReLU(), nn.Dropout(0.3), nn.Linear(64, 2))
+
+    def forward(self, x):
+        return self.classifier(self.features(x))
+
+
 def time_steps(fn, steps, warmup):
     for _ in range(warmup):
         fn()
@@ -70,6 +113,7 @@ def time_steps(fn, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("residual", "small"), default="residual")
     ap.add_argument("--batches", default="32,256,1024")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -78,14 +122,19 @@ def main():
     a = ap.parse_args()
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    stem, blocks, step_flops = flops_per_clip()
+    small = a.model == "small"
+    step_flops = small_flops_per_clip() if small else flops_per_clip()[2]
     for b in [int(v) for v in a.batches.split(",")]:
         g = torch.Generator().manual_seed(b)
         x = torch.randn(b, 1, H, W, generator=g).to(dev)
         y = torch.randint(0, 2, (b,), generator=g).to(dev)
         cw = torch.tensor([1.0, 2.5], device=dev)
-        tr = ResidualTrainer(cda.create_model("residual", n_mels=H), class_weights=cw)
-        tm = TorchResidual().to(dev).train()
+        if small:
+            tr = SmallTrainer(cda.create_model("small", n_mels=H), class_weights=cw)
+            tm = TorchSmall().to(dev).train()
+        else:
+            tr = ResidualTrainer(cda.create_model("residual", n_mels=H), class_weights=cw)
+            tm = TorchResidual().to(dev).train()
         opt = torch.optim.AdamW(tm.parameters(), lr=1e-3, weight_decay=0.01)
         crit = nn.CrossEntropyLoss(weight=cw)
 
@@ -106,11 +155,15 @@ def main():
                 eager.append(time_steps(torch_step, a.steps, a.warmup))
         med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")   # noqa: E731
         h_ms, t_ms = med(hip), med(eager)
-        print(json.dumps({"batch": b, "image": [H, W], "hip_ms": round(h_ms, 4), "torch_eager_ms": round(t_ms, 4),
+        extra = {}
+        if small:
+            nbytes = b * small_bytes_per_clip()
+            extra = {"step_hbm_bytes": nbytes, "hip_hbm_bytes_per_s": round(nbytes / (h_ms * 1e-3), 1)}
+        print(json.dumps({"model": a.model, "batch": b, "image": [H, W], "hip_ms": round(h_ms, 4), "torch_eager_ms": round(t_ms, 4),
                           "hip_clips_per_s": round(b / h_ms * 1e3, 1), "eager_clips_per_s": round(b / t_ms * 1e3, 1),
                           "speedup": round(t_ms / h_ms, 3), "hip_rounds_ms": [round(v, 4) for v in hip],
                           "step_gflop": round(b * step_flops / 1e9, 3),
-                          "hip_share_of_f32_mfma_peak": round(b * step_flops / (h_ms * 1e-3) / F32_MFMA_PEAK, 4)}),
+                          "hip_share_of_f32_mfma_peak": round(b * step_flops / (h_ms * 1e-3) / F32_MFMA_PEAK, 4), **extra}),
               flush=True)
 
 
