@@ -7,10 +7,10 @@ from .model import (CoughDetector, CoughDetectorResidual, CoughDetectorSmall, Co
 from .inference import CoughDetectorInference, RealtimeQueueDetector
 from .pipeline import CoughPipeline
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, create_augmentation_pipeline
-from .training import HipAdamW, ResidualTrainer, SmallTrainer, create_trainer, train_epoch
+from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, create_trainer, train_epoch
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
            "ResidualBlock", "create_model", "count_parameters", "CoughDetectorInference", "RealtimeQueueDetector",
            "CoughPipeline", "AudioAugmentor", "MixUp", "SpecAugment", "create_augmentation_pipeline",
-           "ResidualTrainer", "SmallTrainer", "create_trainer", "HipAdamW", "train_epoch"]
+           "ResidualTrainer", "SmallTrainer", "StandardTrainer", "create_trainer", "HipAdamW", "train_epoch"]

@@ -52,12 +52,14 @@ SYMBOLS = (
     "cough_augment_workspace_bytes", "cough_augment_waveforms", "cough_mix_rows",
     "cough_train_workspace_bytes", "cough_train_forward_backward", "cough_adamw_step",
     "cough_train_small_workspace_bytes", "cough_train_small_forward_backward",
+    "cough_train_std_workspace_bytes", "cough_train_std_forward_backward",
 )
 
 
 MAX_CONTRAST_BANDS = 16
 TRAIN_NUM_PARAMS, TRAIN_NUM_RUNNING = 290370, 1216   # COUGH_TRAIN_NUM_PARAMS / COUGH_TRAIN_NUM_RUNNING
 TRAIN_SMALL_NUM_PARAMS, TRAIN_SMALL_NUM_RUNNING = 21122, 480   # COUGH_TRAIN_SMALL_NUM_PARAMS / _NUM_RUNNING
+TRAIN_STD_NUM_PARAMS, TRAIN_STD_NUM_RUNNING = 421954, 960      # COUGH_TRAIN_STD_NUM_PARAMS / _NUM_RUNNING
 
 
 class FeatConfig(C.Structure):
@@ -185,6 +187,10 @@ def load() -> C.CDLL:
         lib.cough_train_small_workspace_bytes.argtypes = [i, i, i]
         lib.cough_train_small_workspace_bytes.restype = C.c_size_t
         lib.cough_train_small_forward_backward.argtypes = lib.cough_train_forward_backward.argtypes
+        lib.cough_train_std_workspace_bytes.argtypes = [i, i, i]
+        lib.cough_train_std_workspace_bytes.restype = C.c_size_t
+        lib.cough_train_std_forward_backward.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, f, vp, vp, vp, vp, f, f,
+                                                         vp, vp, vp, vp, C.c_size_t, vp]
         lib.cough_adamw_step.argtypes = [vp, vp, vp, vp, ll, f, f, f, f, f, f, C.c_double, C.c_double, vp, vp]
         if lib.cough_amd_abi_version() != 5:
             raise RuntimeError("libcough_amd.so ABI version mismatch; rebuild it")

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "philox.h"
+#include "train_common.h"
 
 namespace cough {
 namespace {
@@ -50,10 +51,8 @@ constexpr int SLAB_N = 12256;
 __host__ __device__ constexpr int seg_dw(int k) { return 2 * k - 1; }
 __host__ __device__ constexpr int seg_pw(int k) { return 2 * k; }
 
-constexpr int NT = 256;                     // threads of every block-reducing kernel
 constexpr int TP = 32;                      // pw wgrad: pixels per LDS tile
 
-__device__ __forceinline__ long long range_lo(int s, int S, long long M) { return M * s / S; }
 
 // v[i] summed over the 256 threads of the block in a fixed order; every thread gets the sums
 template <int N>
@@ -79,9 +78,6 @@ __device__ __forceinline__ float pick(const float (&v)[N], int i) {
     return r;
 }
 
-__device__ __forceinline__ float bn_act(float z, const float* st, const float* g, const float* bt, int c, int C) {
-    return (z - st[c]) * st[C + c] * g[c] + bt[c];
-}
 
 // ------------------------------------------------------------------------------------------ conv1, recomputed
 // a pool window of conv1's output: rows 2wy, 2wy+1 and columns 2wx, 2wx+1 (those inside the image) read the 4x4 patch
@@ -112,14 +108,6 @@ __device__ __forceinline__ float conv1_at(const Patch& p, const float* prm, int 
     return s;
 }
 
-// first index of the largest of a[0..3] (torch's max_pool2d keeps the first of equal values)
-__device__ __forceinline__ int argmax4(const float (&a)[4]) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-        if (a[j] > a[k]) k = j;
-    return k;
-}
 
 // ------------------------------------------------------------------------------------------ BN statistics
 // part[s][C][3] = (count, mean, centred sum of squares) of range s.  Stage 0: windows of conv1's output, 4 channels per
@@ -196,49 +184,6 @@ __global__ __launch_bounds__(NT) void stats_kernel(const float* __restrict__ z, 
         o[0] = n;
         o[1] = mean;
         o[2] = q[0];
-    }
-}
-
-struct Chan {
-    double n, mean, m2;
-};
-__device__ __forceinline__ Chan chan_merge(Chan a, Chan b) {
-    if (b.n == 0.0) return a;
-    if (a.n == 0.0) return b;
-    const double n = a.n + b.n, d = b.mean - a.mean;
-    return Chan{n, a.mean + d * b.n / n, a.m2 + b.m2 + d * d * a.n * b.n / n};
-}
-
-// one block per channel: thread t merges ranges t, t + 256, ... in order, then a fixed pairwise tree.  Batch mean /
-// invstd -> stat[0..1], running statistics (momentum, unbiased variance), num_batches_tracked + 1.
-__global__ __launch_bounds__(NT) void stats_finalize_kernel(const float* __restrict__ part, int S, int C, float eps,
-                                                            float momentum, float* __restrict__ run_mean,
-                                                            float* __restrict__ run_var, long long* __restrict__ nbt,
-                                                            float* __restrict__ stat) {
-    __shared__ double sh[3][NT];
-    const int c = blockIdx.x, t = threadIdx.x;
-    Chan a{0.0, 0.0, 0.0};
-    for (int i = t; i < S; i += NT) {
-        const float* p = part + ((long long)i * C + c) * 3;
-        a = chan_merge(a, Chan{double(p[0]), double(p[1]), double(p[2])});
-    }
-    sh[0][t] = a.n; sh[1][t] = a.mean; sh[2][t] = a.m2;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (t < off) {
-            const Chan m = chan_merge(Chan{sh[0][t], sh[1][t], sh[2][t]}, Chan{sh[0][t + off], sh[1][t + off], sh[2][t + off]});
-            sh[0][t] = m.n; sh[1][t] = m.mean; sh[2][t] = m.m2;
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const double n = sh[0][0], mean = sh[1][0], m2 = sh[2][0];
-        const float var = float(m2 / n), uvar = float(m2 / (n - 1.0)), mu = float(mean);
-        stat[c] = mu;
-        stat[C + c] = 1.0f / sqrtf(var + eps);
-        run_mean[c] = momentum * mu + (1.0f - momentum) * run_mean[c];
-        run_var[c] = momentum * uvar + (1.0f - momentum) * run_var[c];
-        if (c == 0) nbt[0] += 1;
     }
 }
 
@@ -523,33 +468,6 @@ __global__ __launch_bounds__(NT) void bn_bwd_part_kernel(BwdSrc a, const float* 
         float* o = part + ((long long)blockIdx.x * C + c0 + i) * 2;
         o[0] = pick(v, 2 * i);
         o[1] = pick(v, 2 * i + 1);
-    }
-}
-
-// one block per channel: the S ranges summed (thread t: ranges t, t + 256, ...; then a fixed tree) -> stat[2..3],
-// dgamma = sum dy * xhat, dbeta = sum dy
-__global__ __launch_bounds__(NT) void bn_bwd_finalize_kernel(const float* __restrict__ part, int S, int C,
-                                                             float* __restrict__ stat, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta) {
-    __shared__ double sh[2][NT];
-    const int c = blockIdx.x, t = threadIdx.x;
-    double s = 0.0, sx = 0.0;
-    for (int i = t; i < S; i += NT) {
-        s += part[((long long)i * C + c) * 2];
-        sx += part[((long long)i * C + c) * 2 + 1];
-    }
-    sh[0][t] = s; sh[1][t] = sx;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (t < off) { sh[0][t] += sh[0][t + off]; sh[1][t] += sh[1][t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        const float fs = float(sh[0][0]), fsx = float(sh[1][0]);
-        stat[2 * C + c] = fs;
-        stat[3 * C + c] = fsx;
-        dgamma[c] = fsx;
-        dbeta[c] = fs;
     }
 }
 

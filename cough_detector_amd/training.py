@@ -1,4 +1,4 @@
-"""Training of ``CoughDetectorResidual`` and ``CoughDetectorSmall`` on the MI355X: one optimisation step as the reference's ``train_epoch`` takes it
+"""Training of ``CoughDetectorResidual``, ``CoughDetectorSmall`` and ``CoughDetector`` on the MI355X: one optimisation step as the reference's ``train_epoch`` takes it
 (``/root/reference/src/train.py:54-112``, built at :420-455)::
 
     optimizer.zero_grad(); outputs = model(inputs)            # train mode: batch-statistics BN, Dropout(p)
@@ -6,14 +6,16 @@
     clip_grad_norm_(model.parameters(), max_norm); AdamW(lr, betas, eps, weight_decay).step()
 
 The forward, backward and optimizer arithmetic runs in ``csrc/train.hip`` (``cough_train_forward_backward``,
-``cough_adamw_step``) and ``csrc/train_small.hip`` (``cough_train_small_forward_backward``); torch only allocates memory and supplies the stream.  The trainer makes the module's parameters,
+``cough_adamw_step``), ``csrc/train_small.hip`` (``cough_train_small_forward_backward``) and ``csrc/train_std.hip``
+(``cough_train_std_forward_backward``); torch only allocates memory and supplies the stream.  The trainer makes the module's parameters,
 gradients (``p.grad``) and BatchNorm buffers views of flat device buffers that the kernels update in place, so
 ``model.state_dict()`` holds the trained state after every step and ``model.eval()(x)`` runs the inference kernels on it.
 ``model.train()(x)`` still refuses: training goes through the trainer.
 
 Non-finite input gives a NaN loss; the step then leaves NaN gradients and parameters (as torch's own step does: the clip
 coefficient of a NaN norm does not rescue them).  The residual net trains with its shipped channels ``(32, 64, 128)``
-only; ``create_trainer`` picks the trainer of a model.
+only, the standard net with ``channels=(32, 64, 128, 256)`` and ``fc_hidden=128``; ``create_trainer`` picks the trainer of a
+Residual or Small model, and ``StandardTrainer(model)`` trains a ``CoughDetector``.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ from . import _lib
 from .model import CoughDetector, CoughDetectorResidual, CoughDetectorSmall
 
 SHIPPED_CHANNELS = (32, 64, 128)
+STANDARD_CHANNELS, STANDARD_FC_HIDDEN = (32, 64, 128, 256), 128
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -206,6 +209,10 @@ class _FlatTrainer:
     def _dropout_p(self) -> float:
         raise NotImplementedError
 
+    def _dropout_args(self) -> tuple:
+        """The dropout probabilities the forward / backward entry point takes, in its argument order."""
+        return (self._dropout_p(),)
+
     # ------------------------------------------------------------------ step
     def _prepare(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask):
         dev = self.device
@@ -239,13 +246,13 @@ class _FlatTrainer:
         x, t, mask = self._prepare(inputs, targets, dropout_mask)
         self.optimizer.bind_grads()          # after a torch-style zero_grad(set_to_none=True) on the module
         b, _, hgt, wid = x.shape
-        p = self._dropout_p()
+        ps = self._dropout_args()
         offset = self._draws
         if mask is None:
             self._draws += 1
         dev = self.device
         _lib.check(getattr(_lib.load(), self._fb_fn)(
-            x.data_ptr(), b, hgt, wid, t.data_ptr(), _ptr(self.class_weights), _ptr(mask), self.seed, offset, p,
+            x.data_ptr(), b, hgt, wid, t.data_ptr(), _ptr(self.class_weights), _ptr(mask), self.seed, offset, *ps,
             self._params.data_ptr(), self._grads.data_ptr(), self._running.data_ptr(), self._nbt.data_ptr(),
             self._momentum, self._bn_eps, self._loss.data_ptr(), self._logits.data_ptr(), _ptr(mask_out),
             self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
@@ -300,22 +307,50 @@ class SmallTrainer(_FlatTrainer):
         return float(self.model.classifier[3].p)
 
 
+class StandardTrainer(_FlatTrainer):
+    """Trains a ``CoughDetector`` ("standard": ``channels=(32, 64, 128, 256)``, ``fc_hidden=128``) with the reference's
+    ``train_epoch`` step (``csrc/train_std.hip``, ``cough_train_std_forward_backward``): the contract of
+    ``SmallTrainer``, with the dropout keep mask ``(B, 608)``: one Dropout2d keep per (clip, channel) of the four
+    ConvBlocks (32 + 64 + 128 + 256 columns, in block order), then the 128 hidden units of ``fc[2]``.  The blocks'
+    Dropout2d layers share one p, the head has its own.  Trainable shapes: F >= 16 and T >= 16."""
+
+    _model_cls = CoughDetector
+    _name = "StandardTrainer"
+    _n_tensors, _n_params, _n_running, _n_bns, _mask_width = (20, _lib.TRAIN_STD_NUM_PARAMS, _lib.TRAIN_STD_NUM_RUNNING,
+                                                              4, 608)
+    _ws_fn, _fb_fn = "cough_train_std_workspace_bytes", "cough_train_std_forward_backward"
+
+    def _check(self, model) -> None:
+        chans = tuple(int(b.conv.out_channels) for b in model.conv_layers)
+        if chans != STANDARD_CHANNELS:
+            raise ValueError(f"StandardTrainer: channels={chans}; the training kernels are built for {STANDARD_CHANNELS}")
+        if int(model.fc[0].out_features) != STANDARD_FC_HIDDEN:
+            raise ValueError(f"StandardTrainer: fc_hidden={model.fc[0].out_features}; the training kernels are built for "
+                             f"{STANDARD_FC_HIDDEN}")
+        if len({float(b.dropout.p) for b in model.conv_layers}) != 1:
+            raise ValueError("StandardTrainer: the ConvBlocks' Dropout2d layers must share one p")
+
+    def _dropout_args(self) -> tuple:
+        return float(self.model.conv_layers[0].dropout.p), float(self.model.fc[2].p)
+
+
 def create_trainer(model, **kwargs):
     """The HIP trainer of ``model``: ``ResidualTrainer`` for a ``CoughDetectorResidual``, ``SmallTrainer`` for a
-    ``CoughDetectorSmall`` (keyword arguments as theirs).  ``CoughDetector`` ("standard") is not trainable yet."""
+    ``CoughDetectorSmall`` (keyword arguments as theirs).  A ``CoughDetector`` ("standard") is trained by constructing
+    ``StandardTrainer(model)``; this function does not route to it yet."""
     if isinstance(model, CoughDetectorResidual):
         return ResidualTrainer(model, **kwargs)
     if isinstance(model, CoughDetectorSmall):
         return SmallTrainer(model, **kwargs)
     if isinstance(model, CoughDetector):
-        raise TypeError("CoughDetector ('standard') is not trainable yet on the MI355X path: train a "
-                        "CoughDetectorSmall or a CoughDetectorResidual")
+        raise TypeError("CoughDetector ('standard') is not trainable yet through create_trainer: construct "
+                        "StandardTrainer(model)")
     raise TypeError(f"no HIP trainer for {type(model).__name__}")
 
 
 def train_epoch(trainer: _FlatTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:
-    """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer`` or a ``SmallTrainer``
-    (``create_trainer``): ``{'loss', 'accuracy'}``, the mean batch loss and the percentage of train-mode predictions equal to the target."""
+    """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer``, a ``SmallTrainer``
+    (``create_trainer``) or a ``StandardTrainer``: ``{'loss', 'accuracy'}``, the mean batch loss and the percentage of train-mode predictions equal to the target."""
     trainer.model.train()
     running_loss, correct, total, n_batches = 0.0, 0, 0, 0
     for inputs, targets in train_loader:

@@ -28,7 +28,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* The library is built with -fvisibility=hidden: exactly the 49 entry points declared in this header are exported
+/* The library is built with -fvisibility=hidden: exactly the 53 entry points declared in this header are exported
  * (tests/test_host_logic.py compares `nm -D` of the built library with this list). */
 #pragma GCC visibility push(default)
 
@@ -413,6 +413,29 @@ int cough_train_small_forward_backward(const float* d_x, int n_clips, int height
                                        long long* d_num_batches, float momentum, float eps, float* d_loss,
                                        float* d_logits, float* d_mask_out, void* d_workspace, size_t workspace_bytes,
                                        void* stream);
+
+/* ------------------------------------------------------------------ training step (CoughDetector, "standard")
+ * The same step for the reference's CoughDetector (src/model.py:11-141) with channels (32, 64, 128, 256) and
+ * fc_hidden 128: four ConvBlocks (conv3x3 pad 1, BN, ReLU, maxpool 2, Dropout2d(p_block)), global mean,
+ * Linear(256, 128), ReLU, Dropout(p_fc), Linear(128, 2).  Same arguments and conventions as
+ * cough_train_small_forward_backward, with the single p replaced by p_block (the four Dropout2d layers) and p_fc, and
+ *   d_params / d_grads  COUGH_TRAIN_STD_NUM_PARAMS float32 in model.parameters() order (20 tensors)
+ *   d_running           COUGH_TRAIN_STD_NUM_RUNNING float32: running_mean then running_var of each of the 4 BNs
+ *                       (conv_layers.{0..3}.bn); d_num_batches: their 4 num_batches_tracked counters
+ *   d_dropout_mask / d_mask_out  [n_clips][608] keeps: a Dropout2d keep per (clip, channel) of block 0 (32), 1 (64),
+ *                       2 (128) and 3 (256), then the 128 hidden units of fc[2]; the device draw counts
+ *                       (unit / 4, clip, offset) like the other steps' and keeps where u >= the unit's p
+ * Trainable shapes: height >= 16 and width >= 16 (four 2x2 pools), with n_clips * height * width <= 2^27.  The
+ * optimizer step is cough_adamw_step over the COUGH_TRAIN_STD_NUM_PARAMS values. */
+#define COUGH_TRAIN_STD_NUM_PARAMS 421954
+#define COUGH_TRAIN_STD_NUM_RUNNING 960
+size_t cough_train_std_workspace_bytes(int n_clips, int height, int width); /* 0 = shape not trainable */
+int cough_train_std_forward_backward(const float* d_x, int n_clips, int height, int width, const long long* d_targets,
+                                     const float* d_class_weights, const float* d_dropout_mask, unsigned long long seed,
+                                     unsigned long long offset, float p_block, float p_fc, const float* d_params,
+                                     float* d_grads, float* d_running, long long* d_num_batches, float momentum,
+                                     float eps, float* d_loss, float* d_logits, float* d_mask_out, void* d_workspace,
+                                     size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ resampler (front of process())
  * Replaces T.Resample(orig, 16000)(waveform) (/root/reference/src/preprocessing.py:146-183): polyphase

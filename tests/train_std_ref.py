@@ -1,0 +1,167 @@
+"""Float64 CPU restatement of one training step of CoughDetector, the "standard" net (TEST INFRASTRUCTURE, not product).
+
+The step of the reference's ``train_epoch`` (src/train.py:54-112) on its CoughDetector
+(src/model.py:11-141, channels (32, 64, 128, 256), fc_hidden 128), written with torch functionals: per ConvBlock
+F.conv2d (3x3, pad 1), F.batch_norm(training=True), ReLU, max-pool 2 and Dropout2d with an explicit per-(clip, channel)
+keep mask; global average, Linear, ReLU, dropout with an explicit keep mask, Linear; CrossEntropyLoss(weight), autograd,
+clip_grad_norm_ and torch.optim.AdamW.  The keep mask is (B, 608): the 32 + 64 + 128 + 256 channels of the four blocks,
+then the 128 hidden units.
+"""
+from __future__ import annotations
+
+from typing import Dict, List
+
+import torch
+import torch.nn.functional as F
+
+from train_ref import golden_index, golden_sample        # noqa: F401  (the golden's subsampling rule)
+from train_small_ref import _Relu
+
+CHANNELS = (32, 64, 128, 256)
+HIDDEN = 128
+MASK_OFF = (0, 32, 96, 224, 480)
+MASK_WIDTH = 608
+BNS = [f"conv_layers.{i}.bn" for i in range(4)]
+PARAM_NAMES: List[str] = []
+for _i in range(4):
+    PARAM_NAMES += [f"conv_layers.{_i}.conv.weight", f"conv_layers.{_i}.conv.bias", f"conv_layers.{_i}.bn.weight",
+                    f"conv_layers.{_i}.bn.bias"]
+PARAM_NAMES += ["fc.0.weight", "fc.0.bias", "fc.3.weight", "fc.3.bias"]
+# the conv biases feed a BatchNorm: true gradient 0, the reference's is rounding noise -- bounded, never compared
+BN_FED_BIASES = [f"conv_layers.{i}.conv.bias" for i in range(4)]
+
+
+class RefStep:
+    """Float64 parameters / BN buffers / an AdamW of a CoughDetector; ``step`` is one train_epoch iteration.
+    ``pre`` / ``flip`` / ``regrad`` as in train_ref.RefStep."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8,
+                 max_norm=1.0, class_weights=None, momentum=0.1, bn_eps=1e-5, dtype=torch.float64):
+        self.dtype = dtype
+        self.P = {n: sd[n].detach().to(dtype).clone().requires_grad_(True) for n in PARAM_NAMES}
+        self.R = {}
+        for b in BNS:
+            self.R[b + ".running_mean"] = sd[b + ".running_mean"].detach().to(dtype).clone()
+            self.R[b + ".running_var"] = sd[b + ".running_var"].detach().to(dtype).clone()
+            self.R[b + ".num_batches_tracked"] = int(sd.get(b + ".num_batches_tracked", torch.tensor(0)))
+        self.opt = torch.optim.AdamW([self.P[n] for n in PARAM_NAMES], lr=lr, betas=betas, eps=eps,
+                                     weight_decay=weight_decay)
+        self.max_norm, self.momentum, self.bn_eps = max_norm, momentum, bn_eps
+        self.cw = None if class_weights is None else torch.as_tensor(class_weights, dtype=dtype)
+
+    def _bn(self, z, b):
+        self.R[b + ".num_batches_tracked"] += 1
+        self.batch_var[b] = (z.shape[0] * z.shape[2] * z.shape[3], z.detach().var(dim=(0, 2, 3), unbiased=False))
+        return F.batch_norm(z, self.R[b + ".running_mean"], self.R[b + ".running_var"], self.P[b + ".weight"],
+                            self.P[b + ".bias"], training=True, momentum=self.momentum, eps=self.bn_eps)
+
+    def _relu(self, v, name):
+        self.pre[name] = v.detach()
+        self.flip[name] = torch.zeros(v.shape, dtype=torch.bool)
+        return _Relu.apply(v, self.flip[name])
+
+    def forward(self, x, mask, p_block, p_fc):
+        P = self.P
+        self.pre, self.flip, self.batch_var = {}, {}, {}
+        mask = mask.to(self.dtype)
+        h = x
+        for i in range(4):
+            c = f"conv_layers.{i}.conv"
+            h = F.conv2d(h, P[c + ".weight"], P[c + ".bias"], padding=1)
+            h = F.max_pool2d(self._relu(self._bn(h, BNS[i]), f"b{i}"), 2)
+            keep = mask[:, MASK_OFF[i]:MASK_OFF[i + 1]]
+            h = h * (keep * (1.0 / (1.0 - p_block)))[:, :, None, None] if p_block < 1 else h * 0.0
+        g = h.mean(dim=(2, 3))
+        hid = self._relu(F.linear(g, P["fc.0.weight"], P["fc.0.bias"]), "fc")
+        keep = mask[:, MASK_OFF[4]:]
+        d = hid * (keep * (1.0 / (1.0 - p_fc))) if p_fc < 1 else hid * 0.0
+        return F.linear(d, P["fc.3.weight"], P["fc.3.bias"])
+
+    def grads(self, x, y, mask, p_block, p_fc):
+        """Forward + backward: (loss, logits, {name: unclipped grad})."""
+        self.opt.zero_grad()
+        logits = self.forward(x.to(self.dtype), mask, p_block, p_fc)
+        loss = F.cross_entropy(logits, y, weight=self.cw)
+        loss.backward(retain_graph=True)
+        self._loss = loss
+        return loss.detach(), logits.detach(), {n: self.P[n].grad.detach().clone() for n in PARAM_NAMES}
+
+    def regrad(self):
+        self.opt.zero_grad()
+        self._loss.backward(retain_graph=True)
+        return {n: self.P[n].grad.detach().clone() for n in PARAM_NAMES}
+
+    def step(self, x, y, mask, p_block, p_fc):
+        """One train_epoch iteration: (loss, logits, unclipped grads, total norm)."""
+        loss, logits, g = self.grads(x, y, mask, p_block, p_fc)
+        norm = torch.nn.utils.clip_grad_norm_([self.P[n] for n in PARAM_NAMES], max_norm=self.max_norm)
+        self.opt.step()
+        return loss, logits, g, float(norm)
+
+    def state_dict(self):
+        sd = {n: t.detach().clone() for n, t in self.P.items()}
+        for k, v in self.R.items():
+            sd[k] = torch.tensor(v) if isinstance(v, int) else v.clone()
+        return sd
+
+
+def running_names() -> List[str]:
+    return [b + s for b in BNS for s in (".running_mean", ".running_var")]
+
+
+def _worst(g, rgrads):
+    return max((g[n] - rgrads[n]).abs().max().item() / max(rgrads[n].abs().max().item(), 1e-300)
+               for n in PARAM_NAMES if n not in BN_FED_BIASES)
+
+
+def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4):
+    """train_small_ref.resolve_kinks for this network: ReLU inputs within ``kink`` of 0 are flipped one at a time on
+    ``ref`` (after ``grads``) and kept where that brings the restatement closer to ``g``.  Returns (gradients, flips)."""
+    if _worst(g, rgrads) <= rtol:
+        return rgrads, []
+    cand = []
+    for name, v in ref.pre.items():
+        for idx in (v.abs() < kink).nonzero().tolist():
+            cand.append((abs(v[tuple(idx)].item()), name, tuple(idx)))
+    cand.sort()
+    kept, best = [], _worst(g, rgrads)
+    for _, name, idx in cand[:limit]:
+        ref.flip[name][idx] = True
+        trial = ref.regrad()
+        w = _worst(g, trial)
+        if w < best:
+            best, rgrads = w, trial
+            kept.append((name, idx, ref.pre[name][idx].item()))
+            if best <= rtol:
+                break
+        else:
+            ref.flip[name][idx] = False
+    return rgrads, kept
+
+
+def assert_step_matches(model, loss, logits, rloss, rlogits, rgrads, rsd, sd0, grad_rtol=1e-4) -> float:
+    """train_small_ref.assert_step_matches for CoughDetector: loss within 1e-5 of max(|loss|, the logits' bound),
+    logits within 1e-5 of max(1, their largest), every gradient within ``grad_rtol`` of that tensor's largest reference
+    gradient (the BN-fed conv biases bounded by ``grad_rtol`` of their weight's), running statistics rtol 1e-5,
+    num_batches_tracked + 1.  Returns the largest gradient error as a fraction of its tensor's scale."""
+    import numpy as np
+    zscale = max(1.0, rlogits.abs().max().item())
+    dl = abs(loss.item() - rloss.item())
+    assert dl <= 1e-5 * max(abs(rloss.item()), zscale), (loss.item(), rloss.item())
+    assert (logits.cpu().double() - rlogits).abs().max().item() <= 1e-5 * zscale
+    g = {n: p.grad.detach().cpu().double() for n, p in model.named_parameters()}
+    worst = 0.0
+    for n in PARAM_NAMES:
+        if n in BN_FED_BIASES:
+            assert g[n].abs().max().item() <= grad_rtol * rgrads[n.replace(".bias", ".weight")].abs().max().item(), n
+            continue
+        scale = rgrads[n].abs().max().item()
+        err = (g[n] - rgrads[n]).abs().max().item()
+        assert err <= grad_rtol * scale, (n, err, scale)
+        worst = max(worst, err / scale if scale > 0 else 0.0)
+    msd = model.state_dict()
+    for k in running_names():
+        np.testing.assert_allclose(msd[k].cpu().double().numpy(), rsd[k].numpy(), rtol=1e-5, atol=1e-6, err_msg=k)
+    for k in [n for n in msd if n.endswith("num_batches_tracked")]:
+        assert int(msd[k]) == int(sd0[k]) + 1
+    return worst

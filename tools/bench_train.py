@@ -1,10 +1,12 @@
-"""Time one training step (forward, backward, clip, AdamW) of CoughDetectorResidual (``--model residual``, the default) or
-CoughDetectorSmall (``--model small``): the HIP step of ResidualTrainer / SmallTrainer against a torch-eager fp32 step on
+"""Time one training step (forward, backward, clip, AdamW) of CoughDetectorResidual (``--model residual``, the default),
+CoughDetectorSmall (``--model small``) or CoughDetector (``--model standard``): the HIP step of ResidualTrainer /
+SmallTrainer / StandardTrainer against a torch-eager fp32 step on
 the same GPU (a module of torch.nn layers with the reference's structure, torch.optim.AdamW, clip_grad_norm_).  The two paths alternate, `--rounds` times, each round timing `--steps` steps after
 `--warmup` with device events.  Prints one line per batch size (median ms per step, clips/s, FLOP-based share of the
-f32 MFMA peak).  For Small, each line also carries the HBM bytes per step that the HIP step's kernels must move at least (every stored
+f32 MFMA peak).  For Standard, each line also carries the share of the peak of convs 1-3 alone (``--conv-ms``: their
+kernels' time per step from a kernel trace).  For Small and Standard, each line also carries the HBM bytes per step that the HIP step's kernels must move at least (every stored
 activation written once and read once per consumer, x read by each of its passes) and the achieved rate against it.
-Usage: python tools/bench_train.py [--model residual|small] [--batches 32,256,1024] [--steps 20] [--warmup 5] [--rounds 3]
+Usage: python tools/bench_train.py [--model residual|small|standard] [--batches 32,256,1024] [--steps 20] [--warmup 5] [--rounds 3]
 """
 import argparse
 import json
@@ -17,7 +19,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import cough_detector_amd as cda                      # noqa: E402
-from cough_detector_amd.training import ResidualTrainer, SmallTrainer   # noqa: E402
+from cough_detector_amd.training import ResidualTrainer, SmallTrainer, StandardTrainer   # noqa: E402
 
 F32_MFMA_PEAK = 157.3e12
 H, W = 90, 101
@@ -99,6 +101,56 @@ class TorchSmall(nn.Module):
         return self.classifier(self.features(x))
 
 
+STD_CHANNELS = (32, 64, 128, 256)
+
+
+def std_flops_per_clip(h=H, w=W):
+    """2 * MACs of a step of CoughDetector: (conv 0, convs 1-3 forward, step total).  A step is forward, wgrad (same)
+    and dgrad of convs 1-3 (conv 0's input gradient is never needed)."""
+    conv0 = 2 * h * w * 32 * 9
+    blocks, ph, pw = 0, h // 2, w // 2
+    for cin, cout in zip(STD_CHANNELS[:-1], STD_CHANNELS[1:]):
+        blocks += 2 * ph * pw * cout * cin * 9
+        ph, pw = ph // 2, pw // 2
+    return conv0, blocks, 2 * (conv0 + blocks) + blocks
+
+
+def std_bytes_per_clip(h=H, w=W):
+    """HBM bytes of one HIP step of CoughDetector per clip (csrc/train_std.hip), counting each stored tensor once per
+    write and once per reading pass: x read by conv 0 and its weight gradient; per block k the pre-BN output z (written;
+    read by the two statistics passes, the BN-pool-dropout pass, the backward partial sums, and dz: 5 reads), the pooled
+    output a (written; read by the next conv and its weight gradient), its gradient da (written by the dgrad; read by
+    the backward partial sums and dz), the pool's argmax byte (written, read twice), and for k >= 1 dz (written; read by
+    wgrad and dgrad)."""
+    total = 2 * h * w * 4
+    hh, ww = h, w
+    for k, c in enumerate(STD_CHANNELS):
+        z = hh * ww * c * 4
+        ph, pw = hh // 2, ww // 2
+        pooled = ph * pw * c
+        total += 6 * z + 3 * pooled * 4 + 3 * pooled
+        if k < 3:
+            total += 3 * pooled * 4
+        if k > 0:
+            total += 3 * z
+        hh, ww = ph, pw
+    return total
+
+
+class TorchStandard(nn.Module):
+    def __init__(self):
+        super().__init__()
+        layers, cin = [], 1
+        for c in STD_CHANNELS:
+            layers += [nn.Conv2d(cin, c, 3, padding=1), nn.BatchNorm2d(c), nn.ReLU(), nn.MaxPool2d(2), nn.Dropout2d(0.1)]
+            cin = c
+        self.conv_layers = nn.Sequential(*layers)
+        self.fc = nn.Sequential(nn.Linear(256, 128), nn.ReLU(), nn.Dropout(0.5), nn.Linear(128, 2))
+
+    def forward(self, x):
+        return self.fc(F.adaptive_avg_pool2d(self.conv_layers(x), 1).flatten(1))
+
+
 def time_steps(fn, steps, warmup):
     for _ in range(warmup):
         fn()
@@ -113,17 +165,19 @@ def time_steps(fn, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("residual", "small"), default="residual")
+    ap.add_argument("--model", choices=("residual", "small", "standard"), default="residual")
     ap.add_argument("--batches", default="32,256,1024")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only-hip", action="store_true", help="HIP step only (for a kernel trace)")
+    ap.add_argument("--conv-ms", default="", help="standard: batch=ms,... of convs 1-3 per step (from a kernel trace)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
-    small = a.model == "small"
-    step_flops = small_flops_per_clip() if small else flops_per_clip()[2]
+    small, std = a.model == "small", a.model == "standard"
+    step_flops = small_flops_per_clip() if small else std_flops_per_clip()[2] if std else flops_per_clip()[2]
+    conv_ms = {int(k): float(v) for k, v in (kv.split("=") for kv in a.conv_ms.split(",") if kv)}
     for b in [int(v) for v in a.batches.split(",")]:
         g = torch.Generator().manual_seed(b)
         x = torch.randn(b, 1, H, W, generator=g).to(dev)
@@ -132,6 +186,9 @@ def main():
         if small:
             tr = SmallTrainer(cda.create_model("small", n_mels=H), class_weights=cw)
             tm = TorchSmall().to(dev).train()
+        elif std:
+            tr = StandardTrainer(cda.create_model("standard", n_mels=H), class_weights=cw)
+            tm = TorchStandard().to(dev).train()
         else:
             tr = ResidualTrainer(cda.create_model("residual", n_mels=H), class_weights=cw)
             tm = TorchResidual().to(dev).train()
@@ -156,9 +213,13 @@ def main():
         med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")   # noqa: E731
         h_ms, t_ms = med(hip), med(eager)
         extra = {}
-        if small:
-            nbytes = b * small_bytes_per_clip()
+        if small or std:
+            nbytes = b * (small_bytes_per_clip() if small else std_bytes_per_clip())
             extra = {"step_hbm_bytes": nbytes, "hip_hbm_bytes_per_s": round(nbytes / (h_ms * 1e-3), 1)}
+        if std and b in conv_ms:
+            conv_flops = b * 3 * std_flops_per_clip()[1]
+            extra["convs123_ms"] = conv_ms[b]
+            extra["convs123_share_of_f32_mfma_peak"] = round(conv_flops / (conv_ms[b] * 1e-3) / F32_MFMA_PEAK, 4)
         print(json.dumps({"model": a.model, "batch": b, "image": [H, W], "hip_ms": round(h_ms, 4), "torch_eager_ms": round(t_ms, 4),
                           "hip_clips_per_s": round(b / h_ms * 1e3, 1), "eager_clips_per_s": round(b / t_ms * 1e3, 1),
                           "speedup": round(t_ms / h_ms, 3), "hip_rounds_ms": [round(v, 4) for v in hip],
