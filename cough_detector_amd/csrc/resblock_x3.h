@@ -9,8 +9,8 @@
 //
 // One 4-wave workgroup = G clips.  A workgroup takes <= 80 KB of LDS, so that at least TWO share a CU and one's staging /
 // epilogue overlaps the other's MFMA phases, for block 0 up to 24 rows (images of up to 98 rows; the shipped 22 rows:
-// 73 KB) and block 1 at every height but 12 rows; block 0 at 26 / 27 rows (87 / 89 KB) and block 1 at 12 rows (86 KB,
-// two clips) run one workgroup per CU.
+// 73 KB) and block 1 at every height but 12 rows (the shipped 11x13, two clips: 81 440 B); block 0 at 26 / 27 rows
+// (87 / 89 KB) and block 1 at 12 rows (88 KB, two clips) run one workgroup per CU.
 //   * x is staged once into two un-bordered LDS planes (hi, lo).  A plane is chunk-planar -- [8-channel chunk][pixel]
 //     of 16-byte cells -- and its pixels are stored parity-split (even / odd image rows x even / odd columns, each
 //     sub-image with the row pitch of the OUTPUT image), so the output pixels of a tile read, for any tap of the
@@ -22,13 +22,14 @@
 //   * MFMA operands are swapped (weights = A): a lane owns one pixel x 4 consecutive channels per accumulator quad,
 //     so h and the output tile are written with 8 / 16-byte LDS stores.  Weight fragments (hi, lo) stream from L2 in
 //     fragment order through a register ring.  Two bodies (RbxCfg::T16):
-//       - block 0 up to 26 rows (rbx_t16): v_mfma_f32_16x16x32_bf16 only.  Wave w owns output channels 16w..16w+15 of EVERY
-//         16-pixel tile (block 0 at 22x25: 143 pixels = 9 tiles, no partial-tile code path), so one (hi, lo) weight
-//         pair per k32-step feeds all nine tiles.  Activation fragments are fetched P tiles ahead.  A fragment read
-//         puts lanes 16c..16c+15 in chunk plane c; the plane pitch is padded to 256 B, so the ds_read_b128 lane
-//         groups cover all 16 cell residues mod 16; zeros come from a row of 16 cells read at the lane's own residue,
-//         so border reads are bank-conflict-free too.
-//       - block 1, and block 0 at 27 rows: v_mfma_f32_32x32x16_bf16; wave (mg, ng) owns up to MW 32-pixel tiles x one 32-channel
+//       - block 0 up to 26 rows and block 1 (rbx_t16): v_mfma_f32_16x16x32_bf16 only.  Wave w owns CT = 1 (block 0) or
+//         2 (block 1) 16-channel tiles of EVERY 16-pixel tile (block 0 at 22x25: 143 pixels = 9 tiles; block 1 at 11x13:
+//         2 clips x 42 pixels = 6 tiles; no partial-tile code path), so CT (hi, lo) weight pairs per k32-step feed all
+//         the tiles.  Activation fragments are fetched P tiles ahead.  A fragment read puts lanes 16c..16c+15 in chunk
+//         plane c (+ 4 for block 1's second k32-step of a conv1 tap); planes are laid out so that the ds_read_b128
+//         lane groups cover all 16 cell residues mod 16, and zeros come from rows of 16 cells read at the residue of
+//         the lane's in-image cell, so border reads are bank-conflict-free too (RbxCfg).
+//       - block 0 at 27 rows: v_mfma_f32_32x32x16_bf16; wave (mg, ng) owns up to MW 32-pixel tiles x one 32-channel
 //         tile; activation fragments are fetched one k-step ahead.  The 32 lanes of a chunk read 32 consecutive cells,
 //         conflict-free at any plane alignment.
 //   * epilogue: ReLU(acc2 + b2) -> f32 [pixel][COUT] tile in LDS -> one contiguous run of 16-byte global stores;
@@ -74,11 +75,15 @@ struct RbxArgs {
     const int* nanflag;   // fused head: [B] or nullptr; 1 = the clip's image holds a NaN -> NaN logits (nn_common.h: NaN rule)
 };
 
-// Which body a block runs.  The 16x16x32 body needs one 16-channel tile per wave and one k32-step per conv1 tap
-// (block 0: 32 -> 64 channels).  It runs at block-0 heights up to 26 rows; at 27 rows (110-row images) the 32x32x16 body
-// was faster (same-box kernel trace: 315 against 322 us; 26 rows: 312 against 307 us; profiles/r06_block0_t16.txt).
-constexpr bool rbx_t16_shape(int cin, int cout) { return cin == 32 && cout == 64; }
-constexpr bool rbx_t16(int cin, int cout, int xh) { return rbx_t16_shape(cin, cout) && xh <= 26; }
+// Which body a block runs.  The 16x16x32 body needs one or two 16-channel tiles per wave and at most two clips per
+// workgroup (block 0: 32 -> 64 channels, one clip; block 1: 64 -> 128 channels, one or two clips).  Block 0 runs it up
+// to 26 rows; at 27 rows (110-row images) the 32x32x16 body was faster (same-box kernel trace: 315 against 322 us;
+// 26 rows: 312 against 307 us; profiles/r06_block0_t16.txt).  Block 1 runs it at every compiled height: 2-16 % faster
+// than the 32x32x16 body at 8-14 rows (profiles/r07_block1_t16.txt).
+constexpr bool rbx_t16_shape(int cin, int cout) { return (cin == 32 && cout == 64) || (cin == 64 && cout == 128); }
+constexpr bool rbx_t16(int cin, int cout, int xh) {
+    return rbx_t16_shape(cin, cout) && (cin == 64 || xh <= 26);
+}
 
 template <int CIN, int COUT, int G, int XH, int XW>
 struct RbxCfg {
@@ -90,30 +95,55 @@ struct RbxCfg {
     static constexpr int NT = COUT / 32, MG = WAVES / NT, TILES = (M + 31) / 32;
     static constexpr int MW = (TILES + MG - 1) / MG;
     static constexpr int KS1 = 9 * CIN / 16, KSP = CIN / 16, KS2 = 9 * COUT / 16, KS = KS1 + KSP + KS2;
-    // T16 body: NP 16-pixel tiles per wave, 32-wide k-steps
-    static constexpr int NP = (M + 15) / 16;
+    // T16 body: CT 16-channel tiles and NP 16-pixel tiles per wave, 32-wide k-steps
+    static constexpr int CT = COUT / 16 / WAVES, NP = (M + 15) / 16;
     static constexpr int KQ1 = 9 * CIN / 32, KQP = CIN / 32, KQ2 = 9 * COUT / 32, KQ = KQ1 + KQP + KQ2;
-    static_assert(!T16 || (COUT / 16 == WAVES && CIN == 32 && G == 1),
-                  "T16: one 16-channel tile per wave, one k32-step per conv1 tap (one x zero row serves every chunk plane), "
-                  "one clip (16 consecutive pixels = 16 consecutive cells)");
+    static_assert(!T16 || ((CT == 1 || CT == 2) && COUT == 16 * CT * WAVES && (CIN == 32 || CIN == 64) && G <= 2 &&
+                           PER >= 16),
+                  "T16: one or two 16-channel tiles per wave, one or two k32-steps per conv1 tap, at most one 16-pixel "
+                  "tile straddling two clips");
     static constexpr int CHI = CIN / 8, CHO = COUT / 8;
     // x planes: parity-split pixel order.  Sub-image (row parity a, column parity b) holds pixels (2i + a, 2j + b) at
     // i * OW + j; RE / RO = number of even / odd rows; the odd-column sub-images of an odd XW carry one unused column.
     static constexpr int RE = (XH + 1) / 2, RO = XH / 2;
     static constexpr int NPP = 2 * XH * OW;                                  // cells of one clip in one chunk plane
     static constexpr int PB01 = RE * OW, PB10 = 2 * RE * OW, PB11 = 2 * RE * OW + RO * OW;   // sub-image bases (PB00 = 0)
+    // x cells between the starts of two clips in a chunk plane.  T16 with two clips: NPP rounded so that NPPC - PER is
+    // a multiple of 16, and the 16 pixels of a tile that straddles the clips still read 16 distinct residues mod 16.
+    static constexpr int NPPC = T16 && G > 1 ? PER + (NPP - PER + 15) / 16 * 16 : NPP;
     // Bytes of one x / h chunk plane and the zero cells that taps outside the image read.  32x32x16 body: one zero cell
-    // at the end of each chunk plane (byte offset ZX / ZH inside the plane).  T16: plane pitches are multiples of 256 B
-    // (conflict-free 16x16x32 fragment reads), and zeros come as 256-B-aligned rows of 16 cells, so that a lane reading
-    // zeros hits the banks its in-image cell would have hit: one row after the CHI x chunk planes (ZX counts from the
-    // start of the x planes; conv1 and the projection read chunk plane (lane >> 4) only), one row at the end of each h
-    // chunk plane (conv2's second k32-step of a tap reads chunk plane 4 + (lane >> 4) at an immediate offset).
+    // at the end of each chunk plane (byte offset ZX / ZH inside the plane).
+    // T16: a ds_read_b128 lane group (MI355X: lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same in the upper
+    // half) takes complementary pixels from chunk planes (lane >> 4) = 0 and 1 (2 and 3), so planes read by lanes 16
+    // apart must lie a multiple of 256 B apart; zeros come from 256-B-aligned rows of 16 cells, and a lane whose tap
+    // lies outside the image reads the zero cell with the bank residue of its in-image cell.
+    //   x, CIN = 32 (conv1 and the projection read chunk plane lane >> 4 only): planes padded to 256 B, one zero row after
+    //     the four.
+    //   x, CIN = 64: a tap's second k32-step reads plane 4 + (lane >> 4) at the immediate offset KX.  Planes are padded to
+    //     64 B only (so that four of them span a multiple of 256 B), in the order
+    //       [zero row][x0][x2][zero row][x4][x6][x1][x3][256 B unused][x5][x7],
+    //     which puts x1 / x3 / x5 / x7 4 planes + 256 B past x0 / x2 / x4 / x6, every plane c + 4 KX = 2 planes + 256 B
+    //     past plane c, and the second zero row KX past the first.  Padding every plane to 256 B would take block 1 at
+    //     11x13 past 80 KB, and one workgroup per CU.
+    //   h: planes padded to 256 B, one zero row at the end of each (conv2's k32-step c of a tap reads chunk plane
+    //     4c + (lane >> 4) at an immediate offset).
     static constexpr int ZC = T16 ? 16 : 1;
-    static constexpr int CPX = T16 ? (G * NPP * 16 + 255) / 256 * 256 : (G * NPP + 1) * 16;
-    static constexpr int ZX = T16 ? CHI * CPX : G * NPP * 16;
+    static constexpr int CPX = !T16 ? (G * NPP + 1) * 16 : CHI == 4 ? (G * NPPC * 16 + 255) / 256 * 256 : (G * NPPC * 16 + 63) / 64 * 64;
+    static constexpr int xoff(int c) {   // byte offset of x chunk plane c
+        if (!T16 || CHI == 4) return c * CPX;
+        const int s = (c & 1) * 4 + (c >> 1);
+        return 256 + s * CPX + (s >= 2 ? 256 : 0) + (s >= 6 ? 256 : 0);
+    }
+    static constexpr int ZX = !T16 ? G * NPP * 16 : CHI == 4 ? 4 * CPX : 0;
+    static constexpr int KX = T16 && CHI == 8 ? xoff(4) - xoff(0) : 0;
     static constexpr int ZH = T16 ? (M * 16 + 255) / 256 * 256 : M * 16;
     static constexpr int CPH = ZH + ZC * 16;
-    static constexpr int XBYTES = CHI * CPX + (T16 ? ZC * 16 : 0), HBYTES = CHO * CPH;
+    static constexpr int XBYTES = !T16 ? CHI * CPX : CHI == 4 ? 4 * CPX + 256 : xoff(7) + CPX, HBYTES = CHO * CPH;
+    static_assert(!T16 || (ZX % 256 == 0 && CPH % 256 == 0 && (G == 1 || (NPPC - PER) % 16 == 0)), "T16 bank residues");
+    static_assert(!T16 || CHI == 4 || ((xoff(1) - xoff(0)) % 256 == 0 && (xoff(3) - xoff(2)) % 256 == 0 &&
+                                       xoff(5) - xoff(1) == KX && xoff(6) - xoff(2) == KX && xoff(7) - xoff(3) == KX &&
+                                       xoff(0) >= ZX + 256 && xoff(2) + CPX <= ZX + KX && xoff(4) >= ZX + KX + 256),
+                  "T16 x layout, CIN = 64");
     static constexpr int PL = (((XBYTES > HBYTES ? XBYTES : HBYTES) + 255) / 256) * 256;   // pitch between the hi and lo planes
     static constexpr int BIAS = 2 * PL;                                      // b1[COUT], b2[COUT] f32
     static constexpr int HRED = BIAS + 2 * COUT * 4;                         // head reduction scratch [WAVES][2] f32
@@ -124,7 +154,10 @@ struct RbxCfg {
     static_assert(M * OP * 4 <= 2 * PL, "the output tile lies over the planes");
     static constexpr int STAGE_MAX = 18;                                     // 16-byte pieces per thread staged in one batch
     static_assert((G * NPX * CIN / 4 + THREADS - 1) / THREADS <= 2 * STAGE_MAX, "staging registers (f32 input, two batches)");
-    static_assert(LDS <= 160 * 1024, "one workgroup must fit a CU (two do for the shipped image)");
+    static_assert(LDS <= 160 * 1024, "one workgroup must fit a CU");
+    // two workgroups per CU (one's staging / epilogue overlaps the other's MFMA phases): block 0 up to 24 rows, block 1
+    // at every compiled height but 12 rows (two clips of 6x7 outputs)
+    static_assert(LDS <= 80 * 1024 || (CIN == 32 && XH > 24) || (CIN == 64 && XH == 12), "two workgroups per CU");
 };
 
 template <int CIN, int COUT, int G, int XH, int XW>
@@ -134,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     constexpr bool T16 = Cfg::T16;
     using f32x4 = __attribute__((ext_vector_type(4))) float;
     constexpr int CHI = Cfg::CHI, CHO = Cfg::CHO, PL = Cfg::PL, OP = Cfg::OP, CPX = Cfg::CPX, CPH = Cfg::CPH, NPP = Cfg::NPP;
-    constexpr int ZX = Cfg::ZX, ZH = Cfg::ZH, ZC = Cfg::ZC;   // the zero cells (RbxCfg)
+    constexpr int ZX = Cfg::ZX, KX = Cfg::KX, ZH = Cfg::ZH, ZC = Cfg::ZC, NPPC = Cfg::NPPC;   // the zero cells (RbxCfg)
 #ifndef RBX_D
 #define RBX_D 4
 #endif
@@ -161,15 +194,20 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     if (tid < COUT) { bv1 = a.b1[tid]; bv2 = a.b2[tid]; }
 
     // ---- weight fragment stream (hi, lo per k-step): the first DW k-steps are in flight during the staging ----
-    constexpr int DW = T16 ? RBX_DQ : RBX_D;   // prefetch depth in k-steps (T16: one k32-step = NP x 3 MFMAs >= 336 cycles)
-    const bf16_t* wbase = a.wf + size_t(T16 ? wave : wave % Cfg::NT) * 1024 + lane * 8;
-    constexpr int WSTEP = T16 ? Cfg::WAVES : Cfg::NT;   // channel tiles per k-step in the fragment array
-    auto wfrag = [&](int s, int plane) -> bf16x8 {
-        return *reinterpret_cast<const bf16x8*>(wbase + (size_t(s) * WSTEP * 2 + plane) * 512);
+    // prefetch depth in k-steps (T16: one k32-step = NP x CT x 3 MFMAs >= 288 cycles).  Block 1 with one clip (13 / 14
+    // rows, NP = 4) holds 2 k32-steps, so that it stays within 168 VGPRs and three workgroups per CU.
+    constexpr int CT = T16 ? Cfg::CT : 1;      // channel tiles per wave and k-step in the ring
+    constexpr int DW = !T16 ? RBX_D : CT == 2 && G == 1 ? 2 : RBX_DQ;
+    const bf16_t* wbase = a.wf + size_t(T16 ? wave * CT : wave % Cfg::NT) * 1024 + lane * 8;
+    constexpr int WSTEP = T16 ? COUT / 16 : Cfg::NT;   // channel tiles per k-step in the fragment array
+    auto wfrag = [&](int s, int ct, int plane) -> bf16x8 {
+        return *reinterpret_cast<const bf16x8*>(wbase + ((size_t(s) * WSTEP + ct) * 2 + plane) * 512);
     };
-    bf16x8 ring[DW][2];
+    bf16x8 ring[DW][CT][2];
 #pragma unroll
-    for (int i = 0; i < DW; ++i) { ring[i][0] = wfrag(i, 0); ring[i][1] = wfrag(i, 1); }
+    for (int i = 0; i < DW; ++i)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) { ring[i][ct][0] = wfrag(i, ct, 0); ring[i][ct][1] = wfrag(i, ct, 1); }
 
     // ---- stage: the clips' x (f32) is one linear run of 16-byte pieces = 4 channels of one pixel; all loads are
     // issued first, then each piece is split and its hi / lo halves go to the swizzled chunk of the two planes ----
@@ -181,8 +219,11 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         const int valid = nvalid * NPX * QP;
         const float4* src = reinterpret_cast<const float4*>(a.x + (long long)clip0 * NPX * CIN);
         if constexpr (T16) {
-            if (tid < 2 * ZC)   // the zero row, hi and lo
-                *reinterpret_cast<uint4*>(smem + (tid / ZC) * PL + ZX + (tid % ZC) * 16) = make_uint4(0, 0, 0, 0);
+            constexpr int NZ = CHI / 4;   // the zero rows (one per k32-step of a tap), hi and lo
+            if (tid < 2 * NZ * ZC) {
+                const int k = tid / ZC;
+                *reinterpret_cast<uint4*>(smem + (k / NZ) * PL + ZX + (k % NZ) * KX + (tid % ZC) * 16) = make_uint4(0, 0, 0, 0);
+            }
         } else if (tid < 2 * CHI) {   // the zero cell of every chunk plane, hi and lo
             *reinterpret_cast<uint4*>(smem + (tid / CHI) * PL + (tid % CHI) * CPX + ZX) = make_uint4(0, 0, 0, 0);
         }
@@ -202,12 +243,12 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 if (i < NPIECE) {
                     const int P = i / QP, q = i % QP;                      // raster pixel (clip, row, column), quarter-chunk
                     const int g = P / NPX, rem = P % NPX, ih = rem / XW, iw = rem % XW;
-                    const int cell = g * NPP + ((ih & 1) ? ((iw & 1) ? Cfg::PB11 : Cfg::PB10) : ((iw & 1) ? Cfg::PB01 : 0)) +
+                    const int cell = g * NPPC + ((ih & 1) ? ((iw & 1) ? Cfg::PB11 : Cfg::PB10) : ((iw & 1) ? Cfg::PB01 : 0)) +
                                      (ih >> 1) * OW + (iw >> 1);
                     uint2 hi, lo;
                     if (i >= valid) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);   // clips beyond the batch read as zeros
                     split4(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
-                    const int off = (q >> 1) * CPX + cell * 16 + (q & 1) * 8;
+                    const int off = Cfg::xoff(q >> 1) + cell * 16 + (q & 1) * 8;
                     *reinterpret_cast<uint2*>(smem + off) = hi;
                     *reinterpret_cast<uint2*>(smem + off + PL) = lo;
                 }
@@ -252,15 +293,15 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     }
 
     // ---- T16 body: lane l owns pixel (l & 15) of every 16-pixel tile and chunk (l >> 4) of every 32-wide k-step;
-    // its accumulator quads are channels 16 * wave + 4 * (l >> 4) .. +3 ----
+    // its accumulator quads are channels n0 + 16 ct .. +3 (n0 = 16 CT wave + 4 (l >> 4), channel tile ct < CT) ----
     constexpr int NP = Cfg::NP, KQ1 = Cfg::KQ1, KQP = Cfg::KQP, KQ = Cfg::KQ, P = RBX_P, NB = P + 1;
     constexpr int NI = KQ * NP, I2 = (KQ1 + KQP) * NP;   // (k32-step, tile) pairs; the first pair of conv2
-    const int px = lane & 15, tq = lane >> 4, n0 = 16 * wave + 4 * tq;
+    const int px = lane & 15, tq = lane >> 4, n0 = 16 * CT * wave + 4 * tq;
     // per tile: bit tap (0..8) = conv1 tap (kh, kw) = tap / 3, tap % 3 lies inside x; bit 9 + tap: conv2 tap inside h
     unsigned vm[NP];
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
-        const int R = 16 * t + px, oh = R / OW, ow = R % OW;
+        const int R = 16 * t + px, rem = G > 1 ? R % PER : R, oh = rem / OW, ow = rem % OW;
         unsigned m = 0;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -271,10 +312,16 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         }
         vm[t] = R < M ? m : 0u;   // a padding row reads the zero cell at every tap
     }
-    // G == 1: pixel R's cell of sub-image (0, 0) is R, so tile t's cells are this lane's base + 256 t bytes
-    const int lbx = px * 16 + tq * CPX, lbh = px * 16 + tq * CPH, zh = ZH + tq * CPH;
-    // the zero cell a lane reads for a tap outside the image: the one of the same residue mod 16 as its in-image cell
-    auto zcell = [&](int z, int coff) { return z + ((px + coff) & 15) * 16; };
+    // Pixel R of clip g has x cell g * NPPC + R - g * PER of sub-image (0, 0): tile t's cells are this lane's base +
+    // 256 t bytes, + DX from the tile past the clip boundary on; the one tile that straddles it takes its base from lbs.
+    // Pixel R's h cell is R.
+    constexpr int DX = (NPPC - PER) * 16;
+    const int lbx = px * 16 + Cfg::xoff(tq), lbh = px * 16 + tq * CPH, zh = ZH + tq * CPH;
+    const int lbs = lbx + (G > 1 && px >= PER % 16 ? DX : 0);
+    // the zero cell a lane reads for a tap outside the image: the one with the bank residue (mod 16 cells) of its
+    // in-image cell; rx is the residue of the lane's x cell of tile 0 (x planes with CIN = 64 are not 256-B aligned)
+    const int rx = px + (CHI == 4 ? 0 : Cfg::xoff(tq) / 16);
+    auto zcell = [&](int z, int res) { return z + (res & 15) * 16; };
     RB_STAMP(1);
     __syncthreads();
     RB_STAMP(2);
@@ -284,30 +331,33 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
 
     // ---- T16 body ----
     auto body16 = [&]() {
-        f32x4 acc1[NP], acc2[NP];
+        f32x4 acc1[CT][NP], acc2[CT][NP];
 #pragma unroll
-        for (int t = 0; t < NP; ++t) { acc1[t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int t = 0; t < NP; ++t) { acc1[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
         // Address of the hi fragment of pair i = (k32-step i / NP, tile i % NP), compile-time at every call site.  The
-        // tap's cell (base + compile-time offset) or the zero cell is chosen at the tap's first k32-step; further k32-steps
-        // of the tap (chunk planes) and the lo plane are immediate offsets.
+        // tap's cell (base + compile-time offset) or the zero cell is chosen at the tap's first k32-step; further
+        // k32-steps of the tap (chunk planes) and the lo plane are immediate offsets.
         int tadr[NP];
         auto aaddr = [&](auto ic) -> const char* {
             constexpr int i = decltype(ic)::value, q = i / NP, t = i % NP;
             constexpr bool conv1 = q < KQ1, proj = !conv1 && q < KQ1 + KQP;
             constexpr int kt = (conv1 ? q : proj ? q - KQ1 : q - KQ1 - KQP) * 32;   // k inside this operand
-            constexpr int C = (conv1 || proj) ? CIN : COUT, CP = (conv1 || proj) ? CPX : CPH;
+            constexpr int C = (conv1 || proj) ? CIN : COUT;
             constexpr int tap = proj ? 4 : kt / C, c32 = (kt % C) / 32, kh = tap / 3, kw = tap % 3;
             if constexpr (c32 == 0) {
                 if constexpr (conv1 || proj) {
-                    constexpr int off = 256 * t + 16 * tapx(kh, kw);
-                    tadr[t] = (vm[t] & (1u << tap)) ? lbx + off : zcell(ZX, tapx(kh, kw));
+                    constexpr bool strad = G > 1 && 16 * t < PER && 16 * t + 16 > PER;
+                    constexpr int off = 256 * t + (G > 1 && 16 * t >= PER ? DX : 0) + 16 * tapx(kh, kw);
+                    tadr[t] = (vm[t] & (1u << tap)) ? (strad ? lbs : lbx) + off : zcell(ZX, rx + tapx(kh, kw));
                 } else {
                     constexpr int off = 256 * t + 16 * ((kh - 1) * OW + kw - 1);
-                    tadr[t] = (vm[t] & (1u << (9 + tap))) ? lbh + off : zcell(zh, (kh - 1) * OW + kw - 1);
+                    tadr[t] = (vm[t] & (1u << (9 + tap))) ? lbh + off : zcell(zh, px + (kh - 1) * OW + kw - 1);
                 }
             }
-            return smem + tadr[t] + 4 * c32 * CP;
+            return smem + tadr[t] + c32 * ((conv1 || proj) ? KX : 4 * CPH);
         };
         bf16x8 af[NB][2];
         auto fetch = [&](auto ic) {
@@ -329,23 +379,26 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 __builtin_amdgcn_s_setprio(0);
 #endif
                 __syncthreads();
-                static_assert(2 * CHO * ZC <= THREADS, "one thread per zero cell");
-                if (tid < 2 * CHO * ZC) {   // the zero cells of every h chunk plane, hi and lo
-                    const int pl = tid / ZC;
-                    *reinterpret_cast<uint4*>(smem + (pl / CHO) * PL + (pl % CHO) * CPH + ZH + (tid % ZC) * 16) =
+                for (int z = tid; z < 2 * CHO * ZC; z += THREADS) {   // the zero cells of every h chunk plane, hi and lo
+                    const int pl = z / ZC;
+                    *reinterpret_cast<uint4*>(smem + (pl / CHO) * PL + (pl % CHO) * CPH + ZH + (z % ZC) * 16) =
                         make_uint4(0, 0, 0, 0);
                 }
-                const float4 bb = *reinterpret_cast<const float4*>(lbias + n0);
 #pragma unroll
-                for (int u = 0; u < NP; ++u) {
-                    const int R = 16 * u + px;
-                    uint2 hi, lo;
-                    split4(fmaxf(acc1[u][0] + bb.x, 0.f), fmaxf(acc1[u][1] + bb.y, 0.f), fmaxf(acc1[u][2] + bb.z, 0.f),
-                           fmaxf(acc1[u][3] + bb.w, 0.f), hi, lo);
-                    if (R < M) {
-                        const int off = (n0 >> 3) * CPH + R * 16 + ((n0 >> 2) & 1) * 8;
-                        *reinterpret_cast<uint2*>(smem + off) = hi;
-                        *reinterpret_cast<uint2*>(smem + off + PL) = lo;
+                for (int ct = 0; ct < CT; ++ct) {
+                    const int n = n0 + 16 * ct;
+                    const float4 bb = *reinterpret_cast<const float4*>(lbias + n);
+#pragma unroll
+                    for (int u = 0; u < NP; ++u) {
+                        const int R = 16 * u + px;
+                        uint2 hi, lo;
+                        split4(fmaxf(acc1[ct][u][0] + bb.x, 0.f), fmaxf(acc1[ct][u][1] + bb.y, 0.f),
+                               fmaxf(acc1[ct][u][2] + bb.z, 0.f), fmaxf(acc1[ct][u][3] + bb.w, 0.f), hi, lo);
+                        if (R < M) {
+                            const int off = (n >> 3) * CPH + R * 16 + ((n >> 2) & 1) * 8;
+                            *reinterpret_cast<uint2*>(smem + off) = hi;
+                            *reinterpret_cast<uint2*>(smem + off + PL) = lo;
+                        }
                     }
                 }
                 __syncthreads();
@@ -357,32 +410,32 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                     (fetch(std::integral_constant<int, I2 + Js>{}), ...);
                 }(std::make_integer_sequence<int, P>{});
             }
-            // One filler group in front of each of the pair's three MFMAs (~8 free issue cycles each): the address of
-            // pair i + P, its hi read, its lo read; the step's last tile also re-fills the weight ring slot it just
-            // finished with (hi after its last hi use, lo after the lo use).  A prefetch never crosses into conv2: h is
-            // written in between.
+            // The pair's 3 CT MFMAs, kind-major (whi * x_hi, whi * x_lo, wlo * x_hi; channel tiles inner), with one filler
+            // group in front of each (~8 free issue cycles): the address of pair i + P; after the last kind-0 MFMA its hi
+            // read, after the last kind-1 MFMA its lo read.  The step's last tile also re-fills the weight ring slot it
+            // just finished with: a tile's hi weights after its kind-1 MFMA, its lo weights after its kind-2 MFMA.  A
+            // prefetch never crosses into conv2: h is written in between.
             constexpr bool pf = j < NI && (j < I2) == (i < I2);
             constexpr bool wl = t == NP - 1 && q + DW < KQ;
-            const bf16x8 whi = ring[q % DW][0], wlo = ring[q % DW][1];
             const bf16x8 cur_hi = af[i % NB][0], cur_lo = af[i % NB][1];
             const char* np = nullptr;
             if constexpr (pf) np = aaddr(std::integral_constant<int, j>{});
+            [&]<int... Ms>(std::integer_sequence<int, Ms...>) {
+                ([&] {
+                    constexpr int m = Ms, kind = m / CT, ct = m % CT;
+                    const bf16x8 w = ring[q % DW][ct][kind == 2 ? 1 : 0];
+                    const bf16x8 x = kind == 1 ? cur_lo : cur_hi;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (q < KQ1) acc1[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc1[ct][t], 0, 0, 0);
+                    else acc2[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc2[ct][t], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (pf && m == CT - 1) af[j % NB][0] = *reinterpret_cast<const bf16x8*>(np);
+                    if constexpr (pf && m == 2 * CT - 1) af[j % NB][1] = *reinterpret_cast<const bf16x8*>(np + PL);
+                    if constexpr (wl && kind == 1) ring[q % DW][ct][0] = wfrag(q + DW, ct, 0);
+                    if constexpr (wl && kind == 2) ring[q % DW][ct][1] = wfrag(q + DW, ct, 1);
+                }(), ...);
+            }(std::make_integer_sequence<int, 3 * CT>{});
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (q < KQ1) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, cur_hi, acc1[t], 0, 0, 0);
-            else acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, cur_hi, acc2[t], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (pf) af[j % NB][0] = *reinterpret_cast<const bf16x8*>(np);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (q < KQ1) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, cur_lo, acc1[t], 0, 0, 0);
-            else acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, cur_lo, acc2[t], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (pf) af[j % NB][1] = *reinterpret_cast<const bf16x8*>(np + PL);
-            if constexpr (wl) ring[q % DW][0] = wfrag(q + DW, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (q < KQ1) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, cur_hi, acc1[t], 0, 0, 0);
-            else acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, cur_hi, acc2[t], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (wl) ring[q % DW][1] = wfrag(q + DW, 1);
         };
         [&]<int... Is>(std::integer_sequence<int, Is...>) {
             (pair.template operator()<Is>(), ...);
@@ -395,16 +448,19 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
 #endif
         __syncthreads();
         float* otile = reinterpret_cast<float*>(smem);
-        const float4 bb = *reinterpret_cast<const float4*>(lbias + COUT + n0);
 #pragma unroll
-        for (int t = 0; t < NP; ++t) {
-            const int R = 16 * t + px;
-            const float4 o = make_float4(fmaxf(acc2[t][0] + bb.x, 0.f), fmaxf(acc2[t][1] + bb.y, 0.f),
-                                         fmaxf(acc2[t][2] + bb.z, 0.f), fmaxf(acc2[t][3] + bb.w, 0.f));
-            if (R < M) *reinterpret_cast<float4*>(otile + R * OP + n0) = o;
+        for (int ct = 0; ct < CT; ++ct) {
+            const int n = n0 + 16 * ct;
+            const float4 bb = *reinterpret_cast<const float4*>(lbias + COUT + n);
+#pragma unroll
+            for (int t = 0; t < NP; ++t) {
+                const int R = 16 * t + px;
+                const float4 o = make_float4(fmaxf(acc2[ct][t][0] + bb.x, 0.f), fmaxf(acc2[ct][t][1] + bb.y, 0.f),
+                                             fmaxf(acc2[ct][t][2] + bb.z, 0.f), fmaxf(acc2[ct][t][3] + bb.w, 0.f));
+                if (R < M) *reinterpret_cast<float4*>(otile + R * OP + n) = o;
+            }
         }
     };
-
 
     auto body = [&]<int MWX>() {
         f32x16 acc1[MWX], acc2[MWX];
@@ -502,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
             // read (+ the lo weight load) -- so that no filler group is longer than the ~24 issue cycles an MFMA leaves
             // free.  Left alone, the scheduler sinks every ds_read next to its MFMA and each pays the LDS latency; one
             // filler group per MFMA triple (the first version) left the pipe idle behind every third MFMA (+2.3 %).
-            const bf16x8 whi = ring[s % D][0], wlo = ring[s % D][1];
+            const bf16x8 whi = ring[s % D][0][0], wlo = ring[s % D][0][1];
 #pragma unroll
             for (int mt = 0; mt < MWX; ++mt) {
                 constexpr bool pf = s + 1 < KS && s + 1 != KS1 + KSP;
@@ -514,13 +570,13 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 else acc2[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi, cur_hi, acc2[mt], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (pf) af[(s + 1) & 1][mt][0] = *reinterpret_cast<const bf16x8*>(np);
-                if constexpr (s + D < KS) { if (mt == 0) ring[s % D][0] = wfrag(s + D, 0); }
+                if constexpr (s + D < KS) { if (mt == 0) ring[s % D][0][0] = wfrag(s + D, 0, 0); }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (s < KS1) acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi, cur_lo, acc1[mt], 0, 0, 0);
                 else acc2[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi, cur_lo, acc2[mt], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (pf) af[(s + 1) & 1][mt][1] = *reinterpret_cast<const bf16x8*>(np + PL);
-                if constexpr (s + D < KS) { if (mt == 0) ring[s % D][1] = wfrag(s + D, 1); }
+                if constexpr (s + D < KS) { if (mt == 0) ring[s % D][0][1] = wfrag(s + D, 0, 1); }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (s < KS1) acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo, cur_hi, acc1[mt], 0, 0, 0);
                 else acc2[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo, cur_hi, acc2[mt], 0, 0, 0);

@@ -798,7 +798,7 @@ struct cough_resnet {
     void* d_w[4];          // packed [N][Ktot]: b0.conv1, b0.conv2+skip, b1.conv1, b1.conv2+skip
     cough::bf16_t* d_wfrag[4];   // bf16 mode: the same weights as MFMA fragments [K/16][N/32][64][8] (fused block kernels)
     cough::bf16_t* d_wx3[2];     // bf16x3 mode: split-bf16 32x32x16 fragments of block i (conv1, projection, conv2; RbxArgs::wf)
-    cough::bf16_t* d_wx3t16;     //   ... and block 0's 16x16x32 fragments (the heights rbx_t16 picks that body for)
+    cough::bf16_t* d_wx3t16[2];  //   ... and as 16x16x32 fragments (the heights rbx_t16 picks that body for)
     float* d_b[4];
     int ktot[4];
     float* d_fcw;          // [2][128]
@@ -832,9 +832,9 @@ int upload_x3(cough_resnet* m, int blk, const FoldedConv& c1, const FoldedConv& 
     std::vector<bf16_t> wf;
     pack_x3_fragments(wf, c1.w, 9 * c1.C, sk.w, sk.C, c2.w, 9 * c2.C, c1.N);
     if (int e = upload(reinterpret_cast<void**>(&m->d_wx3[blk]), wf)) return e;
-    if (blk != 0 || !rbx_t16_shape(c1.C, c1.N)) return COUGH_OK;
+    if (!rbx_t16_shape(c1.C, c1.N)) return COUGH_OK;
     pack_x3_t16_fragments(wf, c1.w, 9 * c1.C, sk.w, sk.C, c2.w, 9 * c2.C, c1.N);
-    return upload(reinterpret_cast<void**>(&m->d_wx3t16), wf);
+    return upload(reinterpret_cast<void**>(&m->d_wx3t16[blk]), wf);
 }
 
 int upload_packed(cough_resnet* m, int slot, const FoldedConv& main, const FoldedConv* skip) {
@@ -999,7 +999,7 @@ int launch_conv(const cough_resnet* m, const ConvArgs<T>& a, hipStream_t st) {
     return COUGH_OK;
 }
 
-// clips per workgroup of block 1 at the 13x13 / 14x13 inputs: 1 (48-52 KB of LDS, three workgroups per CU; two clips per
+// clips per workgroup of block 1 at the 13x13 / 14x13 inputs: 1 (49-53 KB of LDS, three workgroups per CU; two clips per
 // workgroup = 95-102 KB, one workgroup per CU, measured the same: profiles/r04_heights.txt)
 constexpr int RBX_G_TALL = 1;
 // block-input geometries resblock_x3_kernel is instantiated for (block index, rows, columns): every feature image the
@@ -1008,7 +1008,8 @@ constexpr int RBX_G_TALL = 1;
 //   95..98 24 -> 12 | 103..106 (delta-delta on) 26 -> 13 | 107..110 (+ contrast rows: the constructor's defaults) 27 -> 14
 #define RBX_BLOCK0_ROWS(X) X(16) X(17) X(22) X(23) X(24) X(26) X(27)
 #define RBX_BLOCK1_ROWS(X) X(8) X(9) X(11) X(12) X(13) X(14)
-// clips per workgroup of block 1: 2 up to 12 rows (the shipped 11x13: 95 KB of LDS, one workgroup per CU), RBX_G_TALL above
+// clips per workgroup of block 1: 2 up to 12 rows, RBX_G_TALL above.  The shipped 11x13 takes 81 440 B of LDS and 220
+// VGPRs: two workgroups per CU (12 rows: 89 632 B, one)
 constexpr int rbx_block1_clips(int xh) { return xh <= 12 ? 2 : RBX_G_TALL; }
 inline bool rbx_compiled(int blk, int xh, int xw) {
 #define RBX_HAS(R) || xh == R
@@ -1069,7 +1070,7 @@ int forward_impl(const cough_resnet* m, const float* d_feat, int n, const Shapes
                 RbxArgs ra{};
                 ra.x = reinterpret_cast<const float*>(k.x);
                 ra.n_clips = n;
-                ra.wf = rbx_t16(k.cin, k.cout, k.xh) ? m->d_wx3t16 : m->d_wx3[i];
+                ra.wf = rbx_t16(k.cin, k.cout, k.xh) ? m->d_wx3t16[i] : m->d_wx3[i];
                 ra.b1 = m->d_b[k.s1];
                 ra.b2 = m->d_b[k.s2];
                 ra.out = reinterpret_cast<float*>(k.out);
@@ -1336,7 +1337,8 @@ extern "C" void cough_resnet_destroy(cough_resnet* m) {
     }
     (void)hipFree(m->d_wx3[0]);
     (void)hipFree(m->d_wx3[1]);
-    (void)hipFree(m->d_wx3t16);
+    (void)hipFree(m->d_wx3t16[0]);
+    (void)hipFree(m->d_wx3t16[1]);
     (void)hipFree(m->d_fcw);
     (void)hipFree(m->d_fcb);
     delete m;
