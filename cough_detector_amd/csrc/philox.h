@@ -1,4 +1,4 @@
-// Counter-based random numbers shared by the training-side kernels (augment.hip, train.hip).
+// Counter-based random numbers shared by the training-side kernels (augment.hip, and train_common.h's dropout keep).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,7 +6,7 @@ namespace cough {
 namespace {
 
 // Philox4x32-10 (Salmon et al., SC'11): 128-bit counter c, 64-bit key k (the seed).  augment.hip counts (sample group, clip,
-// 0, 0); train.hip counts (channel group, clip, step offset lo, step offset hi).
+// 0, 0); the training steps count (unit group, clip, step offset lo, step offset hi).
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
     for (int r = 0; r < 10; ++r) {
         const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;

@@ -26,7 +26,7 @@
 
 #include "common.h"
 #include "nn_common.h"
-#include "philox.h"
+#include "train_common.h"
 
 namespace cough {
 namespace {
@@ -134,10 +134,6 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------ convolutions
-// MFMA 32x32x2 f32 operand / result layout: lane (r, h) supplies A[row r][k h] and B[k h][col r]; accumulator register
-// reg of lane (r, h) is C[row (reg & 3) + 8 (reg >> 2) + 4 h][col r].
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
 // stem forward: z[m][32] = conv7x7 s2 p3 (x) + bias, m = (b, oh, ow); K = 49 taps, two per MFMA
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ x, int H, int W, int OH, int OW, long long M,
                                                        const float* __restrict__ w /* [32][49] */,
@@ -301,23 +297,6 @@ __global__ __launch_bounds__(64) void wgrad_kernel(WgArgs a) {
         for (int reg = 0; reg < 16; ++reg) dst[(long long)acc_row(reg, h) * a.kp + nt * 32 + r] = acc[nt][reg];
 }
 
-// sum the S slabs in index order; column (kh, kw, ci) -> the OIHW weight gradient, column kcols -> the bias gradient
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, int S, int N, int kp, int kcols,
-                                                           int C, int KK, float* __restrict__ gw, float* __restrict__ gb) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= N * (kcols + 1)) return;
-    const int co = e / (kcols + 1), col = e - co * (kcols + 1);
-    const float* p = slab + (long long)co * kp + col;
-    float s = 0.f;
-    for (int i = 0; i < S; ++i) s += p[(long long)i * N * kp];
-    if (col == kcols) {
-        gb[co] = s;
-    } else {
-        const int t = col / C, ci = col - t * C;
-        gw[((long long)co * C + ci) * KK + t] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------ BatchNorm
 // stat[4][C] per BN: mean, invstd (forward); sum dy, sum dy * xhat (backward)
 
@@ -357,12 +336,12 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
     }
 }
 
-// Chan merge of the ranges in index order; batch mean / invstd, running statistics (momentum, unbiased variance),
-// num_batches_tracked + 1
-__global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nblk, long long M, long long rows_per, int C,
-                                         float eps, float momentum, float* __restrict__ run_mean,
-                                         float* __restrict__ run_var, long long* __restrict__ nbt,
-                                         float* __restrict__ stat) {
+// one block, one thread per channel: Chan merge of the rows_per ranges in index order; batch mean / invstd, running
+// statistics (momentum, unbiased variance), num_batches_tracked + 1
+__global__ void bn_stats_seq_merge_kernel(const float* __restrict__ part, int nblk, long long M, long long rows_per, int C,
+                                          float eps, float momentum, float* __restrict__ run_mean,
+                                          float* __restrict__ run_var, long long* __restrict__ nbt,
+                                          float* __restrict__ stat) {
     const int c = threadIdx.x;
     if (c >= C) return;
     double n = 0.0, mean = 0.0, m2 = 0.0;
@@ -382,17 +361,13 @@ __global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nbl
     if (c == 0) nbt[0] += 1;
 }
 
-__device__ __forceinline__ float bn_apply(float z, const float* stat, const float* g, const float* bt, int c, int C) {
-    return (z - stat[c]) * stat[C + c] * g[c] + bt[c];
-}
-
 // y = relu(bn(z))
 __global__ __launch_bounds__(256) void bn_relu_kernel(const float* __restrict__ z, long long n, int C,
                                                       const float* __restrict__ stat, const float* __restrict__ g,
                                                       const float* __restrict__ bt, float* __restrict__ y) {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const int c = int(e % C);
-        y[e] = fmaxf(bn_apply(z[e], stat, g, bt, c, C), 0.f);
+        y[e] = fmaxf(bn_act(z[e], stat, g, bt, c, C), 0.f);
     }
 }
 
@@ -404,7 +379,7 @@ __global__ __launch_bounds__(256) void bn_add_relu_kernel(const float* __restric
                                                           float* __restrict__ y) {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const int c = int(e % C);
-        y[e] = fmaxf(bn_apply(z2[e], st2, g2, b2, c, C) + bn_apply(zs[e], sts, gs, bs, c, C), 0.f);
+        y[e] = fmaxf(bn_act(z2[e], st2, g2, b2, c, C) + bn_act(zs[e], sts, gs, bs, c, C), 0.f);
     }
 }
 
@@ -424,7 +399,7 @@ __global__ __launch_bounds__(256) void stem_bn_pool_kernel(const float* __restri
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int oy = 2 * py + (j >> 1), ox = 2 * px + (j & 1);
-            const float v = fmaxf(bn_apply(z[((b * OH + oy) * OW + ox) * 32 + c], stat, g, bt, c, 32), 0.f);
+            const float v = fmaxf(bn_act(z[((b * OH + oy) * OW + ox) * 32 + c], stat, g, bt, c, 32), 0.f);
             if (j == 0 || v > best) { best = v; k = j; }
         }
         p[e] = best;
@@ -483,9 +458,10 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(DySrc src, const fl
     }
 }
 
-// ranges in index order -> stat[2..3], dgamma = sum dy * xhat, dbeta = sum dy
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C, float* __restrict__ stat,
-                                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
+// one block, one thread per channel: the rows_per ranges summed in index order -> stat[2..3], dgamma = sum dy * xhat,
+// dbeta = sum dy
+__global__ void bn_bwd_seq_merge_kernel(const float* __restrict__ part, int nblk, int C, float* __restrict__ stat,
+                                        float* __restrict__ dgamma, float* __restrict__ dbeta) {
     const int c = threadIdx.x;
     if (c >= C) return;
     float s = 0.f, sx = 0.f;
@@ -528,15 +504,7 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
     float s = 0.f;
     for (int i = 0; i < HW; ++i) s += src[(long long)i * HEAD_C];
     const float gap = s / float(HW);
-    float keep;
-    if (mask_in) {
-        keep = mask_in[(long long)b * HEAD_C + c];
-    } else {
-        const uint4 r = philox4x32_10(make_uint4(unsigned(c >> 2), unsigned(b), unsigned(offset), unsigned(offset >> 32)),
-                                      make_uint2(unsigned(seed), unsigned(seed >> 32)));
-        const unsigned v = (c & 3) == 0 ? r.x : (c & 3) == 1 ? r.y : (c & 3) == 2 ? r.z : r.w;
-        keep = (float(v >> 8) * (1.0f / 16777216.0f) >= p) ? 1.f : 0.f;
-    }
+    const float keep = mask_in ? mask_in[(long long)b * HEAD_C + c] : dropout_keep(c, b, seed, offset, p);
     const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
     const float d = gap * (keep * scale);
     dvec[(long long)b * HEAD_C + c] = d;
@@ -547,19 +515,7 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
     __syncthreads();
     if (c == 0) {
         const float z0 = (red[0][0] + red[1][0]) + fcb[0], z1 = (red[0][1] + red[1][1]) + fcb[1];
-        logits[2 * b] = z0;
-        logits[2 * b + 1] = z1;
-        const long long y = targets[b];
-        if (y == 0 || y == 1) {
-            const float mx = fmaxf(z0, z1);
-            const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-            const float wt = class_w ? class_w[y] : 1.f;
-            wnll[2 * b] = wt * (lse - (y ? z1 : z0));
-            wnll[2 * b + 1] = wt;
-        } else {                                // a target outside [0, 2): the loss is NaN (torch raises instead)
-            wnll[2 * b] = __builtin_nanf("");
-            wnll[2 * b + 1] = __builtin_nanf("");
-        }
+        ce_terms(b, z0, z1, targets, class_w, logits, wnll);
     }
 }
 
@@ -592,13 +548,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int HW, const floa
     __syncthreads();
     const float inv_w = 1.0f / tot[1];
     for (int b = t; b < B; b += 256) {
-        const float z0 = logits[2 * b], z1 = logits[2 * b + 1];
-        const float mx = fmaxf(z0, z1);
-        const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
-        const long long y = targets[b];
-        const float k = wnll[2 * b + 1] * inv_w;
-        dl[2 * b] = k * (e0 * inv - (y == 0 ? 1.f : 0.f));
-        dl[2 * b + 1] = k * (e1 * inv - (y == 1 ? 1.f : 0.f));
+        const float2 d = clip_dlogits(logits, targets, b, wnll[2 * b + 1] * inv_w);
+        dl[2 * b] = d.x;
+        dl[2 * b + 1] = d.y;
     }
     __syncthreads();
     {
@@ -660,8 +612,6 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ prm, flo
 }
 
 // ------------------------------------------------------------------------------------------ workspace
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
 struct TWs {
     float *wt, *wd;
     float *z0, *p0, *dz0, *dp0;
@@ -674,13 +624,8 @@ struct TWs {
 
 TWs carve(char* base, int B, const TShapes& s) {
     TWs w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    auto f = [&](long long n) { return reinterpret_cast<float*>(take(size_t(n) * 4)); };
+    Carver ws{base};
+    auto f = [&](long long n) { return ws.floats(n); };
     const Layout L = make_layout();
     w.wt = f(L.n_params);
     w.wd = f(L.n_params);
@@ -689,7 +634,7 @@ TWs carve(char* base, int B, const TShapes& s) {
     w.dz0 = f(m0 * 32);
     w.p0 = f(mp * 32);
     w.dp0 = f(mp * 32);
-    w.idx = reinterpret_cast<unsigned char*>(take(size_t(mp) * 32));
+    w.idx = reinterpret_cast<unsigned char*>(ws.take(size_t(mp) * 32));
     long long wg_most = 0, part_most = 0;
     for (int k = 0; k < 2; ++k) {
         const int c1 = 1 + 3 * k, C = KGEO[c1][1];
@@ -713,11 +658,11 @@ TWs carve(char* base, int B, const TShapes& s) {
     w.wnll = f(2LL * B);
     w.dl = f(2LL * B);
     w.slab = f(wg_most);
-    w.total = off;
+    w.total = ws.off;
     return w;
 }
 
-int grid_for(long long n) { return int(std::min<long long>((n + 255) / 256, 4096)); }
+constexpr int GRID_CAP = 4096;    // blocks of a grid-stride launch
 
 struct Step {
     const Layout& L;
@@ -767,7 +712,7 @@ struct Step {
         const long long M = rows(i), rp = bn_rows_per(M);
         const int nb = bn_nblk(M);
         hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nb), dim3(256), 0, st, z, M, C, rp, w.part);
-        hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(1), dim3(128), 0, st, w.part, nb, M, rp, C, eps, momentum,
+        hipLaunchKernelGGL(bn_stats_seq_merge_kernel, dim3(1), dim3(128), 0, st, w.part, nb, M, rp, C, eps, momentum,
                            running + L.run[i], running + L.run[i] + C, nbt + i, w.stat[i]);
     }
     void bn_backward(int i, const DySrc& src, const float* z, float* dz) const {
@@ -775,14 +720,12 @@ struct Step {
         const long long M = rows(i), rp = bn_rows_per(M);
         const int nb = bn_nblk(M);
         hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nb), dim3(256), 0, st, src, z, w.stat[i], M, C, rp, w.part);
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(1), dim3(128), 0, st, w.part, nb, C, w.stat[i], grd + L.bn_g[i],
+        hipLaunchKernelGGL(bn_bwd_seq_merge_kernel, dim3(1), dim3(128), 0, st, w.part, nb, C, w.stat[i], grd + L.bn_g[i],
                            grd + L.bn_b[i]);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * C)), dim3(256), 0, st, src, z, w.stat[i],
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * C, GRID_CAP)), dim3(256), 0, st, src, z, w.stat[i],
                            prm + L.bn_g[i], M, C, float(1.0 / double(M)), dz);
     }
 };
-
-bool finite_f(float v) { return std::isfinite(v); }
 
 }  // namespace
 }  // namespace cough
@@ -803,8 +746,6 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
                                             float* d_loss, float* d_logits, float* d_mask_out, void* d_workspace,
                                             size_t workspace_bytes, void* stream) {
     using namespace cough;
-    COUGH_REQUIRE(d_x && d_targets && d_params && d_grads && d_running && d_num_batches && d_loss && d_logits && d_workspace,
-                  COUGH_EINVAL, "cough_train_forward_backward: NULL argument");
     COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL,
                   "cough_train_forward_backward: bad shape (%d, %d, %d)", n_clips, height, width);
     const TShapes s = make_tshapes(height, width);
@@ -813,13 +754,12 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
     for (int i = 0; i < NCONV; ++i)
         COUGH_REQUIRE((long long)n_clips * s.oh[i] * s.ow[i] > 1, COUGH_EINVAL,
                       "cough_train_forward_backward: BatchNorm %d sees one value per channel (batch statistics need more)", i);
-    COUGH_REQUIRE(p >= 0.f && p <= 1.f, COUGH_EINVAL, "cough_train_forward_backward: dropout p must be in [0, 1]");
-    COUGH_REQUIRE(finite_f(momentum) && momentum >= 0.f && momentum <= 1.f && finite_f(eps) && eps >= 0.f, COUGH_EINVAL,
-                  "cough_train_forward_backward: bad BatchNorm momentum / eps");
-    COUGH_REQUIRE((reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL,
-                  "cough_train_forward_backward: workspace must be 256-byte aligned");
     const TWs w = carve(static_cast<char*>(d_workspace), n_clips, s);
-    COUGH_REQUIRE(workspace_bytes >= w.total, COUGH_EWORKSPACE, "cough_train_forward_backward: workspace too small");
+    if (const int rc = check_step_args(__func__, {d_x, d_targets, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
+                                                  d_workspace},
+                                       {p}, momentum, eps, d_workspace, workspace_bytes, w.total);
+        rc != COUGH_OK)
+        return rc;
 
     const Layout L = make_layout();
     const int B = n_clips;
@@ -834,8 +774,8 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
     hipLaunchKernelGGL(stem_fwd_kernel, dim3(unsigned((M0 + 127) / 128)), dim3(256), 0, st, d_x, height, width, s.oh[0],
                        s.ow[0], M0, w.wt + L.conv_w[0], d_params + L.conv_b[0], w.z0);
     S.bn_stats(0, w.z0);
-    hipLaunchKernelGGL(stem_bn_pool_kernel, dim3(grid_for(MP * 32)), dim3(256), 0, st, w.z0, s.oh[0], s.ow[0], s.P1h, s.P1w,
-                       MP * 32, w.stat[0], d_params + L.bn_g[0], d_params + L.bn_b[0], w.p0, w.idx);
+    hipLaunchKernelGGL(stem_bn_pool_kernel, dim3(grid_for(MP * 32, GRID_CAP)), dim3(256), 0, st, w.z0, s.oh[0], s.ow[0], s.P1h,
+                       s.P1w, MP * 32, w.stat[0], d_params + L.bn_g[0], d_params + L.bn_b[0], w.p0, w.idx);
     for (int k = 0; k < 2; ++k) {
         const int c1 = 1 + 3 * k, c2 = c1 + 1, sk = c1 + 2, C = KGEO[c1][1];
         const TWs::Blk& q = w.blk[k];
@@ -843,13 +783,13 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
         const long long n = S.rows(c1) * C;
         S.conv_fwd(c1, in, q.z1);
         S.bn_stats(c1, q.z1);
-        hipLaunchKernelGGL(bn_relu_kernel, dim3(grid_for(n)), dim3(256), 0, st, q.z1, n, C, w.stat[c1], d_params + L.bn_g[c1],
-                           d_params + L.bn_b[c1], q.h);
+        hipLaunchKernelGGL(bn_relu_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, st, q.z1, n, C, w.stat[c1],
+                           d_params + L.bn_g[c1], d_params + L.bn_b[c1], q.h);
         S.conv_fwd(c2, q.h, q.z2);
         S.bn_stats(c2, q.z2);
         S.conv_fwd(sk, in, q.zs);
         S.bn_stats(sk, q.zs);
-        hipLaunchKernelGGL(bn_add_relu_kernel, dim3(grid_for(n)), dim3(256), 0, st, q.z2, q.zs, n, C, w.stat[c2],
+        hipLaunchKernelGGL(bn_add_relu_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, st, q.z2, q.zs, n, C, w.stat[c2],
                            d_params + L.bn_g[c2], d_params + L.bn_b[c2], w.stat[sk], d_params + L.bn_g[sk],
                            d_params + L.bn_b[sk], q.out);
     }
@@ -908,7 +848,7 @@ extern "C" int cough_adamw_step(float* d_params, float* d_grads, float* d_exp_av
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(NORM_THREADS), 0, st, d_grads, n, d_total_norm);
     const float step_size = float(double(lr) / bias_correction1), bc2_sqrt = float(std::sqrt(bias_correction2));
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, st, d_params, d_grads, d_exp_avg, d_exp_avg_sq, n,
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, st, d_params, d_grads, d_exp_avg, d_exp_avg_sq, n,
                        d_total_norm, max_norm, lr, beta1, beta2, eps, weight_decay, step_size, bc2_sqrt);
     COUGH_HIP_CHECK(hipGetLastError());
     return COUGH_OK;

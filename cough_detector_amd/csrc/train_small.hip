@@ -27,7 +27,6 @@
 #include <cstdint>
 
 #include "common.h"
-#include "philox.h"
 #include "train_common.h"
 
 namespace cough {
@@ -262,14 +261,14 @@ __global__ __launch_bounds__(NT) void bn_relu_pool_kernel(const float* __restric
 
 // head, one block (128 threads) per clip: mean of relu(bn(z3)) -> Linear(128, 64) -> ReLU -> dropout -> Linear(64, 2)
 // -> weighted CE terms
-__global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__ z3, int HW, const float* __restrict__ st3,
-                                                       const float* __restrict__ prm, const float* __restrict__ mask_in,
-                                                       unsigned long long seed, unsigned long long offset, float p,
-                                                       const long long* __restrict__ targets,
-                                                       const float* __restrict__ class_w, float* __restrict__ logits,
-                                                       float* __restrict__ gap, float* __restrict__ hr,
-                                                       float* __restrict__ mask, float* __restrict__ mask_out,
-                                                       float* __restrict__ wnll) {
+__global__ __launch_bounds__(128) void mlp_head_fwd_kernel(const float* __restrict__ z3, int HW, const float* __restrict__ st3,
+                                                           const float* __restrict__ prm, const float* __restrict__ mask_in,
+                                                           unsigned long long seed, unsigned long long offset, float p,
+                                                           const long long* __restrict__ targets,
+                                                           const float* __restrict__ class_w, float* __restrict__ logits,
+                                                           float* __restrict__ gap, float* __restrict__ hr,
+                                                           float* __restrict__ mask, float* __restrict__ mask_out,
+                                                           float* __restrict__ wnll) {
     __shared__ float sg[128], shd[HID];
     const int c = threadIdx.x, b = blockIdx.x;
     const float* src = z3 + ((long long)b * 128 + c) * HW;
@@ -280,18 +279,8 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
     gap[(long long)b * 128 + c] = gv;
     __syncthreads();
     if (c < HID) {
-        float hv = prm[FC1_B + c];
-        for (int k = 0; k < 128; ++k) hv += prm[FC1_W + c * 128 + k] * sg[k];
-        hv = fmaxf(hv, 0.f);
-        float keep;
-        if (mask_in) {
-            keep = mask_in[(long long)b * HID + c];
-        } else {
-            const uint4 r = philox4x32_10(make_uint4(unsigned(c >> 2), unsigned(b), unsigned(offset), unsigned(offset >> 32)),
-                                          make_uint2(unsigned(seed), unsigned(seed >> 32)));
-            const unsigned v = (c & 3) == 0 ? r.x : (c & 3) == 1 ? r.y : (c & 3) == 2 ? r.z : r.w;
-            keep = (float(v >> 8) * (1.0f / 16777216.0f) >= p) ? 1.f : 0.f;
-        }
+        const float hv = mlp_hidden<128>(prm + FC1_W, prm + FC1_B, sg, c);
+        const float keep = mask_in ? mask_in[(long long)b * HID + c] : dropout_keep(c, b, seed, offset, p);
         const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
         hr[(long long)b * HID + c] = hv;
         mask[(long long)b * HID + c] = keep;
@@ -299,99 +288,7 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
         shd[c] = hv * (keep * scale);
     }
     __syncthreads();
-    if (c == 0) {
-        float z0 = prm[FC2_B], z1 = prm[FC2_B + 1];
-        for (int j = 0; j < HID; ++j) {
-            z0 += prm[FC2_W + j] * shd[j];
-            z1 += prm[FC2_W + HID + j] * shd[j];
-        }
-        logits[2 * b] = z0;
-        logits[2 * b + 1] = z1;
-        const long long y = targets[b];
-        if (y == 0 || y == 1) {
-            const float mx = fmaxf(z0, z1);
-            const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-            const float wt = class_w ? class_w[y] : 1.f;
-            wnll[2 * b] = wt * (lse - (y ? z1 : z0));
-            wnll[2 * b + 1] = wt;
-        } else {                                // a target outside [0, 2): the loss is NaN (torch raises instead)
-            wnll[2 * b] = __builtin_nanf("");
-            wnll[2 * b + 1] = __builtin_nanf("");
-        }
-    }
-}
-
-// one block per clip: the batch's loss and CE weight (every block sums them in the same order; block 0 writes the
-// loss), dlogits, the hidden gradient dh (ReLU and dropout folded in) and the gradient of the global mean / HW
-__global__ __launch_bounds__(128) void head_bwd_kernel(int B, int HW, const float* __restrict__ logits,
-                                                       const long long* __restrict__ targets, const float* __restrict__ wnll,
-                                                       const float* __restrict__ hr, const float* __restrict__ mask, float p,
-                                                       const float* __restrict__ prm, const float* __restrict__ st0,
-                                                       float* __restrict__ loss, float* __restrict__ dl,
-                                                       float* __restrict__ dh, float* __restrict__ dgap) {
-    __shared__ float lds[8], sdh[HID];
-    const int t = threadIdx.x, b = blockIdx.x;
-    float v[2] = {0.f, 0.f};
-    for (int i = t; i < B; i += 128) { v[0] += wnll[2 * i]; v[1] += wnll[2 * i + 1]; }
-    v[0] = wave_sum(v[0]);
-    v[1] = wave_sum(v[1]);
-    if ((t & 63) == 0) { lds[(t >> 6) * 2] = v[0]; lds[(t >> 6) * 2 + 1] = v[1]; }
-    __syncthreads();
-    const float tot = lds[0] + lds[2], totw = lds[1] + lds[3];
-    if (b == 0 && t == 0) {
-        // a non-finite input reaches conv1's batch statistics of every channel; ReLU and max-pool (v_max_f32) would
-        // otherwise drop the NaN before the loss
-        const bool finite = isfinite(st0[0]) && isfinite(st0[16]);
-        loss[0] = finite ? tot / totw : __builtin_nanf("");
-    }
-    const float z0 = logits[2 * b], z1 = logits[2 * b + 1];
-    const float mx = fmaxf(z0, z1);
-    const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
-    const long long y = targets[b];
-    const float k = wnll[2 * b + 1] / totw;
-    const float d0 = k * (e0 * inv - (y == 0 ? 1.f : 0.f)), d1 = k * (e1 * inv - (y == 1 ? 1.f : 0.f));
-    if (t == 0) { dl[2 * b] = d0; dl[2 * b + 1] = d1; }
-    const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
-    if (t < HID) {
-        const float dhd = d0 * prm[FC2_W + t] + d1 * prm[FC2_W + HID + t];
-        const float g = hr[(long long)b * HID + t] > 0.f ? dhd * (mask[(long long)b * HID + t] * scale) : 0.f;
-        sdh[t] = g;
-        dh[(long long)b * HID + t] = g;
-    }
-    __syncthreads();
-    float s = 0.f;
-    for (int j = 0; j < HID; ++j) s += prm[FC1_W + j * 128 + t] * sdh[j];
-    dgap[(long long)b * 128 + t] = s / float(HW);
-}
-
-// the classifier's gradients (fc1 weight [64][128], bias, fc2 weight [2][64], bias: contiguous in the parameters):
-// 64 outputs per block, the batch split in 4 fixed quarters, added ((q0 + q1) + (q2 + q3))
-__global__ __launch_bounds__(NT) void fc_grad_kernel(int B, const float* __restrict__ gap, const float* __restrict__ hr,
-                                                     const float* __restrict__ mask, float p, const float* __restrict__ dl,
-                                                     const float* __restrict__ dh, float* __restrict__ grads) {
-    __shared__ float red[4][64];
-    const int o = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-    constexpr int NOUT = 128 * HID + HID + 2 * HID + 2;
-    const int b0 = int((long long)B * q / 4), b1 = int((long long)B * (q + 1) / 4);
-    const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
-    float s = 0.f;
-    if (o < 128 * HID) {
-        const int j = o >> 7, c = o & 127;
-        for (int b = b0; b < b1; ++b) s += dh[(long long)b * HID + j] * gap[(long long)b * 128 + c];
-    } else if (o < 128 * HID + HID) {
-        const int j = o - 128 * HID;
-        for (int b = b0; b < b1; ++b) s += dh[(long long)b * HID + j];
-    } else if (o < 128 * HID + 3 * HID) {
-        const int k = (o - 128 * HID - HID) / HID, j = (o - 128 * HID - HID) % HID;
-        for (int b = b0; b < b1; ++b)
-            s += dl[2 * b + k] * (hr[(long long)b * HID + j] * (mask[(long long)b * HID + j] * scale));
-    } else if (o < NOUT) {
-        const int k = o - 128 * HID - 3 * HID;
-        for (int b = b0; b < b1; ++b) s += dl[2 * b + k];
-    }
-    red[q][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (q == 0 && o < NOUT) grads[FC1_W + o] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (c == 0) mlp_out<HID>(prm + FC2_W, prm + FC2_B, shd, b, targets, class_w, logits, wnll);
 }
 
 // ------------------------------------------------------------------------------------------ BN backward
@@ -698,8 +595,6 @@ __global__ __launch_bounds__(NT) void slab_reduce_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ workspace
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
 struct Shapes {
     int h[4], w[4];          // BN k's image: conv1's (the input's), then every pool halves it (floor)
     int S;                   // pixel ranges of every partial sum
@@ -722,12 +617,8 @@ struct Ws {
 
 Ws carve(char* base, int B, const Shapes& s) {
     Ws w{};
-    size_t off = 0;
-    auto f = [&](long long n) {
-        float* q = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += align256(size_t(n) * 4);
-        return q;
-    };
+    Carver ws{base};
+    auto f = [&](long long n) { return ws.floats(n); };
     for (int k = 1; k < 4; ++k) {
         const long long px = (long long)B * s.h[k] * s.w[k];
         w.p[k] = f(px * NC[k - 1]);
@@ -747,11 +638,11 @@ Ws carve(char* base, int B, const Shapes& s) {
     w.dgap = f((long long)B * 128);
     w.wnll = f(2LL * B);
     w.dl = f(2LL * B);
-    w.total = off;
+    w.total = ws.off;
     return w;
 }
 
-int grid_for(long long n) { return int(std::min<long long>((n + NT - 1) / NT, 8192)); }
+constexpr int GRID_CAP = 8192;    // blocks of a grid-stride launch
 unsigned blocks_for(long long n) { return unsigned((n + NT - 1) / NT); }
 
 // the shapes torch's train-mode forward accepts: three 2x2 pools need H, W >= 8 and the last BN more than one value per
@@ -761,8 +652,6 @@ bool trainable(int B, int H, int W) {
     if ((long long)B * (H / 8) * (W / 8) <= 1) return false;
     return (long long)B * H * W <= (1LL << 27);
 }
-
-bool finite_f(float v) { return std::isfinite(v); }
 
 }  // namespace
 }  // namespace cough
@@ -782,8 +671,6 @@ extern "C" int cough_train_small_forward_backward(const float* d_x, int n_clips,
                                                   float* d_mask_out, void* d_workspace, size_t workspace_bytes,
                                                   void* stream) {
     using namespace cough;
-    COUGH_REQUIRE(d_x && d_targets && d_params && d_grads && d_running && d_num_batches && d_loss && d_logits && d_workspace,
-                  COUGH_EINVAL, "cough_train_small_forward_backward: NULL argument");
     COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL,
                   "cough_train_small_forward_backward: bad shape (%d, %d, %d)", n_clips, height, width);
     COUGH_REQUIRE(height >= 8 && width >= 8, COUGH_EINVAL,
@@ -794,15 +681,14 @@ extern "C" int cough_train_small_forward_backward(const float* d_x, int n_clips,
                   "need more)");
     COUGH_REQUIRE(trainable(n_clips, height, width), COUGH_EINVAL,
                   "cough_train_small_forward_backward: batch of %d images of %dx%d too large", n_clips, height, width);
-    COUGH_REQUIRE(p >= 0.f && p <= 1.f, COUGH_EINVAL, "cough_train_small_forward_backward: dropout p must be in [0, 1]");
-    COUGH_REQUIRE(finite_f(momentum) && momentum >= 0.f && momentum <= 1.f && finite_f(eps) && eps >= 0.f, COUGH_EINVAL,
-                  "cough_train_small_forward_backward: bad BatchNorm momentum / eps");
-    COUGH_REQUIRE((reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL,
-                  "cough_train_small_forward_backward: workspace must be 256-byte aligned");
     const int B = n_clips, H = height, W = width;
     const Shapes s = make_shapes(B, H, W);
     const Ws w = carve(static_cast<char*>(d_workspace), B, s);
-    COUGH_REQUIRE(workspace_bytes >= w.total, COUGH_EWORKSPACE, "cough_train_small_forward_backward: workspace too small");
+    if (const int rc = check_step_args(__func__, {d_x, d_targets, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
+                                                  d_workspace},
+                                       {p}, momentum, eps, d_workspace, workspace_bytes, w.total);
+        rc != COUGH_OK)
+        return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float* prm = d_params;
@@ -816,8 +702,8 @@ extern "C" int cough_train_small_forward_backward(const float* d_x, int n_clips,
     // ---- forward
     hipLaunchKernelGGL(stats0_kernel, dim3(S, 4), dim3(NT), 0, st, d_x, B, H, W, prm, S, w.part);
     finalize(0);
-    hipLaunchKernelGGL(conv1_pool_kernel, dim3(grid_for((long long)B * 4 * s.h[1] * s.w[1])), dim3(NT), 0, st, d_x, B, H,
-                       W, s.h[1], s.w[1], prm, w.stat[0], w.p[1]);
+    hipLaunchKernelGGL(conv1_pool_kernel, dim3(grid_for((long long)B * 4 * s.h[1] * s.w[1], GRID_CAP)), dim3(NT), 0, st, d_x,
+                       B, H, W, s.h[1], s.w[1], prm, w.stat[0], w.p[1]);
     for (int k = 1; k < 4; ++k) {
         const int h = s.h[k], wd = s.w[k];
         const dim3 g(blocks_for(px(k)));
@@ -828,18 +714,18 @@ extern "C" int cough_train_small_forward_backward(const float* d_x, int n_clips,
         hipLaunchKernelGGL(stats_kernel, dim3(S, NC[k]), dim3(NT), 0, st, w.z[k], B, h * wd, NC[k], S, w.part);
         finalize(k);
         if (k < 3)
-            hipLaunchKernelGGL(bn_relu_pool_kernel, dim3(grid_for((long long)B * NC[k] * (h / 2) * (wd / 2))), dim3(NT), 0, st,
-                               w.z[k], B, NC[k], h, wd, w.stat[k], prm + BN_G[k], prm + BN_B[k], w.p[k + 1]);
+            hipLaunchKernelGGL(bn_relu_pool_kernel, dim3(grid_for((long long)B * NC[k] * (h / 2) * (wd / 2), GRID_CAP)), dim3(NT),
+                               0, st, w.z[k], B, NC[k], h, wd, w.stat[k], prm + BN_G[k], prm + BN_B[k], w.p[k + 1]);
     }
     const int HW3 = s.h[3] * s.w[3];
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(128), 0, st, w.z[3], HW3, w.stat[3], prm, d_dropout_mask, seed, offset,
-                       p, d_targets, d_class_weights, d_logits, w.gap, w.hr, w.mask, d_mask_out, w.wnll);
+    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3(B), dim3(128), 0, st, w.z[3], HW3, w.stat[3], prm, d_dropout_mask, seed,
+                       offset, p, d_targets, d_class_weights, d_logits, w.gap, w.hr, w.mask, d_mask_out, w.wnll);
 
     // ---- backward
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(128), 0, st, B, HW3, d_logits, d_targets, w.wnll, w.hr, w.mask, p, prm,
-                       w.stat[0], d_loss, w.dl, w.dh, w.dgap);
-    hipLaunchKernelGGL(fc_grad_kernel, dim3((128 * HID + 3 * HID + 2 + 63) / 64), dim3(NT), 0, st, B, w.gap, w.hr, w.mask, p,
-                       w.dl, w.dh, d_grads);
+    hipLaunchKernelGGL((mlp_head_bwd_kernel<128, HID, HID, 0>), dim3(B), dim3(128), 0, st, B, HW3, d_logits, d_targets, w.wnll,
+                       w.hr, w.mask, p, prm + FC1_W, prm + FC2_W, w.stat[0], NC[0], d_loss, w.dl, w.dh, w.dgap);
+    hipLaunchKernelGGL((mlp_fc_grad_kernel<128, HID, HID, 0>), dim3((128 * HID + 3 * HID + 2 + 63) / 64), dim3(NT), 0, st, B,
+                       w.gap, w.hr, w.mask, p, w.dl, w.dh, d_grads + FC1_W);
     for (int k = 3; k >= 1; --k) {
         const int h = s.h[k], wd = s.w[k], C = NC[k];
         BwdSrc src{w.z[k], nullptr, k == 3 ? w.dgap : w.dp[k + 1], B, C, h, wd};

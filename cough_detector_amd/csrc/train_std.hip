@@ -35,7 +35,6 @@
 
 #include "common.h"
 #include "nn_common.h"
-#include "philox.h"
 #include "train_common.h"
 
 namespace cough {
@@ -62,14 +61,6 @@ static_assert(FC0_W == BN_B[3] + 256 && FC0_B == FC0_W + HID * 256 && FC3_W == F
               N_PARAMS == FC3_B + 2, "head layout");
 static_assert(RUN[3] + 2 * 256 == N_RUNNING && MOFF[4] + HID == MASK_W, "running statistics / mask layout");
 
-
-
-// MFMA 32x32x2 f32 operand / result layout: lane (r, h) supplies A[row r][k h] and B[k h][col r]; accumulator register
-// reg of lane (r, h) is C[row (reg & 3) + 8 (reg >> 2) + 4 h][col r].
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-
-
 // ------------------------------------------------------------------------------------------ dropout mask
 // mask[b][u] = the keep of unit u of clip b (a caller mask, or a Philox draw against p_block / p_fc)
 __global__ __launch_bounds__(NT) void mask_kernel(int B, const float* __restrict__ mask_in, unsigned long long seed,
@@ -78,16 +69,7 @@ __global__ __launch_bounds__(NT) void mask_kernel(int B, const float* __restrict
     const long long e = (long long)blockIdx.x * NT + threadIdx.x;
     if (e >= (long long)B * MASK_W) return;
     const int b = int(e / MASK_W), u = int(e - (long long)b * MASK_W);
-    float keep;
-    if (mask_in) {
-        keep = mask_in[e];
-    } else {
-        const uint4 r = philox4x32_10(make_uint4(unsigned(u >> 2), unsigned(b), unsigned(offset), unsigned(offset >> 32)),
-                                      make_uint2(unsigned(seed), unsigned(seed >> 32)));
-        const unsigned v = (u & 3) == 0 ? r.x : (u & 3) == 1 ? r.y : (u & 3) == 2 ? r.z : r.w;
-        const float p = u < MOFF[NB] ? p_block : p_fc;
-        keep = (float(v >> 8) * (1.0f / 16777216.0f) >= p) ? 1.f : 0.f;
-    }
+    const float keep = mask_in ? mask_in[e] : dropout_keep(u, b, seed, offset, u < MOFF[NB] ? p_block : p_fc);
     mask[e] = keep;
     if (mask_out) mask_out[e] = keep;
 }
@@ -303,23 +285,6 @@ __global__ __launch_bounds__(64 * WM * WN) void wgrad3x3_kernel(const float* __r
     if (bias_blk && tid < BM) dst[(long long)(co0 + tid) * ld + 9 * Cin] = accb;
 }
 
-// sum the S slabs [Cout][9 Cin + 1] in index order; column t Cin + ci -> the OIHW weight gradient, column 9 Cin -> bias
-__global__ __launch_bounds__(NT) void wgrad_reduce_kernel(const float* __restrict__ slab, int S, int Cout, int Cin,
-                                                          float* __restrict__ gw, float* __restrict__ gb) {
-    const int ld = 9 * Cin + 1;
-    const int e = blockIdx.x * NT + threadIdx.x;
-    if (e >= Cout * ld) return;
-    const int co = e / ld, col = e - co * ld;
-    float s = 0.f;
-    for (int i = 0; i < S; ++i) s += slab[(long long)i * Cout * ld + e];
-    if (col == 9 * Cin) {
-        gb[co] = s;
-    } else {
-        const int t = col / Cin, ci = col - t * Cin;
-        gw[(co * Cin + ci) * 9 + t] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------ BatchNorm
 // BN k of block k, with what its backward needs: z [B h w][C] (pre-BN), stat [4][C] (mean, invstd, sum dy,
 // sum dy * xhat), the pool's argmax idx [B ph pw][C], the gradient of the block's output da ([B ph pw][C], or for the last
@@ -484,12 +449,12 @@ __global__ __launch_bounds__(NT) void wgrad0_kernel(BnSrc a, const float* __rest
 // ------------------------------------------------------------------------------------------ head
 // one block (256 threads) per clip: mean of the last block's output -> Linear(256, 128) -> ReLU -> dropout ->
 // Linear(128, 2) -> weighted CE terms
-__global__ __launch_bounds__(NT) void head_fwd_kernel(const float* __restrict__ a3, int HW, const float* __restrict__ prm,
-                                                      const float* __restrict__ mask, float p_fc,
-                                                      const long long* __restrict__ targets,
-                                                      const float* __restrict__ class_w, float* __restrict__ logits,
-                                                      float* __restrict__ gap, float* __restrict__ hr,
-                                                      float* __restrict__ wnll) {
+__global__ __launch_bounds__(NT) void mlp_head_fwd_kernel(const float* __restrict__ a3, int HW, const float* __restrict__ prm,
+                                                          const float* __restrict__ mask, float p_fc,
+                                                          const long long* __restrict__ targets,
+                                                          const float* __restrict__ class_w, float* __restrict__ logits,
+                                                          float* __restrict__ gap, float* __restrict__ hr,
+                                                          float* __restrict__ wnll) {
     __shared__ float sg[256], shd[HID];
     const int c = threadIdx.x, b = blockIdx.x;
     const float* src = a3 + (long long)b * HW * 256 + c;
@@ -500,114 +465,16 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(const float* __restrict__ 
     gap[(long long)b * 256 + c] = gv;
     __syncthreads();
     if (c < HID) {
-        float hv = prm[FC0_B + c];
-        for (int k = 0; k < 256; ++k) hv += prm[FC0_W + c * 256 + k] * sg[k];
-        hv = fmaxf(hv, 0.f);
+        const float hv = mlp_hidden<256>(prm + FC0_W, prm + FC0_B, sg, c);
         const float scale = p_fc < 1.f ? 1.0f / (1.0f - p_fc) : 0.f;
         hr[(long long)b * HID + c] = hv;
         shd[c] = hv * (mask[(long long)b * MASK_W + MOFF[NB] + c] * scale);
     }
     __syncthreads();
-    if (c == 0) {
-        float z0 = prm[FC3_B], z1 = prm[FC3_B + 1];
-        for (int j = 0; j < HID; ++j) {
-            z0 += prm[FC3_W + j] * shd[j];
-            z1 += prm[FC3_W + HID + j] * shd[j];
-        }
-        logits[2 * b] = z0;
-        logits[2 * b + 1] = z1;
-        const long long y = targets[b];
-        if (y == 0 || y == 1) {
-            const float mx = fmaxf(z0, z1);
-            const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
-            const float wt = class_w ? class_w[y] : 1.f;
-            wnll[2 * b] = wt * (lse - (y ? z1 : z0));
-            wnll[2 * b + 1] = wt;
-        } else {                                // a target outside [0, 2): the loss is NaN (torch raises instead)
-            wnll[2 * b] = __builtin_nanf("");
-            wnll[2 * b + 1] = __builtin_nanf("");
-        }
-    }
-}
-
-// one block per clip: the batch's loss and CE weight (every block sums them in the same order; block 0 writes the
-// loss), dlogits, the hidden gradient dh (ReLU and dropout folded in) and dgap = the gradient of every pooled pixel of
-// the last block's output (the global mean's 1 / HW included)
-__global__ __launch_bounds__(NT) void head_bwd_kernel(int B, int HW, const float* __restrict__ logits,
-                                                      const long long* __restrict__ targets, const float* __restrict__ wnll,
-                                                      const float* __restrict__ hr, const float* __restrict__ mask,
-                                                      float p_fc, const float* __restrict__ prm,
-                                                      const float* __restrict__ st0, float* __restrict__ loss,
-                                                      float* __restrict__ dl, float* __restrict__ dh,
-                                                      float* __restrict__ dgap) {
-    __shared__ float lds[8], sdh[HID];
-    const int t = threadIdx.x, b = blockIdx.x;
-    float v0 = 0.f, v1 = 0.f;
-    for (int i = t; i < B; i += NT) { v0 += wnll[2 * i]; v1 += wnll[2 * i + 1]; }
-    v0 = wave_sum(v0);
-    v1 = wave_sum(v1);
-    if ((t & 63) == 0) { lds[(t >> 6) * 2] = v0; lds[(t >> 6) * 2 + 1] = v1; }
-    __syncthreads();
-    const float tot = (lds[0] + lds[2]) + (lds[4] + lds[6]), totw = (lds[1] + lds[3]) + (lds[5] + lds[7]);
-    if (b == 0 && t == 0) {
-        // a non-finite input reaches conv 0's batch statistics of every channel; ReLU and max-pool (v_max_f32) would
-        // otherwise drop the NaN before the loss
-        const bool finite = isfinite(st0[0]) && isfinite(st0[32]);
-        loss[0] = finite ? tot / totw : __builtin_nanf("");
-    }
-    const float z0 = logits[2 * b], z1 = logits[2 * b + 1];
-    const float mx = fmaxf(z0, z1);
-    const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
-    const long long y = targets[b];
-    const float k = wnll[2 * b + 1] / totw;
-    const float d0 = k * (e0 * inv - (y == 0 ? 1.f : 0.f)), d1 = k * (e1 * inv - (y == 1 ? 1.f : 0.f));
-    if (t == 0) { dl[2 * b] = d0; dl[2 * b + 1] = d1; }
-    const float scale = p_fc < 1.f ? 1.0f / (1.0f - p_fc) : 0.f;
-    if (t < HID) {
-        const float dhd = d0 * prm[FC3_W + t] + d1 * prm[FC3_W + HID + t];
-        const float g = hr[(long long)b * HID + t] > 0.f ? dhd * (mask[(long long)b * MASK_W + MOFF[NB] + t] * scale) : 0.f;
-        sdh[t] = g;
-        dh[(long long)b * HID + t] = g;
-    }
-    __syncthreads();
-    float s = 0.f;
-    for (int j = 0; j < HID; ++j) s += prm[FC0_W + j * 256 + t] * sdh[j];
-    dgap[(long long)b * 256 + t] = s / float(HW);
-}
-
-// the head's gradients (fc.0 weight [128][256], bias, fc.3 weight [2][128], bias: contiguous in the parameters):
-// 64 outputs per block, the batch split in 4 fixed quarters, added ((q0 + q1) + (q2 + q3))
-__global__ __launch_bounds__(NT) void fc_grad_kernel(int B, const float* __restrict__ gap, const float* __restrict__ hr,
-                                                     const float* __restrict__ mask, float p_fc, const float* __restrict__ dl,
-                                                     const float* __restrict__ dh, float* __restrict__ grads) {
-    __shared__ float red[4][64];
-    const int o = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-    constexpr int NOUT = 256 * HID + HID + 2 * HID + 2;
-    const int b0 = int((long long)B * q / 4), b1 = int((long long)B * (q + 1) / 4);
-    const float scale = p_fc < 1.f ? 1.0f / (1.0f - p_fc) : 0.f;
-    float s = 0.f;
-    if (o < 256 * HID) {
-        const int j = o >> 8, c = o & 255;
-        for (int b = b0; b < b1; ++b) s += dh[(long long)b * HID + j] * gap[(long long)b * 256 + c];
-    } else if (o < 256 * HID + HID) {
-        const int j = o - 256 * HID;
-        for (int b = b0; b < b1; ++b) s += dh[(long long)b * HID + j];
-    } else if (o < 256 * HID + 3 * HID) {
-        const int k = (o - 256 * HID - HID) / HID, j = (o - 256 * HID - HID) % HID;
-        for (int b = b0; b < b1; ++b)
-            s += dl[2 * b + k] * (hr[(long long)b * HID + j] * (mask[(long long)b * MASK_W + MOFF[NB] + j] * scale));
-    } else if (o < NOUT) {
-        const int k = o - 256 * HID - 3 * HID;
-        for (int b = b0; b < b1; ++b) s += dl[2 * b + k];
-    }
-    red[q][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (q == 0 && o < NOUT) grads[FC0_W + o] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (c == 0) mlp_out<HID>(prm + FC3_W, prm + FC3_B, shd, b, targets, class_w, logits, wnll);
 }
 
 // ------------------------------------------------------------------------------------------ workspace
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
 // wgrad tiles: block 1 64 x 32 (2 waves), blocks 2, 3 64 x 64 (4 waves)
 constexpr int WG_BM = 64;
 constexpr int wg_bn(int k) { return k == 1 ? 32 : 64; }
@@ -644,13 +511,8 @@ struct Ws {
 
 Ws carve(char* base, int B, const Shapes& s) {
     Ws w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    auto f = [&](long long n) { return reinterpret_cast<float*>(take(size_t(n) * 4)); };
+    Carver ws{base};
+    auto f = [&](long long n) { return ws.floats(n); };
     w.wt = f(N_PARAMS);
     w.wd = f(N_PARAMS);
     long long slab_most = (long long)s.Sw[0] * 320;
@@ -658,7 +520,7 @@ Ws carve(char* base, int B, const Shapes& s) {
         const long long pooled = (long long)B * s.h[k + 1] * s.w[k + 1] * CH[k];
         w.z[k] = f(s.M[k] * CH[k]);
         w.a[k] = f(pooled);
-        w.idx[k] = reinterpret_cast<unsigned char*>(take(size_t(pooled)));
+        w.idx[k] = reinterpret_cast<unsigned char*>(ws.take(size_t(pooled)));
         if (k < NB - 1) w.da[k] = f(pooled);
         if (k > 0) {
             w.dz[k] = f(s.M[k] * CH[k]);
@@ -675,11 +537,11 @@ Ws carve(char* base, int B, const Shapes& s) {
     w.dh = f((long long)B * HID);
     w.wnll = f(2LL * B);
     w.dl = f(2LL * B);
-    w.total = off;
+    w.total = ws.off;
     return w;
 }
 
-int grid_for(long long n) { return int(std::min<long long>((n + NT - 1) / NT, 8192)); }
+constexpr int GRID_CAP = 8192;    // blocks of a grid-stride launch
 
 // the shapes torch's train-mode forward accepts: four 2x2 pools need H, W >= 16 (the last BN then sees B (H/8) (W/8) >= 4
 // values per channel); the pixel count of the largest image must fit the 32-bit pixel arithmetic of the kernels
@@ -687,8 +549,6 @@ bool trainable(int B, int H, int W) {
     if (B < 1 || H < 16 || W < 16) return false;
     return (long long)B * H * W <= (1LL << 27);
 }
-
-bool finite_f(float v) { return std::isfinite(v); }
 
 }  // namespace
 }  // namespace cough
@@ -708,8 +568,6 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
                                                 float* d_logits, float* d_mask_out, void* d_workspace,
                                                 size_t workspace_bytes, void* stream) {
     using namespace cough;
-    COUGH_REQUIRE(d_x && d_targets && d_params && d_grads && d_running && d_num_batches && d_loss && d_logits && d_workspace,
-                  COUGH_EINVAL, "cough_train_std_forward_backward: NULL argument");
     COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL,
                   "cough_train_std_forward_backward: bad shape (%d, %d, %d)", n_clips, height, width);
     COUGH_REQUIRE(height >= 16 && width >= 16, COUGH_EINVAL,
@@ -717,16 +575,14 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
                   width);
     COUGH_REQUIRE(trainable(n_clips, height, width), COUGH_EINVAL,
                   "cough_train_std_forward_backward: batch of %d images of %dx%d too large", n_clips, height, width);
-    COUGH_REQUIRE(p_block >= 0.f && p_block <= 1.f && p_fc >= 0.f && p_fc <= 1.f, COUGH_EINVAL,
-                  "cough_train_std_forward_backward: dropout p must be in [0, 1]");
-    COUGH_REQUIRE(finite_f(momentum) && momentum >= 0.f && momentum <= 1.f && finite_f(eps) && eps >= 0.f, COUGH_EINVAL,
-                  "cough_train_std_forward_backward: bad BatchNorm momentum / eps");
-    COUGH_REQUIRE((reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL,
-                  "cough_train_std_forward_backward: workspace must be 256-byte aligned");
     const int B = n_clips, H = height, W = width;
     const Shapes s = make_shapes(B, H, W);
     const Ws w = carve(static_cast<char*>(d_workspace), B, s);
-    COUGH_REQUIRE(workspace_bytes >= w.total, COUGH_EWORKSPACE, "cough_train_std_forward_backward: workspace too small");
+    if (const int rc = check_step_args(__func__, {d_x, d_targets, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
+                                                  d_workspace},
+                                       {p_block, p_fc}, momentum, eps, d_workspace, workspace_bytes, w.total);
+        rc != COUGH_OK)
+        return rc;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float* prm = d_params;
@@ -747,24 +603,26 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
     hipLaunchKernelGGL(mask_kernel, dim3(unsigned((B * MASK_W + NT - 1) / NT)), dim3(NT), 0, st, B, d_dropout_mask, seed,
                        offset, p_block, p_fc, w.mask, d_mask_out);
     hipLaunchKernelGGL(prep_weights_kernel, dim3(64, 3), dim3(NT), 0, st, prm, w.wt, w.wd);
-    hipLaunchKernelGGL(conv0_fwd_kernel, dim3(grid_for(s.M[0] * 32)), dim3(NT), 0, st, d_x, B, H, W, prm, w.z[0]);
+    hipLaunchKernelGGL(conv0_fwd_kernel, dim3(grid_for(s.M[0] * 32, GRID_CAP)), dim3(NT), 0, st, d_x, B, H, W, prm, w.z[0]);
     for (int k = 0; k < NB; ++k) {
         if (k > 0) conv(w.a[k - 1], CI[k], k, w.wt + CONV_W[k], prm + CONV_B[k], CH[k], w.z[k]);
         hipLaunchKernelGGL(stats_part_kernel, dim3(S), dim3(NT), 0, st, w.z[k], s.M[k], CH[k], S, w.part);
         hipLaunchKernelGGL(stats_finalize_kernel, dim3(CH[k]), dim3(NT), 0, st, w.part, S, CH[k], eps, momentum,
                            d_running + RUN[k], d_running + RUN[k] + CH[k], d_num_batches + k, w.stat[k]);
         const long long pooled = (long long)B * s.h[k + 1] * s.w[k + 1] * CH[k];
-        hipLaunchKernelGGL(bn_pool_drop_kernel, dim3(grid_for(pooled)), dim3(NT), 0, st, src_of(k), pooled, w.a[k], w.idx[k]);
+        hipLaunchKernelGGL(bn_pool_drop_kernel, dim3(grid_for(pooled, GRID_CAP)), dim3(NT), 0, st, src_of(k), pooled, w.a[k],
+                           w.idx[k]);
     }
     const int HW4 = s.h[NB] * s.w[NB];
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(NT), 0, st, w.a[NB - 1], HW4, prm, w.mask, p_fc, d_targets,
+    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3(B), dim3(NT), 0, st, w.a[NB - 1], HW4, prm, w.mask, p_fc, d_targets,
                        d_class_weights, d_logits, w.gap, w.hr, w.wnll);
 
     // ---- backward
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(B), dim3(NT), 0, st, B, HW4, d_logits, d_targets, w.wnll, w.hr, w.mask, p_fc,
-                       prm, w.stat[0], d_loss, w.dl, w.dh, w.dgap);
-    hipLaunchKernelGGL(fc_grad_kernel, dim3((256 * HID + 3 * HID + 2 + 63) / 64), dim3(NT), 0, st, B, w.gap, w.hr, w.mask,
-                       p_fc, w.dl, w.dh, d_grads);
+    hipLaunchKernelGGL((mlp_head_bwd_kernel<256, HID, MASK_W, MOFF[NB]>), dim3(B), dim3(NT), 0, st, B, HW4, d_logits,
+                       d_targets, w.wnll, w.hr, w.mask, p_fc, prm + FC0_W, prm + FC3_W, w.stat[0], CH[0], d_loss, w.dl, w.dh,
+                       w.dgap);
+    hipLaunchKernelGGL((mlp_fc_grad_kernel<256, HID, MASK_W, MOFF[NB]>), dim3((256 * HID + 3 * HID + 2 + 63) / 64), dim3(NT),
+                       0, st, B, w.gap, w.hr, w.mask, p_fc, w.dl, w.dh, d_grads + FC0_W);
     for (int k = NB - 1; k >= 0; --k) {
         const BnSrc a = src_of(k);
         const long long MP = (long long)B * s.h[k + 1] * s.w[k + 1];
@@ -774,7 +632,7 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
         const float inv_n = float(1.0 / double(s.M[k]));
         const int Sw = s.Sw[k];
         if (k > 0) {
-            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(s.M[k] * CH[k])), dim3(NT), 0, st, a, s.M[k] * CH[k],
+            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(s.M[k] * CH[k], GRID_CAP)), dim3(NT), 0, st, a, s.M[k] * CH[k],
                                inv_n, w.dz[k]);
             const dim3 g(unsigned(Sw), unsigned(CH[k] / WG_BM), unsigned(9 * (CI[k] / wg_bn(k))));
             if (k == 1)
@@ -787,9 +645,9 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
         } else {
             hipLaunchKernelGGL(wgrad0_kernel, dim3(Sw), dim3(NT), 0, st, a, d_x, B, H, W, inv_n, Sw, w.slab);
         }
-        const int nout = CH[k] * (9 * CI[k] + 1);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((nout + NT - 1) / NT), dim3(NT), 0, st, w.slab, Sw, CH[k], CI[k],
-                           d_grads + CONV_W[k], d_grads + CONV_B[k]);
+        const int kcols = 9 * CI[k], nout = CH[k] * (kcols + 1);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((nout + NT - 1) / NT), dim3(NT), 0, st, w.slab, Sw, CH[k], kcols + 1,
+                           kcols, CI[k], 9, d_grads + CONV_W[k], d_grads + CONV_B[k]);
     }
     COUGH_HIP_CHECK(hipGetLastError());
     return COUGH_OK;
