@@ -1,4 +1,5 @@
-"""ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``).
+"""ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``) and of its companion
+``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -54,6 +55,11 @@ SYMBOLS = (
     "cough_train_small_workspace_bytes", "cough_train_small_forward_backward",
     "cough_train_std_workspace_bytes", "cough_train_std_forward_backward",
 )
+
+# every symbol include/cough_amd_loop.h declares (the companion library of the epoch loop; cough_amd.h stays at ABI v5)
+LOOP_LIB_PATH = os.environ.get("COUGH_AMD_LOOP_LIB") or os.path.join(HERE, "libcough_amd_loop.so")
+LOOP_SYMBOLS = ("cough_loop_abi_version", "cough_loop_last_error", "cough_epoch_meter_update")
+EPOCH_METER_BYTES = 64   # COUGH_EPOCH_METER_BYTES
 
 
 MAX_CONTRAST_BANDS = 16
@@ -198,15 +204,50 @@ def load() -> C.CDLL:
     return _lib
 
 
+_loop_lib = None
+
+
+def load_loop() -> C.CDLL:
+    """Load (once) and type the companion library of the epoch loop; raise loudly if it is not built."""
+    global _loop_lib
+    if _loop_lib is not None:
+        return _loop_lib
+    with _lock:
+        if _loop_lib is not None:
+            return _loop_lib
+        if not os.path.exists(LOOP_LIB_PATH):
+            raise RuntimeError(
+                f"{LOOP_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(LOOP_LIB_PATH)
+        vp, i = C.c_void_p, C.c_int
+        lib.cough_loop_abi_version.restype = i
+        lib.cough_loop_last_error.restype = C.c_char_p
+        lib.cough_epoch_meter_update.argtypes = [vp, vp, i, vp, vp, vp, vp, vp]
+        if lib.cough_loop_abi_version() != 1:
+            raise RuntimeError("libcough_amd_loop.so ABI version mismatch; rebuild it")
+        _loop_lib = lib
+    return _loop_lib
+
+
+def _raise(status: int, what: str, msg: str) -> None:
+    if status in (EINVAL, EUNSUPPORTED):
+        raise ValueError(f"{what}: {msg}")
+    raise RuntimeError(f"{what}: {msg} (status {status})")
+
+
+def check_loop(status: int, what: str) -> None:
+    """``check`` for a call into the companion library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_loop().cough_loop_last_error().decode("utf-8", "replace"))
+
+
 def check(status: int, what: str) -> None:
     """Map a C status to the reference's exception convention
     (ValueError for argument/config errors, as src/model.py:313-314; RuntimeError otherwise)."""
     if status == OK:
         return
-    msg = load().cough_amd_last_error().decode("utf-8", "replace")
-    if status in (EINVAL, EUNSUPPORTED):
-        raise ValueError(f"{what}: {msg}")
-    raise RuntimeError(f"{what}: {msg} (status {status})")
+    _raise(status, what, load().cough_amd_last_error().decode("utf-8", "replace"))
 
 
 def fptr(t):
