@@ -590,12 +590,14 @@ __global__ __launch_bounds__(NORM_THREADS) void grad_norm_kernel(const float* __
 }
 
 // clip_grad_norm_ (coef = max_norm / (norm + 1e-6) clamped at 1, always applied; the clipped gradient is written back),
-// then torch.optim.AdamW's single-tensor update order
+// then torch.optim.AdamW's single-tensor update order.  A NaN norm gives a NaN coefficient, as torch.clamp keeps it
+// (fminf would drop the NaN and clip nothing).
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ prm, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, long long n, const float* __restrict__ norm,
                                                     float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                                                     float step_size, float bc2_sqrt) {
-    const float coef = fminf(max_norm / (norm[0] + 1e-6f), 1.0f);
+    const float ratio = max_norm / (norm[0] + 1e-6f);
+    const float coef = ratio > 1.0f ? 1.0f : ratio;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float gi = g[i] * coef;
         g[i] = gi;

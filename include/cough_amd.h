@@ -377,7 +377,14 @@ int cough_mix_rows(const float* d_x1, const float* d_x2, const int* d_index2, fl
  * gradients by min(max_norm / (norm + 1e-6), 1) (written back, as clip_grad_norm_ leaves them) and applies
  * torch.optim.AdamW's update: p *= 1 - lr * wd; m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g^2;
  * p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps), bc1 = 1 - beta1^step, bc2 = 1 - beta2^step computed by the caller in
- * double.  The host never waits for the norm.  Every argument is checked before the first launch of either call. */
+ * double.  The kernel forms 1 - beta from the float betas it receives, so only bias corrections formed from those same
+ * float-rounded betas make the step a self-consistent AdamW (HipAdamW.step does so).
+ * Non-finite gradients behave as torch's float32 clip_grad_norm_ + AdamW do: a NaN gradient makes the norm and the clip
+ * coefficient NaN, and with them EVERY gradient, moment and parameter; an infinite gradient, or finite ones whose
+ * squares overflow float, make the norm +inf and the coefficient 0, so every finite gradient is written back as 0 (the
+ * moments only decay, the parameters move by the decayed first moment) and NaN appears only at the infinite elements
+ * (inf * 0).  Nothing is skipped and no error is returned.
+ * The host never waits for the norm.  Every argument is checked before the first launch of either call. */
 #define COUGH_TRAIN_NUM_PARAMS 290370
 #define COUGH_TRAIN_NUM_RUNNING 1216
 size_t cough_train_workspace_bytes(int n_clips, int height, int width);

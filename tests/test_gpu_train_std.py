@@ -22,7 +22,7 @@ import cough_detector_amd as cda
 from cough_detector_amd.training import StandardTrainer, train_epoch
 from test_train_std_host import golden_grad_rtol, load_std_golden, std_sd
 from train_std_ref import (BN_FED_BIASES, MASK_OFF, MASK_WIDTH, PARAM_NAMES, RefStep, assert_step_matches,
-                           golden_sample, resolve_kinks, running_names)
+                           golden_sample, resolve_kinks, running_names, step_on_the_kernels_side)
 
 pytestmark = pytest.mark.gpu
 CW = [1.0, 2.5]
@@ -133,8 +133,14 @@ def test_three_reference_steps_from_the_golden():
             ref = RefStep({k: v.cpu() for k, v in tr.model.state_dict().items()}, lr=lr,
                           weight_decay=float(g["weight_decay"]), class_weights=g["class_weights"])
             ref.opt.load_state_dict(copy.deepcopy(tr.optimizer.state_dict()))
-            rloss, rlogits, _, _ = ref.step(x, y, mask, pb, pf)
-        loss, logits = tr.step(x.cuda(), y.cuda(), dropout_mask=mask.cuda())
+        # tr.step in its two halves, so that the unclipped gradients can be read in between
+        loss, logits = tr.forward_backward(x.cuda(), y.cuda(), dropout_mask=mask.cuda())
+        if s > 0:
+            # ReLU inputs within rounding of 0 from the kernel's side, as in every single-step check (resolve_kinks)
+            grads = {n: p.grad.detach().cpu().double() for n, p in tr.model.named_parameters()}
+            rloss, rlogits, _, _, _ = step_on_the_kernels_side(ref, grads, x, y, mask, pb, pf)
+        tr.optimizer.step()
+        tr.model.invalidate()
         zscale = np.abs(g[f"logits{s}"]).max()
         if s == 0:
             # the golden head's logits reach the hundreds: the loss is a difference on that scale

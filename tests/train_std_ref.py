@@ -139,6 +139,21 @@ def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4):
     return rgrads, kept
 
 
+def step_on_the_kernels_side(ref, g, x, y, mask, p_block, p_fc):
+    """``ref.step`` for a check against a float32 step whose unclipped gradients are ``g``: the same train_epoch
+    iteration, with the ReLU derivatives that are ambiguous in float32 taken as that step took them (``resolve_kinks``,
+    the rule of every single-step check here).  Without it a ReLU input within rounding of 0 moves a whole block's
+    gradients by 1e-2 of their scale, and with them the clip norm and every moment.  Returns ``step``'s tuple and the
+    kept flips."""
+    loss, logits, rg = ref.grads(x, y, mask, p_block, p_fc)
+    rg, kept = resolve_kinks(g, ref, rg)
+    for n in PARAM_NAMES:
+        ref.P[n].grad = rg[n].clone()
+    norm = torch.nn.utils.clip_grad_norm_([ref.P[n] for n in PARAM_NAMES], max_norm=ref.max_norm)
+    ref.opt.step()
+    return loss, logits, rg, float(norm), kept
+
+
 def assert_step_matches(model, loss, logits, rloss, rlogits, rgrads, rsd, sd0, grad_rtol=1e-4) -> float:
     """train_small_ref.assert_step_matches for CoughDetector: loss within 1e-5 of max(|loss|, the logits' bound),
     logits within 1e-5 of max(1, their largest), every gradient within ``grad_rtol`` of that tensor's largest reference
