@@ -826,11 +826,32 @@ hipError_t x3_set_lds() {
     return e;
 }
 
+// single-bf16 LDS-image convolution: band of output rows per workgroup, 4 waves x MW tiles x 32 GEMM rows (x4 rows per
+// output when pooled); 0 if not even one row fits the tiles or the CNN_LDS_UNP * 256 staged pieces
+inline int lds_band(const cough_cnn::Layer& l, const CnnShape& s, int in_w, size_t* lds_bytes) {
+    const int mw = l.cin == 64 ? 2 : 4, per_out = l.pool == 2 ? 4 : 1;
+    int band = (4 * mw * 32) / (per_out * s.w);
+    if (band > s.h) band = s.h;
+    const size_t lds = size_t((l.pool == 2 ? 2 : 1) * band + 2) * (in_w + 2) * l.cin * 2;
+    if (lds_bytes) *lds_bytes = lds;
+    return (band >= 1 && lds <= size_t(CNN_LDS_UNP) * 256 * 16) ? band : 0;
+}
+
 template <typename T>
 int cnn_forward_impl(const cough_cnn* m, const float* d_feat, int n, int H, int W, float* d_logits, float* d_probs,
                      int* d_preds, char* ws, hipStream_t st, int tap_layer, float* d_tap) {
     std::vector<CnnShape> shp;
     cnn_shapes(m, H, W, shp);
+    if (sizeof(T) == 2) {   // refuse an image the single-bf16 kernels cannot take before the first launch
+        int iw = W;
+        for (size_t i = 0; i < m->layers.size(); ++i) {
+            if (i > 0 && m->layers[i].d_wfrag && lds_band(m->layers[i], shp[i], iw, nullptr) < 1) {
+                set_error("cough_cnn_forward: image %dx%d too wide for the LDS-image convolution", i ? shp[i - 1].h : H, iw);
+                return COUGH_EUNSUPPORTED;
+            }
+            iw = shp[i].w;
+        }
+    }
     size_t buf = 0;
     for (const auto& s : shp) buf = std::max(buf, align256(size_t(n) * s.h * s.w * s.c * m->esize));
     T* ping[2] = {reinterpret_cast<T*>(ws), reinterpret_cast<T*>(ws + buf)};
@@ -858,13 +879,10 @@ int cnn_forward_impl(const cough_cnn* m, const float* d_feat, int n, int H, int 
                                    static_cast<const float*>(l.d_w), l.d_b, l.cout, dst);
         } else if (l.d_wfrag && sizeof(T) == 2) {
             if constexpr (sizeof(T) == 2) {
-                // band of output rows per workgroup: 4 waves x MW tiles x 32 GEMM rows (x4 rows per output when pooled)
-                const int mw = l.cin == 64 ? 2 : 4, per_out = l.pool == 2 ? 4 : 1;
-                int band = (4 * mw * 32) / (per_out * s.w);
-                if (band > s.h) band = s.h;
-                const int n_bands = (s.h + band - 1) / band;
-                const size_t lds = size_t((l.pool == 2 ? 2 : 1) * band + 2) * (cw + 2) * l.cin * 2;
-                if (band >= 1 && lds <= size_t(CNN_LDS_UNP) * 256 * 16) {
+                size_t lds = 0;
+                const int band = lds_band(l, s, cw, &lds);
+                if (band >= 1) {
+                    const int n_bands = (s.h + band - 1) / band;
                     CnnLdsArgs a{cur, l.d_wfrag, l.d_b, dst, ch, cw, s.h, s.w, band, n_bands};
                     const dim3 grid((unsigned)(n * n_bands));
 #define COUGH_LDS_LAUNCH(CIN, NT, MW)                                                                            \
@@ -876,7 +894,7 @@ int cnn_forward_impl(const cough_cnn* m, const float* d_feat, int n, int H, int 
                     else if (l.cin == 32) COUGH_LDS_LAUNCH(32, 2, 4);
                     else COUGH_LDS_LAUNCH(64, 4, 2);
 #undef COUGH_LDS_LAUNCH
-                } else {
+                } else {   // not reached: the check ahead of the first launch has refused this image
                     set_error("cough_cnn_forward: image %dx%d too wide for the LDS-image convolution", ch, cw);
                     return COUGH_EUNSUPPORTED;
                 }
