@@ -10,6 +10,7 @@ from .augmentation import AudioAugmentor, MixUp, SpecAugment, create_augmentatio
 from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, create_trainer, train_epoch
 from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, load_checkpoint, save_checkpoint,
                    train_epoch_async, validate)
+from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -17,4 +18,4 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "CoughPipeline", "AudioAugmentor", "MixUp", "SpecAugment", "create_augmentation_pipeline",
            "ResidualTrainer", "SmallTrainer", "StandardTrainer", "create_trainer", "HipAdamW", "train_epoch",
            "EpochMeter", "EarlyStopping", "train_epoch_async", "validate", "save_checkpoint", "load_checkpoint",
-           "class_weights_from_counts", "fit"]
+           "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders"]

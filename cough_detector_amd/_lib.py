@@ -1,5 +1,6 @@
 """ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``) and of its companion
-``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``).
+``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``) and
+``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -60,6 +61,13 @@ SYMBOLS = (
 LOOP_LIB_PATH = os.environ.get("COUGH_AMD_LOOP_LIB") or os.path.join(HERE, "libcough_amd_loop.so")
 LOOP_SYMBOLS = ("cough_loop_abi_version", "cough_loop_last_error", "cough_epoch_meter_update")
 EPOCH_METER_BYTES = 64   # COUGH_EPOCH_METER_BYTES
+
+# every symbol include/cough_amd_data.h declares (the companion library of the input pipeline)
+DATA_LIB_PATH = os.environ.get("COUGH_AMD_DATA_LIB") or os.path.join(HERE, "libcough_amd_data.so")
+DATA_SYMBOLS = ("cough_data_abi_version", "cough_data_last_error", "cough_gather_rows", "cough_prepare_rows",
+                "cough_mask_images")
+PREP_NORMALIZE = 1       # COUGH_PREP_NORMALIZE
+MAX_MASKS = 16           # COUGH_MAX_MASKS
 
 
 MAX_CONTRAST_BANDS = 16
@@ -230,6 +238,34 @@ def load_loop() -> C.CDLL:
     return _loop_lib
 
 
+_data_lib = None
+
+
+def load_data() -> C.CDLL:
+    """Load (once) and type the companion library of the input pipeline; raise loudly if it is not built."""
+    global _data_lib
+    if _data_lib is not None:
+        return _data_lib
+    with _lock:
+        if _data_lib is not None:
+            return _data_lib
+        if not os.path.exists(DATA_LIB_PATH):
+            raise RuntimeError(
+                f"{DATA_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(DATA_LIB_PATH)
+        vp, ll, i = C.c_void_p, C.c_longlong, C.c_int
+        lib.cough_data_abi_version.restype = i
+        lib.cough_data_last_error.restype = C.c_char_p
+        lib.cough_gather_rows.argtypes = [vp, vp, vp, i, vp, ll, i, vp]
+        lib.cough_prepare_rows.argtypes = [vp, vp, vp, i, vp, i, i, vp]
+        lib.cough_mask_images.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp]
+        if lib.cough_data_abi_version() != 1:
+            raise RuntimeError("libcough_amd_data.so ABI version mismatch; rebuild it")
+        _data_lib = lib
+    return _data_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -240,6 +276,12 @@ def check_loop(status: int, what: str) -> None:
     """``check`` for a call into the companion library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_loop().cough_loop_last_error().decode("utf-8", "replace"))
+
+
+def check_data(status: int, what: str) -> None:
+    """``check`` for a call into the input pipeline's library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_data().cough_data_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:

@@ -9,7 +9,8 @@
 * ``SpecAugment`` (:271-331): random draws on the host in the reference's order -- ``random.random()`` for the coin, then
   per mask two ``torch.rand(1)`` as torchaudio's ``mask_along_axis`` draws them -- so a seeded run masks the same rows /
   columns as the reference.  The masking itself is one pass of ``cough_mask_axes`` over the whole batch (all frequency and
-  time masks at once) instead of one ``masked_fill`` pass per mask.
+  time masks at once) instead of one ``masked_fill`` pass per mask.  ``mask_batch`` draws a coin and masks per image, as
+  a Dataset that calls SpecAugment per item does, and applies them in one pass of ``cough_mask_images``.
 * ``MixUp`` (:334-369) and ``create_augmentation_pipeline`` (:372-398); the mixing runs in ``cough_mix_rows``.
 
 Differences a caller can observe: results come back where the input lives, as float32.  ``pitch_shift`` draws its coin
@@ -31,6 +32,29 @@ import torch
 from . import _lib, _tables
 from ._native import cuda_device
 from .preprocessing import load_wave
+
+
+def mask_images(src: torch.Tensor, out: torch.Tensor, axis: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+                n_masks: int) -> None:
+    """One ``cough_mask_images`` launch over the (..., F, T) float32 GPU tensor ``src`` into ``out`` (which may be
+    ``src``): image b gets masks ``[b][0 .. n_masks)`` of the device int32 arrays ``axis`` / ``start`` / ``end``."""
+    dev = src.device
+    if not (src.is_contiguous() and out.is_contiguous() and src.dtype == out.dtype == torch.float32 and out.shape == src.shape
+            and out.device == dev and dev.type == "cuda" and src.dim() >= 2):
+        raise ValueError("mask_images: src and out must be contiguous float32 (..., F, T) tensors of one shape on the GPU")
+    h, w = src.shape[-2], src.shape[-1]
+    n_img = src.numel() // (h * w) if h * w else 0
+    arrays = [a if n_masks else None for a in (axis, start, end)]
+    for a in arrays:
+        if a is not None and not (a.device == dev and a.dtype == torch.int32 and a.is_contiguous()
+                                  and a.numel() == n_img * n_masks):
+            raise ValueError(f"mask_images: the mask arrays must be contiguous int32 [{n_img}][{n_masks}] on {dev}")
+    if n_img == 0:
+        return
+    ptr = lambda a: None if a is None else a.data_ptr()      # noqa: E731
+    _lib.check_data(_lib.load_data().cough_mask_images(src.data_ptr(), out.data_ptr(), n_img, h, w, n_masks, ptr(arrays[0]),
+                                                       ptr(arrays[1]), ptr(arrays[2]),
+                                                       torch.cuda.current_stream(dev).cuda_stream), "cough_mask_images")
 
 
 class SpecAugment:
@@ -78,6 +102,28 @@ class SpecAugment:
                                                    arr(0), arr(1), arr(2), torch.cuda.current_stream(dev).cuda_stream),
                        "cough_mask_axes")
         return out.to(spectrogram.device) if spectrogram.device.type == "cpu" else out
+
+    def mask_batch(self, features: torch.Tensor) -> torch.Tensor:
+        """(B, C, F, T) or (B, F, T) -> a new tensor of that shape where the input lives: item b gets a coin and masks of
+        its own, drawn item by item in batch order (``random.random()``, then ``draw_masks`` when it fired -- what a
+        Dataset that calls ``self(item)`` per item draws); the channels of an item share its masks.  One pass of
+        ``cough_mask_images`` over the batch."""
+        if features.dim() not in (3, 4):
+            raise ValueError(f"SpecAugment.mask_batch: expected (B, C, F, T) or (B, F, T), got {tuple(features.shape)}")
+        b, f, t = features.shape[0], features.shape[-2], features.shape[-1]
+        per_item = [self.draw_masks(f, t) if not (random.random() > self.p) else [] for _ in range(b)]
+        n = max((len(m) for m in per_item), default=0)
+        channels = features.shape[1] if features.dim() == 4 else 1
+        arr = np.zeros((3, b, channels, n), dtype=np.int32)
+        for i, masks in enumerate(per_item):
+            for k, m in enumerate(masks):
+                arr[:, i, :, k] = np.asarray(m, dtype=np.int32)[:, None]
+        dev = cuda_device()
+        src = features.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.empty_like(src)
+        d = torch.from_numpy(arr).to(dev)
+        mask_images(src, out, d[0].reshape(-1), d[1].reshape(-1), d[2].reshape(-1), n)
+        return out.to(features.device)
 
 
 # ---------------------------------------------------------------------------------------------- waveform augmentation

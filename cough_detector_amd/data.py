@@ -1,0 +1,346 @@
+"""The reference's dataset module (``/root/reference/src/dataset.py``) with the whole input pipeline on the MI355X.
+
+* ``DeviceClipBank``: what ``CoughDataset`` (:22-173) holds -- the clips of a ``non_cough`` / ``cough`` directory tree,
+  resampled and averaged to mono, with its ``class_counts`` and ``sample_weights`` -- packed into ONE device buffer.  A
+  cough corpus is thousands of short clips at 64 KB per second of audio: it fits in HBM many times over.
+* ``DeviceDataLoader``: what a ``DataLoader`` over that dataset yields, ``(features (B, 1, F, T), targets (B,))`` on the
+  device, a batch per five launches instead of a clip per ``__getitem__``: ``cough_gather_rows`` (ragged clips -> a
+  matrix), ``cough_augment_waveforms``, ``cough_prepare_rows`` (``normalize`` -> ``pad_or_trim``; the peak is that of the
+  whole augmented clip, before the trim, as in :158-160), the featuriser, ``cough_mask_images`` (SpecAugment with a
+  coin and masks per item, :169-171).  The three new kernels live in ``libcough_amd_data.so``
+  (``include/cough_amd_data.h``).
+* ``create_data_loaders`` (:368-418): the ``WeightedRandomSampler`` / ``drop_last=True`` training loader and the
+  sequential validation loader.
+
+The random draws are the reference's, in the order a ``num_workers=0`` loader makes them: the sampler's indices for the
+epoch, then item by item in batch order the augmentor's draws for that clip's length, its ``torch.randn`` when the
+gaussian step fired (``noise="host"``), SpecAugment's coin and, when it fired, its masks.  All of them are host draws;
+everything else is stream-ordered device work, so drawing batch k + 1 overlaps the kernels of batch k.
+
+Differences a caller can observe: WAVE files only (``load_audio``); ``noise="device"`` (the default) draws the gaussian
+noise with the seeded counter-based generator of ``cough_augment_waveforms`` instead of ``torch.randn``;
+``cache_features`` keeps the unmasked features of the whole bank in one device tensor and is refused when a waveform
+augmentation could run (the reference's ``cache_spectrograms`` would silently freeze the first epoch's augmentation).
+"""
+from __future__ import annotations
+
+import random
+import warnings
+from pathlib import Path
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch.utils.data import RandomSampler, WeightedRandomSampler
+
+from . import _lib
+from ._native import cuda_device
+from .augmentation import AudioAugmentor, SpecAugment, mask_images
+
+CLASSES = ["non_cough", "cough"]
+_AUDIO_EXTENSIONS = {".wav", ".mp3", ".flac", ".ogg", ".webm"}      # dataset.py:86
+
+
+def _stream(dev: torch.device) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _upload(dev: torch.device, i64: np.ndarray, i32: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One host-to-device copy of an int64 and an int32 array through pinned memory, without waiting for it: torch's
+    pinned allocator hands the staging block out again only once the copy has run."""
+    n64, n32 = int(i64.size), int(i32.size)
+    host = torch.empty(max(n64 * 8 + n32 * 4, 1), dtype=torch.uint8, pin_memory=True)
+    raw = host.numpy()
+    raw[:n64 * 8].view(np.int64)[:] = i64
+    raw[n64 * 8:n64 * 8 + n32 * 4].view(np.int32)[:] = i32
+    d = host.to(dev, non_blocking=True)
+    return d[:n64 * 8].view(torch.int64), d[n64 * 8:n64 * 8 + n32 * 4].view(torch.int32)
+
+
+class DeviceClipBank:
+    """Mono float32 clips of any lengths >= 1, packed end to end into one buffer ``data`` on ``device``; clip k is
+    ``data[offsets[k] : offsets[k] + lengths[k]]`` with label ``labels[k]`` (0 = non_cough, 1 = cough).  ``offsets``
+    (int64), ``lengths`` (int32) and ``labels`` (int64) are host tensors, ``offsets_dev`` / ``lengths_dev`` /
+    ``labels_dev`` their device copies."""
+
+    classes = CLASSES
+
+    def __init__(self, waveforms: Sequence, labels: Sequence[int], device=None):
+        clips = []
+        for k, w in enumerate(waveforms):
+            t = torch.as_tensor(w)
+            if not t.dtype.is_floating_point:
+                raise TypeError(f"DeviceClipBank: clip {k} is {t.dtype}; expected floating-point samples")
+            if t.dim() == 2 and t.shape[0] == 1:
+                t = t[0]
+            if t.dim() != 1 or t.numel() < 1:
+                raise ValueError(f"DeviceClipBank: clip {k} has shape {tuple(t.shape)}; expected (n,) or (1, n) mono "
+                                 "samples, n >= 1")
+            clips.append(t.detach().to("cpu", torch.float32))
+        labels = [int(v) for v in (labels.tolist() if isinstance(labels, torch.Tensor) else labels)]
+        if len(labels) != len(clips):
+            raise ValueError(f"DeviceClipBank: {len(clips)} clips but {len(labels)} labels")
+        if any(v not in (0, 1) for v in labels):
+            raise ValueError("DeviceClipBank: labels are 0 (non_cough) or 1 (cough)")
+        lengths = [int(c.numel()) for c in clips]
+        if lengths and max(lengths) > 2**31 - 1:
+            raise ValueError("DeviceClipBank: a clip is longer than 2^31 - 1 samples")
+        self.device = torch.device(device) if device is not None else cuda_device()
+        packed = torch.cat(clips) if clips else torch.zeros(0, dtype=torch.float32)
+        self._set(packed.to(self.device), lengths, labels)
+
+    def _set(self, data: torch.Tensor, lengths: List[int], labels: List[int]) -> None:
+        self.data = data
+        self.lengths = torch.tensor(lengths, dtype=torch.int32)
+        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)[:-1]]) if lengths else [],
+                                    dtype=torch.int64)
+        self.labels = torch.tensor(labels, dtype=torch.int64)
+        self.offsets_dev = self.offsets.to(self.device)
+        self.lengths_dev = self.lengths.to(self.device)
+        self.labels_dev = self.labels.to(self.device)
+
+    def __len__(self) -> int:
+        return int(self.labels.numel())
+
+    @property
+    def class_counts(self) -> Dict[int, int]:
+        """{0: clips labelled non_cough, 1: clips labelled cough} (dataset.py:102-107)."""
+        counts = {i: 0 for i in range(len(CLASSES))}
+        for v in self.labels.tolist():
+            counts[v] += 1
+        return counts
+
+    @property
+    def sample_weights(self) -> torch.Tensor:
+        """``total / (2 * class_counts[label])`` per clip (dataset.py:109-116): what ``WeightedRandomSampler`` takes."""
+        counts, total = self.class_counts, len(self)
+        return torch.tensor([total / (len(CLASSES) * counts[v]) for v in self.labels.tolist()])
+
+    def clip(self, k: int) -> torch.Tensor:
+        """Clip ``k`` as a (1, n) view of the device buffer."""
+        o, n = int(self.offsets[k]), int(self.lengths[k])
+        return self.data[o:o + n].unsqueeze(0)
+
+    def subset(self, indices: Sequence[int]) -> "DeviceClipBank":
+        """A bank of the clips ``indices`` in that order (a train / validation split), on the same device."""
+        idx = [int(i) for i in (indices.tolist() if isinstance(indices, torch.Tensor) else indices)]
+        n = len(self)
+        if any(i < -n or i >= n for i in idx):
+            raise IndexError(f"DeviceClipBank.subset: indices must lie in 0..{n - 1}")
+        out = object.__new__(DeviceClipBank)
+        out.device = self.device
+        parts = [self.clip(i)[0] for i in idx]
+        data = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=self.device)
+        out._set(data, [int(self.lengths[i]) for i in idx], [int(self.labels[i]) for i in idx])
+        return out
+
+    @classmethod
+    def from_directory(cls, data_dir: str, preprocessor, device=None) -> "DeviceClipBank":
+        """The clips ``CoughDataset`` collects (dataset.py:83-100): ``data_dir/non_cough`` then ``data_dir/cough``, the
+        files of each in directory order, read with ``preprocessor.load_audio``, ``resample`` and ``to_mono``.  WAVE
+        files only: files with one of the reference's other suffixes are skipped, with one warning naming the count."""
+        root = Path(data_dir)
+        waveforms, labels, skipped = [], [], 0
+        for label, class_name in enumerate(CLASSES):
+            class_dir = root / class_name
+            if not class_dir.exists():
+                warnings.warn(f"DeviceClipBank: class directory {class_dir} not found", stacklevel=2)
+                continue
+            for audio_file in class_dir.iterdir():
+                suffix = audio_file.suffix.lower()
+                if suffix not in _AUDIO_EXTENSIONS:
+                    continue
+                if suffix != ".wav":
+                    skipped += 1
+                    continue
+                waveform, sr = preprocessor.load_audio(str(audio_file))
+                waveform = preprocessor.to_mono(preprocessor.resample(waveform, sr))
+                waveforms.append(waveform.cpu())
+                labels.append(label)
+        if skipped:
+            warnings.warn(f"DeviceClipBank: skipped {skipped} audio file(s) that are not WAVE files; this build decodes "
+                          "WAVE only", stacklevel=2)
+        return cls(waveforms, labels, device=device)
+
+
+class BatchPlan:
+    """The host draws of one batch: ``clips`` (a ``CoughAugClip`` per item, or None without waveform augmentation),
+    ``gaussian`` (the ``torch.randn`` rows of ``noise="host"``, or None), ``seed`` (the device generator's) and ``masks``
+    (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it)."""
+
+    __slots__ = ("clips", "gaussian", "seed", "masks")
+
+    def __init__(self, clips=None, gaussian=None, seed=0, masks=None):
+        self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
+
+
+class DeviceDataLoader:
+    """Batches of a ``DeviceClipBank`` as ``(features (B, 1, F, T) float32, targets (B,) int64)`` on the bank's device,
+    ready for ``trainer.step``, ``train_epoch_async``, ``validate`` and ``fit``.  Iterating it anew is a new epoch.
+
+    Indices: training with ``use_weighted_sampler`` visits ``WeightedRandomSampler(bank.sample_weights, len(bank), True,
+    generator=generator)``, training without it ``RandomSampler(range(n), generator=generator)``; otherwise the order is
+    sequential.  ``drop_last`` defaults to ``is_training``.  The augmentors run only when ``is_training``.
+    ``noise``: where the gaussian step's noise comes from (``AudioAugmentor.augment_batch``); with ``"device"`` one
+    Philox seed is drawn per batch from torch's CPU generator, after the batch's per-item draws.
+    ``cache_features``: featurise the bank once (unmasked) and gather later batches from that tensor; refused when a
+    waveform augmentation can run."""
+
+    def __init__(self, bank: DeviceClipBank, preprocessor, batch_size: int = 32,
+                 audio_augmentor: Optional[AudioAugmentor] = None, spec_augmentor: Optional[SpecAugment] = None,
+                 is_training: bool = True, use_weighted_sampler: bool = True, drop_last: Optional[bool] = None,
+                 generator: Optional[torch.Generator] = None, noise: str = "device", cache_features: bool = False):
+        if batch_size < 1:
+            raise ValueError(f"DeviceDataLoader: batch_size={batch_size} must be positive")
+        if noise not in ("device", "host"):
+            raise ValueError(f"DeviceDataLoader: noise must be 'device' or 'host', got {noise!r}")
+        self.bank, self.preprocessor, self.batch_size = bank, preprocessor, int(batch_size)
+        self.audio_augmentor, self.spec_augmentor = audio_augmentor, spec_augmentor
+        self.is_training, self.use_weighted_sampler = bool(is_training), bool(use_weighted_sampler)
+        self.drop_last = self.is_training if drop_last is None else bool(drop_last)
+        self.generator, self.noise, self.cache_features = generator, noise, bool(cache_features)
+        self._augments = self.is_training and audio_augmentor is not None
+        self._masks = self.is_training and spec_augmentor is not None
+        if self.cache_features and self._augments:
+            raise ValueError("DeviceDataLoader: cache_features=True with a waveform augmentor on a training loader would "
+                             "freeze the first epoch's augmentation; drop one of the two")
+        self._n_masks = len(self._mask_slots()) if self._masks else 0
+        if self._n_masks > _lib.MAX_MASKS:
+            raise ValueError(f"DeviceDataLoader: at most {_lib.MAX_MASKS} masks per image")
+        self._cache: Optional[torch.Tensor] = None
+
+    def _mask_slots(self) -> List[int]:
+        s = self.spec_augmentor
+        return [0] * (s.n_freq_masks if s.freq_mask_param >= 1 else 0) + [1] * (s.n_time_masks if s.time_mask_param >= 1 else 0)
+
+    def feature_shape(self) -> Tuple[int, int]:
+        pre = self.preprocessor
+        return pre.get_num_features(), pre._frames(pre.segment_samples)
+
+    def __len__(self) -> int:
+        n, b = len(self.bank), self.batch_size
+        return n // b if self.drop_last else (n + b - 1) // b
+
+    # ------------------------------------------------------------------ host side: indices and draws
+    def epoch_indices(self) -> List[int]:
+        """The clip indices of one epoch, drawn the way the reference's samplers draw them."""
+        n = len(self.bank)
+        if not self.is_training:
+            return list(range(n))
+        if self.use_weighted_sampler:
+            return list(WeightedRandomSampler(self.bank.sample_weights, n, True, generator=self.generator))
+        return list(RandomSampler(range(n), generator=self.generator))
+
+    def draw_batch(self, indices: Sequence[int]) -> BatchPlan:
+        """One batch's host draws, item by item in batch order (what ``CoughDataset.__getitem__`` draws per item)."""
+        plan = BatchPlan()
+        if not (self._augments or self._masks):
+            return plan
+        lengths = [int(self.bank.lengths[i]) for i in indices]
+        f, t = self.feature_shape()
+        if self._augments:
+            plan.clips = []
+            if self.noise == "host":
+                plan.gaussian = torch.zeros((len(indices), max(lengths)), dtype=torch.float32, pin_memory=self._pinned())
+        if self._masks:
+            plan.masks = []
+        for row, n in enumerate(lengths):
+            if self._augments:
+                c = self.audio_augmentor.draw_clip(n)
+                plan.clips.append(c)
+                if c.gaussian and plan.gaussian is not None:
+                    plan.gaussian[row, :n] = torch.randn(n)
+            if self._masks:
+                fired = not (random.random() > self.spec_augmentor.p)
+                plan.masks.append(self.spec_augmentor.draw_masks(f, t) if fired else [])
+        if self._augments and self.noise == "device":
+            plan.seed = int(torch.randint(0, 2**62, (1,)).item())
+        return plan
+
+    def _pinned(self) -> bool:
+        return self.bank.device.type == "cuda"
+
+    # ------------------------------------------------------------------ device side: five launches
+    def _mask_arrays(self, masks: List[list]) -> np.ndarray:
+        """[3][B][n_masks] int32 (axis, start, end); an image whose coin did not fire keeps all of its masks empty."""
+        arr = np.zeros((3, len(masks), self._n_masks), dtype=np.int32)
+        for b, ms in enumerate(masks):
+            for k, m in enumerate(ms):
+                arr[:, b, k] = m
+        return arr
+
+    def _features(self, indices: Sequence[int], plan: BatchPlan, i64: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """Unmasked features (B, F, T) of the clips ``indices``; ``i64`` holds their bank offsets, then B matrix-row
+        offsets, on the device."""
+        bank, pre, dev = self.bank, self.preprocessor, self.bank.device
+        lib, b = _lib.load_data(), len(indices)
+        seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
+        src, offsets = bank.data, i64[:b]
+        if plan.clips is not None:
+            host_lens = [int(bank.lengths[i]) for i in indices]
+            row_len = max(host_lens)
+            rows = torch.empty((b, row_len), dtype=torch.float32, device=dev)
+            _lib.check_data(lib.cough_gather_rows(bank.data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
+                                                  rows.data_ptr(), row_len, row_len, _stream(dev)), "cough_gather_rows")
+            gaussian = plan.gaussian.to(dev, non_blocking=True) if plan.gaussian is not None else None
+            src = self.audio_augmentor._run(rows, plan.clips, host_lens, gaussian, plan.seed)
+            offsets = i64[b:2 * b]
+        _lib.check_data(lib.cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b, seg.data_ptr(),
+                                               pre.segment_samples, _lib.PREP_NORMALIZE, _stream(dev)), "cough_prepare_rows")
+        return pre.featurize_batch(seg, normalize=False)
+
+    def _fill_cache(self) -> None:
+        n, f_t = len(self.bank), self.feature_shape()
+        self._cache = torch.empty((n,) + f_t, dtype=torch.float32, device=self.bank.device)
+        for lo in range(0, n, self.batch_size):
+            idx = list(range(lo, min(lo + self.batch_size, n)))
+            self._cache[lo:lo + len(idx)] = self._features(idx, BatchPlan(), self.bank.offsets_dev[lo:lo + len(idx)],
+                                                            self.bank.lengths_dev[lo:lo + len(idx)])
+
+    def launch_batch(self, indices: Sequence[int], plan: BatchPlan) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Everything of a batch that runs on the device, stream-ordered; nothing here waits for the device."""
+        bank, dev = self.bank, self.bank.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
+                               "(there is no CPU fallback)")
+        b = len(indices)
+        idx = np.asarray(indices, dtype=np.int64)
+        host_lens = bank.lengths.numpy()[idx]
+        row_len = int(host_lens.max())
+        masks = self._mask_arrays(plan.masks) if plan.masks is not None and self._n_masks else np.zeros(0, np.int32)
+        i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
+                                                bank.labels.numpy()[idx], idx]),
+                           np.concatenate([host_lens, masks.reshape(-1)]))
+        targets = i64[2 * b:3 * b]
+        if self.cache_features:
+            if self._cache is None:
+                self._fill_cache()
+            feats = self._cache[i64[3 * b:4 * b]]
+        else:
+            feats = self._features(indices, plan, i64, i32[:b])
+        if masks.size:
+            m = i32[b:].view(3, b, self._n_masks)
+            mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
+        return feats.unsqueeze(1), targets
+
+    def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        indices = self.epoch_indices()
+        stop = len(self) * self.batch_size if self.drop_last else len(indices)
+        for lo in range(0, stop, self.batch_size):
+            batch = indices[lo:min(lo + self.batch_size, stop)]
+            yield self.launch_batch(batch, self.draw_batch(batch))
+
+
+def create_data_loaders(train_bank: DeviceClipBank, val_bank: DeviceClipBank, preprocessor, batch_size: int = 32,
+                        use_weighted_sampler: bool = True, audio_augmentor: Optional[AudioAugmentor] = None,
+                        spec_augmentor: Optional[SpecAugment] = None, **kw) -> Tuple[DeviceDataLoader, DeviceDataLoader]:
+    """(train_loader, val_loader) as the reference's ``create_data_loaders`` (dataset.py:368-418): the training loader
+    samples with ``WeightedRandomSampler`` (or shuffles), augments and drops the last ragged batch; the validation
+    loader is sequential, unaugmented and keeps it.  ``kw`` goes to the training loader (``generator``, ``noise``,
+    ``cache_features``); ``cache_features`` also to the validation loader."""
+    train = DeviceDataLoader(train_bank, preprocessor, batch_size=batch_size, audio_augmentor=audio_augmentor,
+                             spec_augmentor=spec_augmentor, is_training=True, use_weighted_sampler=use_weighted_sampler,
+                             **kw)
+    val = DeviceDataLoader(val_bank, preprocessor, batch_size=batch_size, is_training=False,
+                           cache_features=kw.get("cache_features", False))
+    return train, val

@@ -329,6 +329,8 @@ class AudioPreprocessor:
         w = waveforms.to(device=dev, dtype=torch.float32)
         if w.stride(1) != 1 or w.stride(0) % 4 != 0 or w.data_ptr() % 16 != 0:
             w = w.contiguous()
+            if w.data_ptr() % 16 != 0:       # a one-row view counts as contiguous wherever it starts (a trimmed clip)
+                w = w.clone()
         b = w.shape[0]
         f, t = self.get_num_features(), self._frames(n_samples)
         if out is None:
