@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: 1 s @ 16 kHz clips/s through featurise (K1) + CoughDetectorResidual (K2-K5).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: set up, pre-warm, warm up, time the K steps, write
+``--dump-outputs``, print the line.  Every measurement that takes a run of its own -- the ``rocprofv3 --pmc`` child runs,
+the stand-alone STFT stage, the CPU baseline -- and the committed PMC records are behind ``--full`` (off by default).
 
 With N > 1 and no torchrun environment this process only LAUNCHES the ranks (``python -m torch.distributed.run
 --nproc-per-node N bench.py ...`` as a child, before anything touches the GPU), relays rank 0's single JSON line
@@ -25,12 +29,13 @@ as ``DIR/<name>.npy`` once timing is done.  Inputs and weights are seeded, so tw
 be compared output for output.
 
 Extra objects on that line: ``roofline`` (featurise kernel vs HBM: algorithmic bytes per clip over the kernel's
-HIP-event time inside the timed region; ``traffic`` = HBM-side bytes per launch COLLECTED IN THIS RUN by child runs of
+HIP-event time inside the timed region; with ``--full``, ``traffic`` = HBM-side bytes per launch COLLECTED IN THIS RUN by child runs of
 this script under ``rocprofv3 --pmc`` (FETCH_SIZE; WRITE_SIZE; MFMA busy -- three passes, ~6 s; ``--no-live-pmc`` or a missing
 rocprofv3 falls back to the committed record and says so in ``traffic_source``)), ``roofline_classifier`` (algorithmic 35.67 MFLOP/clip of the residual blocks
-vs the dense bf16 MFMA peak; the split-bf16 scheme issues 3 MFMAs per algorithmic one, reported as ``mfma_issue_frac``),
-``roofline_stft`` (the STFT stage on its own) and ``cpu_baseline`` (the torch-CPU oracle timed on this box's host
-cores on a bounded sample; rank 0, N = 1 only).
+vs the dense bf16 MFMA peak; the split-bf16 scheme issues 3 MFMAs per algorithmic one, reported as ``mfma_issue_frac``)
+and, with ``--full`` only, ``roofline_stft`` (the STFT stage on its own) and ``cpu_baseline`` (the torch-CPU oracle timed
+on this box's host cores on a bounded sample; rank 0, N = 1 only).  Without ``--full`` the two roofline objects hold what
+the timed steps' own HIP events give; their PMC fields are null and ``traffic_source`` says so.
 """
 from __future__ import annotations
 
@@ -180,7 +185,7 @@ def live_pmc(args, passes=LIVE_PMC_PASSES, kernels=LIVE_PMC_KERNELS):
     if shutil.which("rocprofv3") is None:
         return None, "not collected: rocprofv3 not found"
     child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--prewarm-s", "0",
-             "--batch", str(args.batch), "--dtype", args.dtype, "--no-live-pmc", "--stft-launches", "4"] + \
+             "--batch", str(args.batch), "--dtype", args.dtype, "--full", "--no-live-pmc", "--stft-launches", "4"] + \
             (["--featurize-only"] if args.featurize_only else [])
     res = {}
     tmp = tempfile.mkdtemp(prefix="cough_pmc_", dir="/tmp")
@@ -347,16 +352,19 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=4096, help="clips per rank per step")
     ap.add_argument("--dtype", default=os.environ.get("COUGH_BENCH_DTYPE", "bf16x3"), choices=["bf16x3", "bf16_approx", "fp32"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: live PMC child runs (roofline.traffic, MFMA busy), the "
+                         "stand-alone STFT stage (roofline_stft), the CPU baseline (cpu_baseline), the committed PMC records")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--featurize-only", action="store_true", help="time K1 alone (BASELINE configs[1])")
     ap.add_argument("--rotate", type=int, default=3, help="distinct device-resident input batches the steps cycle over")
     ap.add_argument("--prewarm-s", type=float, default=0.6, help="untimed GPU pre-warm before --warmup (seconds)")
     ap.add_argument("--gather-every", type=int, default=8,
                     help="N > 1: steps per all-gather of logits (one bucketed exchange per this many steps)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not collect roofline.traffic with rocprofv3 --pmc child runs (N = 1); use the committed PMC record")
+                    help="--full: do not collect roofline.traffic with rocprofv3 --pmc child runs (N = 1); use the committed PMC record")
     ap.add_argument("--stft-launches", type=int, default=210,
-                    help="timed launches of the stand-alone STFT stage (roofline_stft); the PMC child runs use a handful")
+                    help="--full: timed launches of the stand-alone STFT stage (roofline_stft); the PMC child runs use a handful")
     ap.add_argument("--total-clips", type=int, default=0,
                     help="configs[3]: one pass over a stream of this many distinct clips (all ranks together); "
                          "overrides --steps and --rotate")
@@ -364,6 +372,10 @@ def parse_args(argv=None):
                     help="after the timed steps, write what the last timed step computed (logits; features with "
                          "--featurize-only) as DIR/<name>.npy, at most 64 MiB in all (a seeded sample of rows beyond that)")
     args = ap.parse_args(argv)
+    given = sys.argv[1:] if argv is None else argv
+    # options that only act under --full and were given without it (main() says so on stderr)
+    args.inert = [] if args.full else [o for o in ("--cpu-seconds", "--no-live-pmc", "--stft-launches")
+                                       if any(a == o or a.startswith(o + "=") for a in given)]
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dtype == "bf16":              # the pre-r03 name of the approximate mode (argparse does not check an env default)
@@ -384,6 +396,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     args.gpus = world
+    if args.inert and rank == 0:
+        print(f"bench.py: {', '.join(args.inert)} only act(s) with --full; ignored in this plain run", file=sys.stderr)
     from cough_detector_amd.hostcpu import bind_to_gpu_numa, bound_torch_threads
     share_gpu = os.environ.get("COUGH_BENCH_SHARE_GPU") == "1"       # REHEARSAL only: several ranks on one card
     backend = os.environ.get("COUGH_BENCH_BACKEND", "nccl")          # REHEARSAL only: "gloo" (RCCL refuses two ranks per GPU)
@@ -547,12 +561,14 @@ def main():
         # clip); that hand-off shows up in `traffic` (PMC), not in `achieved`.
         k1_bytes = BYTES_PER_CLIP
         achieved = Bk * k1_bytes / (k1_ms * 1e-3) / 1e9 if k1_ms > 0 else 0.0
-        pmc = measured_pmc(Bk, ("k1_fused_" + args.dtype) if fused else "k1")
-        traffic, traffic_src = pmc.get("traffic_bytes_per_launch"), pmc.get("source")
+        # a plain run stops at what the timed steps' own events give; PMC figures (committed or live) need --full
+        pmc = measured_pmc(Bk, ("k1_fused_" + args.dtype) if fused else "k1") if args.full else {}
+        traffic = pmc.get("traffic_bytes_per_launch")
+        traffic_src = pmc.get("source") if args.full else "not collected: PMC figures are part of --full"
         live_all = None
         if traffic is not None:
             traffic = int(traffic)
-        if (world == 1 and not dist and not args.no_live_pmc and args.total_clips == 0 and Bk == B
+        if (args.full and world == 1 and not dist and not args.no_live_pmc and args.total_clips == 0 and Bk == B
                 and os.environ.get("COUGH_BENCH_LIVE_PMC", "1") == "1"):
             live_all, why_not = live_pmc(args)
             if live_all is None and traffic_src:
@@ -618,7 +634,7 @@ def main():
                 line["roofline_classifier"]["mfma_pipe_busy"] = busy
                 line["roofline_classifier"]["mfma_pipe_busy_source"] = "live: rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE (child run of this command)"
         stft_in = [b_ for b_ in batches[:8] if b_.shape[0] == B]
-        if world == 1 and not dist and stft_in:
+        if args.full and world == 1 and not dist and stft_in:
             line["roofline_stft"] = stft_stage(pre, stft_in, launches=max(1, args.stft_launches),
                                                warm=min(60, max(1, args.stft_launches)))
             lv = (live_all or {}).get("stft3_kernel")
@@ -628,7 +644,7 @@ def main():
                 rs["traffic_source"] = (f"live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE ({lv['launches']} launches): "
                                         f"{lv['fetch']} + {lv['write']} bytes per launch")
                 rs["traffic_over_algorithmic"] = round(lv["traffic"] / rs["algorithmic_bytes_per_launch"], 3)
-        if world == 1 and not dist and args.cpu_seconds > 0:
+        if args.full and world == 1 and not dist and args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         if dist:
             line["rccl_world"] = dist.get_world_size()

@@ -114,6 +114,32 @@ def test_live_pmc_never_nests_profilers_and_scrubs_the_child_environment(monkeyp
     assert not any(k.startswith(("ROCP_", "ROCPROF_")) for k in env) and env["TMPDIR"] == "/tmp"
 
 
+def test_full_is_off_by_default_and_the_pmc_children_ask_for_it(monkeypatch):
+    """A plain run measures only its headline; --full turns the other measurements on.  The `rocprofv3 --pmc` children of a --full
+    run count the stand-alone STFT kernel too, so they are --full runs themselves (without PMC children or a CPU leg of their own)."""
+    assert bench.parse_args([]).full is False and bench.parse_args(["--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    # the options of the moved measurements do nothing in a plain run: parse_args names them, main() says so on stderr
+    assert bench.parse_args(["--cpu-seconds", "0", "--stft-launches=4", "--steps", "3"]).inert == ["--cpu-seconds", "--stft-launches"]
+    assert bench.parse_args(["--full", "--cpu-seconds", "0", "--no-live-pmc"]).inert == [] and bench.parse_args([]).inert == []
+    started = []
+
+    class FakeProc:
+        def __init__(self, cmd, **kw):
+            started.append(cmd)
+
+        def wait(self, timeout=None):
+            return 1
+
+    monkeypatch.setattr(bench.subprocess, "Popen", FakeProc)
+    monkeypatch.setattr(__import__("shutil"), "which", lambda name: "/usr/bin/" + name)
+    monkeypatch.setattr(bench, "under_profiler", lambda env=None: False)
+    res, why = bench.live_pmc(bench.parse_args(["--full", "--steps", "3"]))
+    assert res is None and len(started) == 1
+    child = started[0][started[0].index("--") + 1:]
+    assert "--full" in child and "--no-live-pmc" in child and child[child.index("--cpu-seconds") + 1] == "0"
+
+
 def test_streaming_bench_parent_command_and_single_aggregated_line():
     """configs[4] under torchrun must yield ONE JSON line for the job -- global latency percentiles over every
     rank's samples, aggregate windows/s over the slowest rank's wall time, the per-rank records -- not one line per rank."""

@@ -7,12 +7,12 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-python bench.py --steps 20 --warmup 5 > $OUT/bench_default_20.json 2> $OUT/bench_default_20.err && \
-python bench.py --cpu-seconds 0 > $OUT/bench_default_long.json 2> $OUT/bench_default_long.err && \
-python bench.py --steps 200 --cpu-seconds 0 --featurize-only > $OUT/bench_featurize_only.json 2> $OUT/bench_featurize_only.err && \
-python bench.py --steps 200 --cpu-seconds 0 --dtype bf16_approx > $OUT/bench_bf16_approx.json 2> $OUT/bench_bf16.err && \
-python bench.py --steps 50 --cpu-seconds 0 --dtype fp32 > $OUT/bench_fp32.json 2> $OUT/bench_fp32.err && \
-python bench.py --total-clips 1000000 --cpu-seconds 0 > $OUT/bench_total_1M.json 2> $OUT/bench_total_1M.err && \
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default_20.json 2> $OUT/bench_default_20.err && \
+python bench.py --full --cpu-seconds 0 > $OUT/bench_default_long.json 2> $OUT/bench_default_long.err && \
+python bench.py --full --steps 200 --cpu-seconds 0 --featurize-only > $OUT/bench_featurize_only.json 2> $OUT/bench_featurize_only.err && \
+python bench.py --full --steps 200 --cpu-seconds 0 --dtype bf16_approx > $OUT/bench_bf16_approx.json 2> $OUT/bench_bf16.err && \
+python bench.py --full --steps 50 --cpu-seconds 0 --dtype fp32 > $OUT/bench_fp32.json 2> $OUT/bench_fp32.err && \
+python bench.py --full --total-clips 1000000 --cpu-seconds 0 > $OUT/bench_total_1M.json 2> $OUT/bench_total_1M.err && \
 COUGH_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err && \
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 tests/multirank_check.py > $OUT/rccl_check_1rank.txt 2>&1 && \
 python bench_streaming.py --streams 64 --seconds 20 > $OUT/streaming_64.json 2> $OUT/streaming_64.err && \

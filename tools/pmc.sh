@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 PMC passes for any kernel of bench.py (separate passes; never combined with tracing).
 # Usage on the GPU box: bash tools/pmc.sh <outdir-under-gpurun_out> <kernel-name-substring> [bench args...]
+# A plain bench.py run does not launch stft3_kernel (roofline_stft): put --full among the bench args to count that kernel.
 set -u
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/$1; KSUB=$2; shift 2
 mkdir -p "$OUT"
