@@ -11,6 +11,7 @@ from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, 
 from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, load_checkpoint, save_checkpoint,
                    train_epoch_async, validate)
 from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
+from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -18,4 +19,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "CoughPipeline", "AudioAugmentor", "MixUp", "SpecAugment", "create_augmentation_pipeline",
            "ResidualTrainer", "SmallTrainer", "StandardTrainer", "create_trainer", "HipAdamW", "train_epoch",
            "EpochMeter", "EarlyStopping", "train_epoch_async", "validate", "save_checkpoint", "load_checkpoint",
-           "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders"]
+           "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders",
+           "SegmentTable", "frame_energy", "find_segments", "extract_segments"]

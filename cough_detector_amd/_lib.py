@@ -1,6 +1,7 @@
 """ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``) and of its companion
 ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``) and
-``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``).
+``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``) and
+``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -68,6 +69,13 @@ DATA_SYMBOLS = ("cough_data_abi_version", "cough_data_last_error", "cough_gather
                 "cough_mask_images")
 PREP_NORMALIZE = 1       # COUGH_PREP_NORMALIZE
 MAX_MASKS = 16           # COUGH_MAX_MASKS
+
+# every symbol include/cough_amd_segments.h declares (the companion library of corpus curation)
+SEGMENTS_LIB_PATH = os.environ.get("COUGH_AMD_SEGMENTS_LIB") or os.path.join(HERE, "libcough_amd_segments.so")
+SEGMENTS_SYMBOLS = ("cough_segments_abi_version", "cough_segments_last_error", "cough_frame_energy_tile_frames",
+                    "cough_frame_energy", "cough_pick_segments", "cough_copy_segments")
+MAX_SEGMENTS = 16        # COUGH_MAX_SEGMENTS
+MAX_FRAME_LENGTH = 4096  # COUGH_MAX_FRAME_LENGTH
 
 
 MAX_CONTRAST_BANDS = 16
@@ -266,6 +274,35 @@ def load_data() -> C.CDLL:
     return _data_lib
 
 
+_segments_lib = None
+
+
+def load_segments() -> C.CDLL:
+    """Load (once) and type the companion library of corpus curation; raise loudly if it is not built."""
+    global _segments_lib
+    if _segments_lib is not None:
+        return _segments_lib
+    with _lock:
+        if _segments_lib is not None:
+            return _segments_lib
+        if not os.path.exists(SEGMENTS_LIB_PATH):
+            raise RuntimeError(
+                f"{SEGMENTS_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(SEGMENTS_LIB_PATH)
+        vp, i, d = C.c_void_p, C.c_int, C.c_double
+        lib.cough_segments_abi_version.restype = i
+        lib.cough_segments_last_error.restype = C.c_char_p
+        lib.cough_frame_energy_tile_frames.argtypes = [i, i]
+        lib.cough_frame_energy.argtypes = [vp, vp, vp, vp, i, vp, i, i, i, vp, vp]
+        lib.cough_pick_segments.argtypes = [vp, vp, vp, i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp]
+        lib.cough_copy_segments.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
+        if lib.cough_segments_abi_version() != 1:
+            raise RuntimeError("libcough_amd_segments.so ABI version mismatch; rebuild it")
+        _segments_lib = lib
+    return _segments_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -282,6 +319,12 @@ def check_data(status: int, what: str) -> None:
     """``check`` for a call into the input pipeline's library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_data().cough_data_last_error().decode("utf-8", "replace"))
+
+
+def check_segments(status: int, what: str) -> None:
+    """``check`` for a call into the curation library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_segments().cough_segments_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:
