@@ -12,6 +12,8 @@ from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, lo
                    train_epoch_async, validate)
 from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
+from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
+                    sweep_thresholds)
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -20,4 +22,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "ResidualTrainer", "SmallTrainer", "StandardTrainer", "create_trainer", "HipAdamW", "train_epoch",
            "EpochMeter", "EarlyStopping", "train_epoch_async", "validate", "save_checkpoint", "load_checkpoint",
            "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders",
-           "SegmentTable", "frame_energy", "find_segments", "extract_segments"]
+           "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
+           "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report"]

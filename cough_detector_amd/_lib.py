@@ -1,7 +1,8 @@
 """ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``) and of its companion
 ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``) and
 ``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``) and
-``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``).
+``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``)
+and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -76,6 +77,13 @@ SEGMENTS_SYMBOLS = ("cough_segments_abi_version", "cough_segments_last_error", "
                     "cough_frame_energy", "cough_pick_segments", "cough_copy_segments")
 MAX_SEGMENTS = 16        # COUGH_MAX_SEGMENTS
 MAX_FRAME_LENGTH = 4096  # COUGH_MAX_FRAME_LENGTH
+
+# every symbol include/cough_amd_score.h declares (the companion library of offline scoring)
+SCORE_LIB_PATH = os.environ.get("COUGH_AMD_SCORE_LIB") or os.path.join(HERE, "libcough_amd_score.so")
+SCORE_SYMBOLS = ("cough_score_abi_version", "cough_score_last_error", "cough_smooth_windows", "cough_sweep_thresholds",
+                 "cough_list_events")
+MAX_SMOOTHING = 32       # COUGH_MAX_SMOOTHING
+MAX_THRESHOLDS = 1024    # COUGH_MAX_THRESHOLDS
 
 
 MAX_CONTRAST_BANDS = 16
@@ -303,6 +311,34 @@ def load_segments() -> C.CDLL:
     return _segments_lib
 
 
+_score_lib = None
+
+
+def load_score() -> C.CDLL:
+    """Load (once) and type the companion library of offline scoring; raise loudly if it is not built."""
+    global _score_lib
+    if _score_lib is not None:
+        return _score_lib
+    with _lock:
+        if _score_lib is not None:
+            return _score_lib
+        if not os.path.exists(SCORE_LIB_PATH):
+            raise RuntimeError(
+                f"{SCORE_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(SCORE_LIB_PATH)
+        vp, ll, i, d = C.c_void_p, C.c_longlong, C.c_int, C.c_double
+        lib.cough_score_abi_version.restype = i
+        lib.cough_score_last_error.restype = C.c_char_p
+        lib.cough_smooth_windows.argtypes = [vp, vp, i, ll, i, vp, vp]
+        lib.cough_sweep_thresholds.argtypes = [vp, vp, i, ll, vp, i, i, vp, vp, vp, vp, vp]
+        lib.cough_list_events.argtypes = [vp, vp, i, ll, d, i, vp, ll, vp, vp, vp]
+        if lib.cough_score_abi_version() != 1:
+            raise RuntimeError("libcough_amd_score.so ABI version mismatch; rebuild it")
+        _score_lib = lib
+    return _score_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -325,6 +361,12 @@ def check_segments(status: int, what: str) -> None:
     """``check`` for a call into the curation library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_segments().cough_segments_last_error().decode("utf-8", "replace"))
+
+
+def check_score(status: int, what: str) -> None:
+    """``check`` for a call into the scoring library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_score().cough_score_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:
