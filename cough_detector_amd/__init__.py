@@ -11,6 +11,7 @@ from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, 
 from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, load_checkpoint, save_checkpoint,
                    train_epoch_async, validate)
 from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
+from .draws import augment_rows_drawn, draw_batch
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
                     sweep_thresholds)
@@ -23,4 +24,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "EpochMeter", "EarlyStopping", "train_epoch_async", "validate", "save_checkpoint", "load_checkpoint",
            "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders",
            "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
-           "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report"]
+           "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report",
+           "draw_batch", "augment_rows_drawn"]

@@ -2,7 +2,8 @@
 ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``) and
 ``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``) and
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``)
-and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``).
+and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``) and
+``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -84,6 +85,11 @@ SCORE_SYMBOLS = ("cough_score_abi_version", "cough_score_last_error", "cough_smo
                  "cough_list_events")
 MAX_SMOOTHING = 32       # COUGH_MAX_SMOOTHING
 MAX_THRESHOLDS = 1024    # COUGH_MAX_THRESHOLDS
+
+# every symbol include/cough_amd_draws.h declares (the companion library of the device-side draws)
+DRAWS_LIB_PATH = os.environ.get("COUGH_AMD_DRAWS_LIB") or os.path.join(HERE, "libcough_amd_draws.so")
+DRAWS_SYMBOLS = ("cough_draws_abi_version", "cough_draws_last_error", "cough_draw_batch",
+                 "cough_augment_rows_drawn_workspace_bytes", "cough_augment_rows_drawn")
 
 
 MAX_CONTRAST_BANDS = 16
@@ -339,6 +345,35 @@ def load_score() -> C.CDLL:
     return _score_lib
 
 
+_draws_lib = None
+
+
+def load_draws() -> C.CDLL:
+    """Load (once) and type the companion library of the device-side draws; raise loudly if it is not built."""
+    global _draws_lib
+    if _draws_lib is not None:
+        return _draws_lib
+    with _lock:
+        if _draws_lib is not None:
+            return _draws_lib
+        if not os.path.exists(DRAWS_LIB_PATH):
+            raise RuntimeError(
+                f"{DRAWS_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(DRAWS_LIB_PATH)
+        vp, ll, i, d, ull = C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_ulonglong
+        lib.cough_draws_abi_version.restype = i
+        lib.cough_draws_last_error.restype = C.c_char_p
+        lib.cough_draw_batch.argtypes = [ull, i, vp, d, i, vp, d, i, i, i, i, i, i, vp, vp, vp, vp, vp]
+        lib.cough_augment_rows_drawn_workspace_bytes.argtypes = [i]
+        lib.cough_augment_rows_drawn_workspace_bytes.restype = C.c_size_t
+        lib.cough_augment_rows_drawn.argtypes = [vp, vp, vp, i, i, vp, vp, ll, vp, vp, i, ull, vp, vp, C.c_size_t, vp]
+        if lib.cough_draws_abi_version() != 1:
+            raise RuntimeError("libcough_amd_draws.so ABI version mismatch; rebuild it")
+        _draws_lib = lib
+    return _draws_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -367,6 +402,12 @@ def check_score(status: int, what: str) -> None:
     """``check`` for a call into the scoring library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_score().cough_score_last_error().decode("utf-8", "replace"))
+
+
+def check_draws(status: int, what: str) -> None:
+    """``check`` for a call into the draws library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_draws().cough_draws_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:

@@ -144,6 +144,7 @@ class AudioAugmentor:
         self._bank_offsets: List[int] = []
         self._bank_lengths: List[int] = []
         self._bank_dev = None
+        self._bank_tables = None                         # (device, int64 offsets, int32 lengths) on the device
         if noise_dir and Path(noise_dir).exists():
             self._load_noise_samples(noise_dir)
 
@@ -191,6 +192,7 @@ class AudioAugmentor:
         self._bank_host = (torch.cat([w.reshape(-1).float() for w in self.noise_samples]) if lengths
                            else torch.zeros(0, dtype=torch.float32))
         self._bank_dev = None
+        self._bank_tables = None
         if lengths and torch.cuda.is_available():
             self._bank_dev = self._bank_host.to(cuda_device())
 
@@ -198,6 +200,13 @@ class AudioAugmentor:
         if self._bank_dev is None or self._bank_dev.device != dev:
             self._bank_dev = self._bank_host.to(dev)
         return self._bank_dev
+
+    def _bank_tables_device(self, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The bank's offsets (int64) and lengths (int32) as device tensors, uploaded once per packing of the bank."""
+        if self._bank_tables is None or self._bank_tables[0] != dev:
+            self._bank_tables = (dev, torch.tensor(self._bank_offsets, dtype=torch.int64).to(dev),
+                                 torch.tensor(self._bank_lengths, dtype=torch.int32).to(dev))
+        return self._bank_tables[1], self._bank_tables[2]
 
     # ------------------------------------------------------------------ host draws (the reference's order)
     def _coin(self) -> bool:

@@ -1,12 +1,12 @@
-"""Build libcough_amd.so and its companions libcough_amd_loop.so, libcough_amd_data.so, libcough_amd_segments.so and
-libcough_amd_score.so (HIP, gfx950 only) in-tree with hipcc.
+"""Build libcough_amd.so and its companions libcough_amd_loop.so, libcough_amd_data.so, libcough_amd_segments.so,
+libcough_amd_score.so and libcough_amd_draws.so (HIP, gfx950 only) in-tree with hipcc.
 
 Every translation unit is compiled to an object file of its own (in parallel, cached under ``build/`` by the newest
 source / header time) and the objects are linked into the shared libraries: ``SOURCES`` into ``libcough_amd.so`` (the
 C-ABI of ``include/cough_amd.h``), ``LOOP_SOURCES`` into ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``),
 ``DATA_SOURCES`` into ``libcough_amd_data.so`` (``include/cough_amd_data.h``), ``SEGMENTS_SOURCES`` into
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``), ``SCORE_SOURCES`` into ``libcough_amd_score.so``
-(``include/cough_amd_score.h``).  The libraries are build products and stay out of git.
+(``include/cough_amd_score.h``), ``DRAWS_SOURCES`` into ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``).  The libraries are build products and stay out of git.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
 from __future__ import annotations
@@ -36,6 +36,10 @@ SEGMENTS_SOURCES = ("segments.hip",)
 # the companion library of offline scoring (deque mean, threshold sweep, event list), on the same terms
 SCORE_LIB = os.path.join(HERE, "libcough_amd_score.so")
 SCORE_SOURCES = ("score.hip",)
+# the companion library of the device-side draws (a batch's augmentation records and masks, augmentation from them), on
+# the same terms; it compiles csrc/augment_kernel.h, the kernel augment.hip runs
+DRAWS_LIB = os.path.join(HERE, "libcough_amd_draws.so")
+DRAWS_SOURCES = ("draws.hip",)
 # -fno-slp-vectorize: left alone, -O3 packs adjacent f32 adds / multiplies of the FFT butterflies into v_pk_*_f32, which issue
 # slower than the two scalar operations they replace on gfx950 (same-box A/B: K1 -2.4 %, STFT stage -3.2 %, classifier unchanged;
 # profiles/r04_flag_ab.txt)
@@ -56,20 +60,22 @@ def _hipcc() -> str:
 def _headers_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     deps += [os.path.join(HERE, "..", "include", h) for h in ("cough_amd.h", "cough_amd_loop.h", "cough_amd_data.h",
-                                                                   "cough_amd_segments.h", "cough_amd_score.h")]
+                                                                   "cough_amd_segments.h", "cough_amd_score.h",
+                                                                   "cough_amd_draws.h")]
     deps.append(os.path.abspath(__file__))   # the flags live here
     deps += [os.path.join(CSRC, m) for m in ("exports.map", "exports_loop.map", "exports_data.map", "exports_segments.map",
-                                             "exports_score.map")]
+                                             "exports_score.map", "exports_draws.map")]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB)
+    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t
-                                       for s in SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES)
+                                       for s in SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
+                                       + DRAWS_SOURCES)
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB) -> str:
@@ -99,7 +105,8 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
         subprocess.run(cmd, check=True)
 
     variant = bool(extra_flags) or out != LIB
-    sources = SOURCES if variant else SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
+    sources = SOURCES if variant else (SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
+                                      + DRAWS_SOURCES)
     with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, sources))
     link(objs[:len(SOURCES)], "exports.map", out)
@@ -109,7 +116,9 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
         link(objs[len(SOURCES) + len(LOOP_SOURCES):data_end], "exports_data.map", DATA_LIB)
         segments_end = data_end + len(SEGMENTS_SOURCES)
         link(objs[data_end:segments_end], "exports_segments.map", SEGMENTS_LIB)
-        link(objs[segments_end:], "exports_score.map", SCORE_LIB)
+        score_end = segments_end + len(SCORE_SOURCES)
+        link(objs[segments_end:score_end], "exports_score.map", SCORE_LIB)
+        link(objs[score_end:], "exports_draws.map", DRAWS_LIB)
     return out
 
 

@@ -21,6 +21,11 @@ Differences a caller can observe: WAVE files only (``load_audio``); ``noise="dev
 noise with the seeded counter-based generator of ``cough_augment_waveforms`` instead of ``torch.randn``;
 ``cache_features`` keeps the unmasked features of the whole bank in one device tensor and is refused when a waveform
 augmentation could run (the reference's ``cache_spectrograms`` would silently freeze the first epoch's augmentation).
+
+``draws="device"`` moves every per-item draw to the device as well (``cough_detector_amd/draws.py``): the host draws the
+epoch's indices and ONE seed per epoch, and a batch is four launches -- draw, augment the rows in place in the bank,
+``cough_prepare_rows``, the featuriser -- plus ``cough_mask_images`` when there are masks.  The draws then have the
+reference's distributions but are not its random stream (the masks are drawn in float64, the reference's in float32).
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ import torch
 from torch.utils.data import RandomSampler, WeightedRandomSampler
 
 from . import _lib
+from . import draws as _draws
 from ._native import cuda_device
 from .augmentation import AudioAugmentor, SpecAugment, mask_images
 
@@ -184,16 +190,29 @@ class DeviceDataLoader:
     ``noise``: where the gaussian step's noise comes from (``AudioAugmentor.augment_batch``); with ``"device"`` one
     Philox seed is drawn per batch from torch's CPU generator, after the batch's per-item draws.
     ``cache_features``: featurise the bank once (unmasked) and gather later batches from that tensor; refused when a
-    waveform augmentation can run."""
+    waveform augmentation can run.
+    ``draws``: ``"host"`` (the default) makes the per-item draws on the host, in the reference's order, as described
+    above.  ``"device"`` makes them on the device (needs ``noise="device"``): after the epoch's indices, ``__iter__``
+    draws one ``epoch_seed`` from ``generator`` (kept as ``last_epoch_seed``), and batch k draws its records, its masks
+    and its gaussian noise under ``(epoch_seed + k) mod 2^64`` in ``launch_batch_drawn``; no per-clip Python runs and
+    nothing is copied from pageable memory.  These draws have the reference's distributions, not its random stream
+    (float64 masks where the reference draws float32): a seeded run repeats itself, not a reference loader.  A loader that
+    has nothing to draw (no augmentor, or not training) behaves the same in both modes."""
 
     def __init__(self, bank: DeviceClipBank, preprocessor, batch_size: int = 32,
                  audio_augmentor: Optional[AudioAugmentor] = None, spec_augmentor: Optional[SpecAugment] = None,
                  is_training: bool = True, use_weighted_sampler: bool = True, drop_last: Optional[bool] = None,
-                 generator: Optional[torch.Generator] = None, noise: str = "device", cache_features: bool = False):
+                 generator: Optional[torch.Generator] = None, noise: str = "device", cache_features: bool = False,
+                 draws: str = "host"):
         if batch_size < 1:
             raise ValueError(f"DeviceDataLoader: batch_size={batch_size} must be positive")
         if noise not in ("device", "host"):
             raise ValueError(f"DeviceDataLoader: noise must be 'device' or 'host', got {noise!r}")
+        if draws not in ("device", "host"):
+            raise ValueError(f"DeviceDataLoader: draws must be 'device' or 'host', got {draws!r}")
+        if draws == "device" and noise == "host":
+            raise ValueError("DeviceDataLoader: draws='device' takes the gaussian noise from the device generator too; "
+                             "it cannot be combined with noise='host'")
         self.bank, self.preprocessor, self.batch_size = bank, preprocessor, int(batch_size)
         self.audio_augmentor, self.spec_augmentor = audio_augmentor, spec_augmentor
         self.is_training, self.use_weighted_sampler = bool(is_training), bool(use_weighted_sampler)
@@ -208,6 +227,8 @@ class DeviceDataLoader:
         if self._n_masks > _lib.MAX_MASKS:
             raise ValueError(f"DeviceDataLoader: at most {_lib.MAX_MASKS} masks per image")
         self._cache: Optional[torch.Tensor] = None
+        self.draws = draws
+        self.last_epoch_seed: Optional[int] = None
 
     def _mask_slots(self) -> List[int]:
         s = self.spec_augmentor
@@ -323,12 +344,54 @@ class DeviceDataLoader:
             mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
         return feats.unsqueeze(1), targets
 
+    def launch_batch_drawn(self, indices: Sequence[int], seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
+        gaussian noise): draw, augment the rows in place in the bank, ``cough_prepare_rows``, the featuriser, and
+        ``cough_mask_images`` when there are masks.  The result equals ``launch_batch(indices, plan)`` for the
+        ``BatchPlan`` that holds the same records and masks with ``seed`` as its noise seed."""
+        bank, pre, dev = self.bank, self.preprocessor, self.bank.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
+                               "(there is no CPU fallback)")
+        b = len(indices)
+        idx = np.asarray(indices, dtype=np.int64)
+        host_lens = bank.lengths.numpy()[idx]
+        row_len = int(host_lens.max())
+        i64, lens = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
+                                                 bank.labels.numpy()[idx], idx]), host_lens)
+        targets = i64[2 * b:3 * b]
+        clips, masks = _draws.draw_batch(seed, lens, self.audio_augmentor if self._augments else None,
+                                         self.spec_augmentor if self._n_masks else None, self.feature_shape())
+        if self.cache_features:
+            if self._cache is None:
+                self._fill_cache()
+            feats = self._cache[i64[3 * b:4 * b]]
+        else:
+            src, offsets = bank.data, i64[:b]
+            if clips is not None:
+                src = _draws.augment_rows_drawn(bank.data, offsets, lens, row_len, clips, self.audio_augmentor, seed)
+                offsets = i64[b:2 * b]
+            seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
+            _lib.check_data(_lib.load_data().cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
+                                                                seg.data_ptr(), pre.segment_samples, _lib.PREP_NORMALIZE,
+                                                                _stream(dev)), "cough_prepare_rows")
+            feats = pre.featurize_batch(seg, normalize=False)
+        if masks is not None:
+            mask_images(feats, feats, masks[0], masks[1], masks[2], self._n_masks)
+        return feats.unsqueeze(1), targets
+
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         indices = self.epoch_indices()
         stop = len(self) * self.batch_size if self.drop_last else len(indices)
-        for lo in range(0, stop, self.batch_size):
+        drawn = self.draws == "device" and (self._augments or self._masks)
+        if drawn:
+            self.last_epoch_seed = int(torch.randint(0, 2**62, (1,), generator=self.generator).item())
+        for k, lo in enumerate(range(0, stop, self.batch_size)):
             batch = indices[lo:min(lo + self.batch_size, stop)]
-            yield self.launch_batch(batch, self.draw_batch(batch))
+            if drawn:
+                yield self.launch_batch_drawn(batch, (self.last_epoch_seed + k) & (2**64 - 1))
+            else:
+                yield self.launch_batch(batch, self.draw_batch(batch))
 
 
 def create_data_loaders(train_bank: DeviceClipBank, val_bank: DeviceClipBank, preprocessor, batch_size: int = 32,
@@ -337,7 +400,7 @@ def create_data_loaders(train_bank: DeviceClipBank, val_bank: DeviceClipBank, pr
     """(train_loader, val_loader) as the reference's ``create_data_loaders`` (dataset.py:368-418): the training loader
     samples with ``WeightedRandomSampler`` (or shuffles), augments and drops the last ragged batch; the validation
     loader is sequential, unaugmented and keeps it.  ``kw`` goes to the training loader (``generator``, ``noise``,
-    ``cache_features``); ``cache_features`` also to the validation loader."""
+    ``cache_features``, ``draws``); ``cache_features`` also to the validation loader."""
     train = DeviceDataLoader(train_bank, preprocessor, batch_size=batch_size, audio_augmentor=audio_augmentor,
                              spec_augmentor=spec_augmentor, is_training=True, use_weighted_sampler=use_weighted_sampler,
                              **kw)
