@@ -130,13 +130,31 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
     return *reinterpret_cast<uint16_t*>(&b);
 }
 // geometry of the fused stem for the 90x101 feature image (resnet.hip: stem_bf16_kernel / stem_lds)
-constexpr int ST_P1H = 22, ST_P1W = 25, ST_ROWS = 94, ST_PITCH = 106;   // image width = NFRAMES
+constexpr int ST_P1H = 22, ST_P1W = 25, ST_ROWS = 94;   // image width = NFRAMES
 constexpr int ST_PER = ST_P1H * ST_P1W, ST_TILES = (ST_PER + 7) / 8;
-constexpr size_t ST_IMG = size_t(ST_ROWS) * ST_PITCH * 2;   // bytes of one bf16 image
-static_assert(ST_IMG <= LDS_MEL, "the bf16 feature image aliases the dB buffer");
-// split-bf16 stem: two images (hi, lo) at the end of the workgroup's LDS, over everything but the z-scored MFCC rows
-constexpr size_t ST_X3_OFF = LDS_TOTAL - 2 * ST_IMG;
-static_assert(ST_X3_OFF % 16 == 0 && ST_IMG % 4 == 0 && ST_X3_OFF >= size_t(NMF) * 4, "hi / lo images vs the MFCC buffer");
+// Image pitch in bf16.  An A fragment is four ds_read_b32 at dword (2 (2 ph + dy) + sh) * pitch / 2 + 2 pw + dx (+ 0..3): a
+// 32-lane group covers 16 consecutive dwords per dy, and dy adds two image rows = `pitch` dwords.  106 (the narrowest even pitch
+// of the 101 + 3 + 2 columns) puts the dy = 1 half 10 banks behind the dy = 0 half, so 6 banks are hit twice and every read
+// takes two passes; 112 puts it 16 banks behind -- disjoint banks, conflicts only where a tile crosses a pooled row (modelled
+// over the 69 tiles of a clip: 1.275 x the conflict-free cycles against 2.000 x; tests/test_stem_lds_banking.py).
+// The wide pitch costs 2 x 1128 B of LDS, so the FULL instantiations keep 106: their CSR filterbank already takes them to 53 488 B
+// of the 53 760 B at which three workgroups share a CU.
+constexpr int ST_PITCH_NARROW = 106, ST_PITCH_WIDE = 112;
+constexpr int st_pitch(bool full) { return full ? ST_PITCH_NARROW : ST_PITCH_WIDE; }
+constexpr size_t st_img(bool full) { return size_t(ST_ROWS) * st_pitch(full) * 2; }   // bytes of one bf16 image
+static_assert((2 * (ST_PITCH_WIDE / 2)) % 32 == 16 && ST_PITCH_WIDE % 2 == 0, "wide pitch: dy moves a fragment 16 banks on");
+static_assert(st_img(false) <= LDS_MEL, "the bf16 feature image aliases the dB buffer");
+// split-bf16 stem: two images (hi, lo) at the end of the workgroup's LDS, over everything but the z-scored MFCC rows.  FULL: the
+// images end where the shipped layout's LDS_TOTAL ends; shipped: they start right behind the MFCC rows and the workgroup grows to
+// LDS_X3_WIDE bytes
+constexpr size_t LDS_WG3_MAX = 53760;   // three workgroups per CU up to here (1280-byte granules, tools/micro/lds_occupancy.hip)
+constexpr size_t st_x3_off(bool full) { return full ? LDS_TOTAL - 2 * st_img(true) : (size_t(NMF) * 4 + 15) & ~size_t(15); }
+constexpr size_t LDS_X3_WIDE = st_x3_off(false) + 2 * st_img(false);   // 47 376
+static_assert(st_x3_off(false) % 16 == 0 && st_x3_off(true) % 16 == 0 && st_img(false) % 4 == 0 && st_img(true) % 4 == 0 &&
+              st_x3_off(true) >= size_t(NMF) * 4, "hi / lo images vs the MFCC buffer");
+static_assert(LDS_X3_WIDE >= LDS_TOTAL && LDS_X3_WIDE <= LDS_WG3_MAX, "the widened split-bf16 stem keeps three workgroups per CU");
+// dynamic LDS of a shipped (FULL = false) instantiation: only the split-bf16 stem's two wide images reach past LDS_TOTAL
+constexpr size_t shipped_lds_bytes(int stem) { return stem == 2 ? LDS_X3_WIDE : LDS_TOTAL; }
 
 // kernel argument of the FULL instantiations: device pointers into the featuriser's full-band blob
 struct FullBank {
@@ -194,6 +212,11 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
     float* __restrict__ peak_out /* [n] or nullptr: the clip's max |sample| under the fused normalise (the contrast path's scale) */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(!GEO || (FULL && STEM == 0 && !TALL && !PCS), "run-time geometry: full-band instantiations without a stem");
+    // the stem's image pitch and the offset of the split-bf16 images: wide for the shipped layout, narrow for FULL (whose LDS is
+    // sized at run time by the filterbank: full_lds_bytes); shipped_lds_bytes(STEM) is what launch_featurize gives the shipped ones
+    constexpr int ST_PITCH = st_pitch(FULL);
+    constexpr size_t ST_X3_OFF = st_x3_off(FULL);
+    static_assert(FULL || shipped_lds_bytes(STEM) <= LDS_WG3_MAX, "a shipped instantiation keeps three workgroups per CU");
     // frames per clip, four-frame groups, samples per clip, hop: compile-time constants unless GEO
     const int NF = GEO ? fbk.n_frames : NFRAMES, NGR = GEO ? (fbk.n_frames + FPW - 1) / FPW : NGROUP;
     const int NSMP = GEO ? fbk.n_samples : NS, HP = GEO ? fbk.hop : HOP;
@@ -1021,21 +1044,33 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
         const int q = sr >> 2, dy = (sr >> 1) & 1, dx = sr & 1;
         using out_t = std::conditional_t<STEM == 2, float, uint16_t>;
         out_t* oa = reinterpret_cast<out_t*>(stem.a1) + clip * (long long)ST_PER * 32;
-        auto frag_base = [&](int tile) -> const uint32_t* {
+        // byte offset of a tile's fragment (plane 0, k-step 0) in the workgroup's LDS
+        constexpr uint32_t IMG_OFF = STEM == 2 ? uint32_t(ST_X3_OFF) : uint32_t(lds_xch);
+        auto frag_base = [&](int tile) -> uint32_t {
             int P = tile * 8 + q;
             if (P >= ST_PER) P = ST_PER - 1;
             const int ph = P / ST_P1W, pw = P - ph * ST_P1W;
-            return reinterpret_cast<const uint32_t*>(img + (2 * (2 * ph + dy) + sh) * ST_PITCH + 2 * (2 * pw + dx));
+            return IMG_OFF + 2 * uint32_t((2 * (2 * ph + dy) + sh) * ST_PITCH + 2 * (2 * pw + dx));
         };
-        auto load_frags = [&](const uint32_t* base, bf16x8 (&a)[NP][4]) {
+        // One address register per (plane, pair of k-steps): a k-step is two image rows = 4 ST_PITCH bytes on, so the four dwords
+        // of both steps lie within the 1020-byte reach of ds_read2_b32's offsets.  The empty asm keeps the compiler from folding
+        // the plane / row constants back into one base, which costs it a v_add_u32 per ds_read2_b32 (16 per tile instead of 4).
+        static_assert(4 * ST_PITCH + 12 <= 1020, "both k-steps of a pair within ds_read2_b32's reach");
+        auto load_frags = [&](uint32_t base, bf16x8 (&a)[NP][4]) {
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-                for (int st = 0; st < 4; ++st) {
-                    const uint32_t* p = base + pl * (ST_ROWS * ST_PITCH / 2) + st * ST_PITCH;   // +2 image rows per step = ST_PITCH dwords
-                    union { uint32_t u[4]; bf16x8 v; } t;
-                    t.u[0] = p[0]; t.u[1] = p[1]; t.u[2] = p[2]; t.u[3] = p[3];
-                    a[pl][st] = t.v;
+                for (int sp = 0; sp < 2; ++sp) {
+                    using lds_u32 = const __attribute__((address_space(3))) uint32_t;
+                    lds_u32* p = (lds_u32*)(smem + (base + pl * (ST_ROWS * ST_PITCH * 2) + sp * (8 * ST_PITCH)));
+                    asm("" : "+v"(p));
+#pragma unroll
+                    for (int s2 = 0; s2 < 2; ++s2) {
+                        union { uint32_t u[4]; bf16x8 v; } t;
+                        t.u[0] = p[s2 * ST_PITCH]; t.u[1] = p[s2 * ST_PITCH + 1];
+                        t.u[2] = p[s2 * ST_PITCH + 2]; t.u[3] = p[s2 * ST_PITCH + 3];
+                        a[pl][2 * sp + s2] = t.v;
+                    }
                 }
         };
         auto mma = [&](const bf16x8 (&a)[NP][4], f32x16& c) {
@@ -1448,7 +1483,8 @@ int launch_featurize(const cough_featurizer* f, const float* d_wav, long long wa
                    : p.contrast == FEAT_CONTRAST_STFT        ? contrast_peaks(d_workspace, n_clips)
                                                              : gen_peaks(d_workspace);
     const int rows = f->cfg.use_mfcc ? (f->cfg.use_delta_delta ? 1 : 0) : 2;   // kernel row selector
-    hipLaunchKernelGGL(kernel, dim3(n_clips), dim3(THREADS), p.lds, stream, d_wav, wav_stride, d_feat, f->nfeat, f->d_tables, norm,
+    const size_t lds = full ? p.lds : shipped_lds_bytes(stem ? (stem->x3 ? 2 : 1) : 0);   // p.lds, plus the wide stem images
+    hipLaunchKernelGGL(kernel, dim3(n_clips), dim3(THREADS), lds, stream, d_wav, wav_stride, d_feat, f->nfeat, f->d_tables, norm,
                        f->cfg.pre_emphasis_coef, rows, f->cfg.use_pcen, stem ? *stem : StemFuse{}, bank, bank.dct, peaks);
     COUGH_HIP_CHECK(hipGetLastError());
     // rows [nbase, nfeat): from the un-emphasised signal (preprocessing.py:476-478)
