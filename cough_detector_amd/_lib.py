@@ -3,7 +3,8 @@
 ``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``) and
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``)
 and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``) and
-``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``).
+``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``)
+and ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``: the training steps on soft targets; ``load_soft`` / ``check_soft``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -90,6 +91,11 @@ MAX_THRESHOLDS = 1024    # COUGH_MAX_THRESHOLDS
 DRAWS_LIB_PATH = os.environ.get("COUGH_AMD_DRAWS_LIB") or os.path.join(HERE, "libcough_amd_draws.so")
 DRAWS_SYMBOLS = ("cough_draws_abi_version", "cough_draws_last_error", "cough_draw_batch",
                  "cough_augment_rows_drawn_workspace_bytes", "cough_augment_rows_drawn")
+
+# every symbol include/cough_amd_soft.h declares (the companion library of the soft-target steps and the batch MixUp)
+SOFT_LIB_PATH = os.environ.get("COUGH_AMD_SOFT_LIB") or os.path.join(HERE, "libcough_amd_soft.so")
+SOFT_SYMBOLS = ("cough_soft_abi_version", "cough_soft_last_error", "cough_train_forward_backward_soft",
+                "cough_train_small_forward_backward_soft", "cough_train_std_forward_backward_soft", "cough_mix_batch")
 
 
 MAX_CONTRAST_BANDS = 16
@@ -374,6 +380,38 @@ def load_draws() -> C.CDLL:
     return _draws_lib
 
 
+_soft_lib = None
+
+
+def load_soft() -> C.CDLL:
+    """Load (once) and type the companion library of the soft-target steps; raise loudly if it is not built."""
+    global _soft_lib
+    if _soft_lib is not None:
+        return _soft_lib
+    with _lock:
+        if _soft_lib is not None:
+            return _soft_lib
+        if not os.path.exists(SOFT_LIB_PATH):
+            raise RuntimeError(
+                f"{SOFT_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(SOFT_LIB_PATH)
+        vp, ll, i, f, ull = C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_ulonglong
+        lib.cough_soft_abi_version.restype = i
+        lib.cough_soft_last_error.restype = C.c_char_p
+        # the argument lists of the v5 steps, with the soft targets where the class indices were
+        lib.cough_train_forward_backward_soft.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, vp, vp, vp, vp, f, f, vp,
+                                                          vp, vp, vp, C.c_size_t, vp]
+        lib.cough_train_small_forward_backward_soft.argtypes = lib.cough_train_forward_backward_soft.argtypes
+        lib.cough_train_std_forward_backward_soft.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, f, vp, vp, vp, vp, f,
+                                                              f, vp, vp, vp, vp, C.c_size_t, vp]
+        lib.cough_mix_batch.argtypes = [vp, vp, vp, vp, i, ll, vp, vp, vp]
+        if lib.cough_soft_abi_version() != 1:
+            raise RuntimeError("libcough_amd_soft.so ABI version mismatch; rebuild it")
+        _soft_lib = lib
+    return _soft_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -408,6 +446,12 @@ def check_draws(status: int, what: str) -> None:
     """``check`` for a call into the draws library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_draws().cough_draws_last_error().decode("utf-8", "replace"))
+
+
+def check_soft(status: int, what: str) -> None:
+    """``check`` for a call into the soft-target library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_soft().cough_soft_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:

@@ -402,6 +402,42 @@ def _mix(x1: torch.Tensor, x2: torch.Tensor, lam: np.ndarray, index: Optional[to
     return out.to(x1.device)
 
 
+def mix_coefficients(lam) -> np.ndarray:
+    """(B, 2) float32 ``(lam, 1 - lam)``, each formed in float64 and then rounded: the coefficients ``_mix`` hands to
+    ``cough_mix_rows`` and ``mix_batch_rows`` expects."""
+    lam64 = np.asarray(lam, dtype=np.float64).reshape(-1)
+    return np.stack([lam64, 1.0 - lam64], axis=1).astype(np.float32)
+
+
+def mix_batch_rows(x: torch.Tensor, labels: torch.Tensor, perm: torch.Tensor,
+                   coef: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MixUp of a device batch with a permutation of itself in ONE launch (``cough_mix_batch`` of
+    ``libcough_amd_soft.so``): ``x`` (B, ...) float32, ``labels`` (B,) int64, ``perm`` (B,) int32, ``coef`` (B, 2) float32
+    (``mix_coefficients``), all contiguous on the GPU.  Returns ``(mixed x, soft targets (B, 2) float32)``:
+    ``lam x[b] + (1 - lam) x[perm[b]]`` and the same mix of the one-hot labels, both bit-equal to what
+    ``MixUp.mix_batch(x, onehot(labels), perm)`` gives with the same λ.  A ``perm`` entry outside ``0..B-1`` leaves its
+    row as it is.  Nothing is read back."""
+    b = int(x.shape[0]) if x.dim() else 0
+    want = (("x", x, torch.float32, None), ("labels", labels, torch.int64, (b,)), ("perm", perm, torch.int32, (b,)),
+            ("coef", coef, torch.float32, (b, 2)))
+    for name, t, dtype, shape in want:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"mix_batch_rows: {name} must be a contiguous {dtype} tensor on {x.device}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise ValueError(f"mix_batch_rows: {name} must have shape {shape}, got {tuple(t.shape)}")
+    if b < 1 or x.numel() < b:
+        raise ValueError(f"mix_batch_rows: expected x (B, ...) with B >= 1 and at least one value per row, got {tuple(x.shape)}")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"mix_batch_rows: the tensors live on {x.device}; the kernel needs them on the GPU (there is "
+                           "no CPU fallback)")
+    out = torch.empty_like(x)
+    soft = torch.empty((b, 2), dtype=torch.float32, device=x.device)
+    _lib.check_soft(_lib.load_soft().cough_mix_batch(x.data_ptr(), labels.data_ptr(), perm.data_ptr(), coef.data_ptr(), b,
+                                                     x.numel() // b, out.data_ptr(), soft.data_ptr(),
+                                                     torch.cuda.current_stream(x.device).cuda_stream), "cough_mix_batch")
+    return out, soft
+
+
 class MixUp:
     def __init__(self, alpha: float = 0.2):
         self.alpha = alpha

@@ -1,12 +1,13 @@
 """Build libcough_amd.so and its companions libcough_amd_loop.so, libcough_amd_data.so, libcough_amd_segments.so,
-libcough_amd_score.so and libcough_amd_draws.so (HIP, gfx950 only) in-tree with hipcc.
+libcough_amd_score.so, libcough_amd_draws.so and libcough_amd_soft.so (HIP, gfx950 only) in-tree with hipcc.
 
 Every translation unit is compiled to an object file of its own (in parallel, cached under ``build/`` by the newest
 source / header time) and the objects are linked into the shared libraries: ``SOURCES`` into ``libcough_amd.so`` (the
 C-ABI of ``include/cough_amd.h``), ``LOOP_SOURCES`` into ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``),
 ``DATA_SOURCES`` into ``libcough_amd_data.so`` (``include/cough_amd_data.h``), ``SEGMENTS_SOURCES`` into
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``), ``SCORE_SOURCES`` into ``libcough_amd_score.so``
-(``include/cough_amd_score.h``), ``DRAWS_SOURCES`` into ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``).  The libraries are build products and stay out of git.
+(``include/cough_amd_score.h``), ``DRAWS_SOURCES`` into ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``), ``SOFT_SOURCES`` and the three training
+translation units compiled a second time with ``SOFT_FLAGS`` into ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``).  The libraries are build products and stay out of git.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
 from __future__ import annotations
@@ -40,6 +41,13 @@ SCORE_SOURCES = ("score.hip",)
 # the same terms; it compiles csrc/augment_kernel.h, the kernel augment.hip runs
 DRAWS_LIB = os.path.join(HERE, "libcough_amd_draws.so")
 DRAWS_SOURCES = ("draws.hip",)
+# the companion library of the soft-target training steps and the batch MixUp, on the same terms.  Its three steps are
+# the training translation units of libcough_amd.so compiled a second time: SOFT_FLAGS only selects which extern "C"
+# functions they emit (the *_forward_backward_soft entry points instead of the v5 ones), so the step code exists once
+SOFT_LIB = os.path.join(HERE, "libcough_amd_soft.so")
+SOFT_SOURCES = ("soft.hip",)
+SOFT_SHARED_SOURCES = ("train.hip", "train_small.hip", "train_std.hip")
+SOFT_FLAGS = ("-DCOUGH_SOFT_EXPORTS",)
 # -fno-slp-vectorize: left alone, -O3 packs adjacent f32 adds / multiplies of the FFT butterflies into v_pk_*_f32, which issue
 # slower than the two scalar operations they replace on gfx950 (same-box A/B: K1 -2.4 %, STFT stage -3.2 %, classifier unchanged;
 # profiles/r04_flag_ab.txt)
@@ -61,21 +69,21 @@ def _headers_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     deps += [os.path.join(HERE, "..", "include", h) for h in ("cough_amd.h", "cough_amd_loop.h", "cough_amd_data.h",
                                                                    "cough_amd_segments.h", "cough_amd_score.h",
-                                                                   "cough_amd_draws.h")]
+                                                                   "cough_amd_draws.h", "cough_amd_soft.h")]
     deps.append(os.path.abspath(__file__))   # the flags live here
     deps += [os.path.join(CSRC, m) for m in ("exports.map", "exports_loop.map", "exports_data.map", "exports_segments.map",
-                                             "exports_score.map", "exports_draws.map")]
+                                             "exports_score.map", "exports_draws.map", "exports_soft.map")]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB)
+    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB, SOFT_LIB)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t
                                        for s in SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                       + DRAWS_SOURCES)
+                                       + DRAWS_SOURCES + SOFT_SOURCES)
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB) -> str:
@@ -88,10 +96,11 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
     os.makedirs(objdir, exist_ok=True)
     hdr = _headers_mtime()
 
-    def compile_one(src: str) -> str:
-        s, o = os.path.join(CSRC, src), os.path.join(objdir, src.replace(".hip", ".o"))
+    def compile_one(job) -> str:
+        src, flags, suffix = job if isinstance(job, tuple) else (job, (), "")
+        s, o = os.path.join(CSRC, src), os.path.join(objdir, src.replace(".hip", suffix + ".o"))
         if force or not os.path.exists(o) or os.path.getmtime(o) < max(hdr, os.path.getmtime(s)):
-            cmd = [hipcc, *CFLAGS, *extra_flags, "-c", s, "-o", o]
+            cmd = [hipcc, *CFLAGS, *extra_flags, *flags, "-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)
@@ -106,7 +115,8 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
 
     variant = bool(extra_flags) or out != LIB
     sources = SOURCES if variant else (SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                      + DRAWS_SOURCES)
+                                      + DRAWS_SOURCES + SOFT_SOURCES
+                                      + tuple((src, SOFT_FLAGS, "_soft") for src in SOFT_SHARED_SOURCES))
     with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, sources))
     link(objs[:len(SOURCES)], "exports.map", out)
@@ -118,7 +128,9 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
         link(objs[data_end:segments_end], "exports_segments.map", SEGMENTS_LIB)
         score_end = segments_end + len(SCORE_SOURCES)
         link(objs[segments_end:score_end], "exports_score.map", SCORE_LIB)
-        link(objs[score_end:], "exports_draws.map", DRAWS_LIB)
+        draws_end = score_end + len(DRAWS_SOURCES)
+        link(objs[score_end:draws_end], "exports_draws.map", DRAWS_LIB)
+        link(objs[draws_end:], "exports_soft.map", SOFT_LIB)
     return out
 
 

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(NT) void epoch_meter_kernel(const float* __restrict
         }
         if (!batch_loss) {
             float lg[2], wn[2];
-            ce_terms(0, z0, z1, targets + b, class_w, lg, wn);
+            ce_terms(0, z0, z1, targets + b, nullptr, class_w, lg, wn);
             s += double(wn[0]);
             w += double(wn[1]);
         }

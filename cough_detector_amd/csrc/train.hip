@@ -495,6 +495,7 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
                                                        const float* __restrict__ fcb, const float* __restrict__ mask_in,
                                                        unsigned long long seed, unsigned long long offset, float p,
                                                        const long long* __restrict__ targets,
+                                                       const float* __restrict__ soft,
                                                        const float* __restrict__ class_w, float* __restrict__ logits,
                                                        float* __restrict__ dvec, float* __restrict__ mask,
                                                        float* __restrict__ mask_out, float* __restrict__ wnll) {
@@ -515,13 +516,14 @@ __global__ __launch_bounds__(128) void head_fwd_kernel(const float* __restrict__
     __syncthreads();
     if (c == 0) {
         const float z0 = (red[0][0] + red[1][0]) + fcb[0], z1 = (red[0][1] + red[1][1]) + fcb[1];
-        ce_terms(b, z0, z1, targets, class_w, logits, wnll);
+        ce_terms(b, z0, z1, targets, soft, class_w, logits, wnll);
     }
 }
 
 // one workgroup for the batch: loss, dlogits, dFC, and the gradient reaching every pixel of the last block's output
 __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int HW, const float* __restrict__ logits,
-                                                       const long long* __restrict__ targets, const float* __restrict__ wnll,
+                                                       const long long* __restrict__ targets, const float* __restrict__ soft,
+                                                       const float* __restrict__ class_w, const float* __restrict__ wnll,
                                                        const float* __restrict__ dvec, const float* __restrict__ mask, float p,
                                                        const float* __restrict__ fcw, const float* __restrict__ stem_stat,
                                                        float* __restrict__ loss, float* __restrict__ dl,
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int HW, const floa
     __syncthreads();
     const float inv_w = 1.0f / tot[1];
     for (int b = t; b < B; b += 256) {
-        const float2 d = clip_dlogits(logits, targets, b, wnll[2 * b + 1] * inv_w);
+        const float2 d = clip_dlogits(logits, targets, soft, class_w, b, wnll[2 * b + 1] * inv_w);
         dl[2 * b] = d.x;
         dl[2 * b + 1] = d.y;
     }
@@ -729,35 +731,24 @@ struct Step {
     }
 };
 
-}  // namespace
-}  // namespace cough
-
-extern "C" size_t cough_train_workspace_bytes(int n_clips, int height, int width) {
-    using namespace cough;
-    if (n_clips < 1 || height < 1 || width < 1) return 0;
+// The step behind cough_train_forward_backward (d_targets: class indices, d_soft null) and
+// cough_train_forward_backward_soft of libcough_amd_soft.so (d_soft: [B][2] class probabilities, d_targets null); fn names
+// the entry point in the messages.  The two differ in what the two head kernels read, nowhere else.
+int train_step(const char* fn, const float* d_x, int n_clips, int height, int width, const long long* d_targets,
+               const float* d_soft, const float* d_class_weights, const float* d_dropout_mask, unsigned long long seed,
+               unsigned long long offset, float p, const float* d_params, float* d_grads, float* d_running,
+               long long* d_num_batches, float momentum, float eps, float* d_loss, float* d_logits, float* d_mask_out,
+               void* d_workspace, size_t workspace_bytes, void* stream) {
+    COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL, "%s: bad shape (%d, %d, %d)", fn, n_clips, height,
+                  width);
     const TShapes s = make_tshapes(height, width);
-    if (s.P1h < 1 || s.P1w < 1) return 0;
-    return carve(nullptr, n_clips, s).total;
-}
-
-extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int height, int width,
-                                            const long long* d_targets, const float* d_class_weights,
-                                            const float* d_dropout_mask, unsigned long long seed,
-                                            unsigned long long offset, float p, const float* d_params, float* d_grads,
-                                            float* d_running, long long* d_num_batches, float momentum, float eps,
-                                            float* d_loss, float* d_logits, float* d_mask_out, void* d_workspace,
-                                            size_t workspace_bytes, void* stream) {
-    using namespace cough;
-    COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL,
-                  "cough_train_forward_backward: bad shape (%d, %d, %d)", n_clips, height, width);
-    const TShapes s = make_tshapes(height, width);
-    COUGH_REQUIRE(s.P1h >= 1 && s.P1w >= 1, COUGH_EINVAL,
-                  "cough_train_forward_backward: input %dx%d too small for the network", height, width);
+    COUGH_REQUIRE(s.P1h >= 1 && s.P1w >= 1, COUGH_EINVAL, "%s: input %dx%d too small for the network", fn, height, width);
     for (int i = 0; i < NCONV; ++i)
         COUGH_REQUIRE((long long)n_clips * s.oh[i] * s.ow[i] > 1, COUGH_EINVAL,
-                      "cough_train_forward_backward: BatchNorm %d sees one value per channel (batch statistics need more)", i);
+                      "%s: BatchNorm %d sees one value per channel (batch statistics need more)", fn, i);
     const TWs w = carve(static_cast<char*>(d_workspace), n_clips, s);
-    if (const int rc = check_step_args(__func__, {d_x, d_targets, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
+    const void* d_y = d_soft ? static_cast<const void*>(d_soft) : d_targets;
+    if (const int rc = check_step_args(fn, {d_x, d_y, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
                                                   d_workspace},
                                        {p}, momentum, eps, d_workspace, workspace_bytes, w.total);
         rc != COUGH_OK)
@@ -797,12 +788,12 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
     }
     const int HW = s.oh[5] * s.ow[5];
     hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(HEAD_C), 0, st, w.blk[1].out, HW, d_params + L.fc_w, d_params + L.fc_b,
-                       d_dropout_mask, seed, offset, p, d_targets, d_class_weights, d_logits, w.dvec, w.mask, d_mask_out,
-                       w.wnll);
+                       d_dropout_mask, seed, offset, p, d_targets, d_soft, d_class_weights, d_logits, w.dvec, w.mask,
+                       d_mask_out, w.wnll);
 
     // ---- backward
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(1), dim3(256), 0, st, B, HW, d_logits, d_targets, w.wnll, w.dvec, w.mask, p,
-                       d_params + L.fc_w, w.stat[0], d_loss, w.dl, d_grads + L.fc_w, d_grads + L.fc_b, w.dgap);
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(1), dim3(256), 0, st, B, HW, d_logits, d_targets, d_soft, d_class_weights, w.wnll,
+                       w.dvec, w.mask, p, d_params + L.fc_w, w.stat[0], d_loss, w.dl, d_grads + L.fc_w, d_grads + L.fc_b, w.dgap);
     for (int k = 1; k >= 0; --k) {
         const int c1 = 1 + 3 * k, c2 = c1 + 1, sk = c1 + 2;
         const TWs::Blk& q = w.blk[k];
@@ -833,6 +824,45 @@ extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int h
     return COUGH_OK;
 }
 
+}  // namespace
+}  // namespace cough
+
+#ifdef COUGH_SOFT_EXPORTS   // the second compilation of this file, for libcough_amd_soft.so: the soft entry point alone
+#include "../../include/cough_amd_soft.h"
+
+extern "C" int cough_train_forward_backward_soft(const float* d_x, int n_clips, int height, int width,
+                                                 const float* d_soft_targets, const float* d_class_weights,
+                                                 const float* d_dropout_mask, unsigned long long seed,
+                                                 unsigned long long offset, float p, const float* d_params,
+                                                 float* d_grads, float* d_running, long long* d_num_batches,
+                                                 float momentum, float eps, float* d_loss, float* d_logits,
+                                                 float* d_mask_out, void* d_workspace, size_t workspace_bytes,
+                                                 void* stream) {
+    return cough::train_step(__func__, d_x, n_clips, height, width, nullptr, d_soft_targets, d_class_weights, d_dropout_mask,
+                             seed, offset, p, d_params, d_grads, d_running, d_num_batches, momentum, eps, d_loss, d_logits,
+                             d_mask_out, d_workspace, workspace_bytes, stream);
+}
+#else
+extern "C" size_t cough_train_workspace_bytes(int n_clips, int height, int width) {
+    using namespace cough;
+    if (n_clips < 1 || height < 1 || width < 1) return 0;
+    const TShapes s = make_tshapes(height, width);
+    if (s.P1h < 1 || s.P1w < 1) return 0;
+    return carve(nullptr, n_clips, s).total;
+}
+
+extern "C" int cough_train_forward_backward(const float* d_x, int n_clips, int height, int width,
+                                            const long long* d_targets, const float* d_class_weights,
+                                            const float* d_dropout_mask, unsigned long long seed,
+                                            unsigned long long offset, float p, const float* d_params, float* d_grads,
+                                            float* d_running, long long* d_num_batches, float momentum, float eps,
+                                            float* d_loss, float* d_logits, float* d_mask_out, void* d_workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return cough::train_step(__func__, d_x, n_clips, height, width, d_targets, nullptr, d_class_weights, d_dropout_mask, seed,
+                             offset, p, d_params, d_grads, d_running, d_num_batches, momentum, eps, d_loss, d_logits,
+                             d_mask_out, d_workspace, workspace_bytes, stream);
+}
+
 extern "C" int cough_adamw_step(float* d_params, float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, long long n,
                                 float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                                 double bias_correction1, double bias_correction2, float* d_total_norm, void* stream) {
@@ -855,3 +885,4 @@ extern "C" int cough_adamw_step(float* d_params, float* d_grads, float* d_exp_av
     COUGH_HIP_CHECK(hipGetLastError());
     return COUGH_OK;
 }
+#endif

@@ -138,11 +138,22 @@ __device__ __forceinline__ float dropout_keep(int u, int b, unsigned long long s
     return (float(v >> 8) * (1.0f / 16777216.0f) >= p) ? 1.f : 0.f;
 }
 
-// clip b's logits and weighted CE terms: wnll[2b] = w_y (logsumexp(z) - z_y), wnll[2b + 1] = w_y
-__device__ __forceinline__ void ce_terms(int b, float z0, float z1, const long long* targets, const float* class_w,
-                                         float* logits, float* wnll) {
+// clip b's logits and weighted CE terms: wnll[2b] = w_y (logsumexp(z) - z_y), wnll[2b + 1] = w_y.  With soft targets
+// (soft != nullptr: [B][2] class probabilities, torch's F.cross_entropy(z, y, weight=w) for a floating y; targets is then
+// not read) wnll[2b] = -(w0 y0 lp0 + w1 y1 lp1) with lp_c = z_c - logsumexp(z), and wnll[2b + 1] = 1: the batch's loss
+// divides by B, not by the sum of the weights.  Rows need not sum to 1; a NaN in a row gives a NaN loss.
+__device__ __forceinline__ void ce_terms(int b, float z0, float z1, const long long* targets, const float* soft,
+                                         const float* class_w, float* logits, float* wnll) {
     logits[2 * b] = z0;
     logits[2 * b + 1] = z1;
+    if (soft) {
+        const float mx = fmaxf(z0, z1);
+        const float lse = mx + logf(expf(z0 - mx) + expf(z1 - mx));
+        const float a0 = (class_w ? class_w[0] : 1.f) * soft[2 * b], a1 = (class_w ? class_w[1] : 1.f) * soft[2 * b + 1];
+        wnll[2 * b] = -(a0 * (z0 - lse) + a1 * (z1 - lse));
+        wnll[2 * b + 1] = 1.f;
+        return;
+    }
     const long long y = targets[b];
     if (y == 0 || y == 1) {
         const float mx = fmaxf(z0, z1);
@@ -156,11 +167,19 @@ __device__ __forceinline__ void ce_terms(int b, float z0, float z1, const long l
     }
 }
 
-// dlogits of clip b: k (the clip's CE weight over the batch's total, formed by the caller) * (softmax(z) - onehot(y))
-__device__ __forceinline__ float2 clip_dlogits(const float* logits, const long long* targets, int b, float k) {
+// dlogits of clip b: k (the clip's CE weight over the batch's total, formed by the caller) * (softmax(z) - onehot(y)); with
+// soft targets k * (softmax(z) S - w_c y_c), S = w0 y0 + w1 y1 (k is then 1 / B).  The soft form multiplies e_c by inv * S
+// so that a one-hot row without class weights (S = 1) is the hard expression operation by operation.
+__device__ __forceinline__ float2 clip_dlogits(const float* logits, const long long* targets, const float* soft,
+                                               const float* class_w, int b, float k) {
     const float z0 = logits[2 * b], z1 = logits[2 * b + 1];
     const float mx = fmaxf(z0, z1);
     const float e0 = expf(z0 - mx), e1 = expf(z1 - mx), inv = 1.0f / (e0 + e1);
+    if (soft) {
+        const float a0 = (class_w ? class_w[0] : 1.f) * soft[2 * b], a1 = (class_w ? class_w[1] : 1.f) * soft[2 * b + 1];
+        const float inv_s = inv * (a0 + a1);
+        return make_float2(k * (e0 * inv_s - a0), k * (e1 * inv_s - a1));
+    }
     const long long y = targets[b];
     return make_float2(k * (e0 * inv - (y == 0 ? 1.f : 0.f)), k * (e1 * inv - (y == 1 ? 1.f : 0.f)));
 }
@@ -187,13 +206,13 @@ __device__ __forceinline__ float mlp_hidden(const float* w1, const float* b1, co
 // the output Linear on the dropped-out hidden units hd, then clip b's logits and CE terms
 template <int HID>
 __device__ __forceinline__ void mlp_out(const float* w2, const float* b2, const float* hd, int b, const long long* targets,
-                                        const float* class_w, float* logits, float* wnll) {
+                                        const float* soft, const float* class_w, float* logits, float* wnll) {
     float z0 = b2[0], z1 = b2[1];
     for (int j = 0; j < HID; ++j) {
         z0 += w2[j] * hd[j];
         z1 += w2[HID + j] * hd[j];
     }
-    ce_terms(b, z0, z1, targets, class_w, logits, wnll);
+    ce_terms(b, z0, z1, targets, soft, class_w, logits, wnll);
 }
 
 // one block per clip: the batch's loss and CE weight (every block sums them in the same order, the CIN / 64 waves as a
@@ -202,6 +221,8 @@ __device__ __forceinline__ void mlp_out(const float* w2, const float* b2, const 
 template <int CIN, int HID, int MLD, int MOFF>
 __global__ __launch_bounds__(CIN) void mlp_head_bwd_kernel(int B, int HW, const float* __restrict__ logits,
                                                            const long long* __restrict__ targets,
+                                                           const float* __restrict__ soft,
+                                                           const float* __restrict__ class_w,
                                                            const float* __restrict__ wnll, const float* __restrict__ hr,
                                                            const float* __restrict__ mask, float p,
                                                            const float* __restrict__ w1, const float* __restrict__ w2,
@@ -223,7 +244,7 @@ __global__ __launch_bounds__(CIN) void mlp_head_bwd_kernel(int B, int HW, const 
         const bool finite = isfinite(st0[0]) && isfinite(st0[C0]);
         loss[0] = finite ? tot / totw : __builtin_nanf("");
     }
-    const float2 d = clip_dlogits(logits, targets, b, wnll[2 * b + 1] / totw);
+    const float2 d = clip_dlogits(logits, targets, soft, class_w, b, wnll[2 * b + 1] / totw);
     if (t == 0) { dl[2 * b] = d.x; dl[2 * b + 1] = d.y; }
     const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;
     if (t < HID) {

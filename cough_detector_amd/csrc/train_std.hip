@@ -452,6 +452,7 @@ __global__ __launch_bounds__(NT) void wgrad0_kernel(BnSrc a, const float* __rest
 __global__ __launch_bounds__(NT) void mlp_head_fwd_kernel(const float* __restrict__ a3, int HW, const float* __restrict__ prm,
                                                           const float* __restrict__ mask, float p_fc,
                                                           const long long* __restrict__ targets,
+                                                          const float* __restrict__ soft,
                                                           const float* __restrict__ class_w, float* __restrict__ logits,
                                                           float* __restrict__ gap, float* __restrict__ hr,
                                                           float* __restrict__ wnll) {
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(NT) void mlp_head_fwd_kernel(const float* __restric
         shd[c] = hv * (mask[(long long)b * MASK_W + MOFF[NB] + c] * scale);
     }
     __syncthreads();
-    if (c == 0) mlp_out<HID>(prm + FC3_W, prm + FC3_B, shd, b, targets, class_w, logits, wnll);
+    if (c == 0) mlp_out<HID>(prm + FC3_W, prm + FC3_B, shd, b, targets, soft, class_w, logits, wnll);
 }
 
 // ------------------------------------------------------------------------------------------ workspace
@@ -550,35 +551,25 @@ bool trainable(int B, int H, int W) {
     return (long long)B * H * W <= (1LL << 27);
 }
 
-}  // namespace
-}  // namespace cough
-
-extern "C" size_t cough_train_std_workspace_bytes(int n_clips, int height, int width) {
-    using namespace cough;
-    if (!trainable(n_clips, height, width)) return 0;
-    return carve(nullptr, n_clips, make_shapes(n_clips, height, width)).total;
-}
-
-extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, int height, int width,
-                                                const long long* d_targets, const float* d_class_weights,
-                                                const float* d_dropout_mask, unsigned long long seed,
-                                                unsigned long long offset, float p_block, float p_fc,
-                                                const float* d_params, float* d_grads, float* d_running,
-                                                long long* d_num_batches, float momentum, float eps, float* d_loss,
-                                                float* d_logits, float* d_mask_out, void* d_workspace,
-                                                size_t workspace_bytes, void* stream) {
-    using namespace cough;
-    COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL,
-                  "cough_train_std_forward_backward: bad shape (%d, %d, %d)", n_clips, height, width);
-    COUGH_REQUIRE(height >= 16 && width >= 16, COUGH_EINVAL,
-                  "cough_train_std_forward_backward: input %dx%d too small for the network (four 2x2 pools)", height,
+// The step behind cough_train_std_forward_backward (d_targets: class indices, d_soft null) and
+// cough_train_std_forward_backward_soft of libcough_amd_soft.so (d_soft: [B][2] class probabilities, d_targets null); fn
+// names the entry point in the messages.  The two differ in what the two head kernels read, nowhere else.
+int train_step(const char* fn, const float* d_x, int n_clips, int height, int width, const long long* d_targets,
+               const float* d_soft, const float* d_class_weights, const float* d_dropout_mask, unsigned long long seed,
+               unsigned long long offset, float p_block, float p_fc, const float* d_params, float* d_grads, float* d_running,
+               long long* d_num_batches, float momentum, float eps, float* d_loss, float* d_logits, float* d_mask_out,
+               void* d_workspace, size_t workspace_bytes, void* stream) {
+    COUGH_REQUIRE(n_clips >= 1 && height >= 1 && width >= 1, COUGH_EINVAL, "%s: bad shape (%d, %d, %d)", fn, n_clips, height,
                   width);
-    COUGH_REQUIRE(trainable(n_clips, height, width), COUGH_EINVAL,
-                  "cough_train_std_forward_backward: batch of %d images of %dx%d too large", n_clips, height, width);
+    COUGH_REQUIRE(height >= 16 && width >= 16, COUGH_EINVAL, "%s: input %dx%d too small for the network (four 2x2 pools)", fn,
+                  height, width);
+    COUGH_REQUIRE(trainable(n_clips, height, width), COUGH_EINVAL, "%s: batch of %d images of %dx%d too large", fn, n_clips,
+                  height, width);
     const int B = n_clips, H = height, W = width;
     const Shapes s = make_shapes(B, H, W);
     const Ws w = carve(static_cast<char*>(d_workspace), B, s);
-    if (const int rc = check_step_args(__func__, {d_x, d_targets, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
+    const void* d_y = d_soft ? static_cast<const void*>(d_soft) : d_targets;
+    if (const int rc = check_step_args(fn, {d_x, d_y, d_params, d_grads, d_running, d_num_batches, d_loss, d_logits,
                                                   d_workspace},
                                        {p_block, p_fc}, momentum, eps, d_workspace, workspace_bytes, w.total);
         rc != COUGH_OK)
@@ -614,13 +605,13 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
                            w.idx[k]);
     }
     const int HW4 = s.h[NB] * s.w[NB];
-    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3(B), dim3(NT), 0, st, w.a[NB - 1], HW4, prm, w.mask, p_fc, d_targets,
+    hipLaunchKernelGGL(mlp_head_fwd_kernel, dim3(B), dim3(NT), 0, st, w.a[NB - 1], HW4, prm, w.mask, p_fc, d_targets, d_soft,
                        d_class_weights, d_logits, w.gap, w.hr, w.wnll);
 
     // ---- backward
     hipLaunchKernelGGL((mlp_head_bwd_kernel<256, HID, MASK_W, MOFF[NB]>), dim3(B), dim3(NT), 0, st, B, HW4, d_logits,
-                       d_targets, w.wnll, w.hr, w.mask, p_fc, prm + FC0_W, prm + FC3_W, w.stat[0], CH[0], d_loss, w.dl, w.dh,
-                       w.dgap);
+                       d_targets, d_soft, d_class_weights, w.wnll, w.hr, w.mask, p_fc, prm + FC0_W, prm + FC3_W, w.stat[0],
+                       CH[0], d_loss, w.dl, w.dh, w.dgap);
     hipLaunchKernelGGL((mlp_fc_grad_kernel<256, HID, MASK_W, MOFF[NB]>), dim3((256 * HID + 3 * HID + 2 + 63) / 64), dim3(NT),
                        0, st, B, w.gap, w.hr, w.mask, p_fc, w.dl, w.dh, d_grads + FC0_W);
     for (int k = NB - 1; k >= 0; --k) {
@@ -652,3 +643,42 @@ extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, i
     COUGH_HIP_CHECK(hipGetLastError());
     return COUGH_OK;
 }
+
+}  // namespace
+}  // namespace cough
+
+#ifdef COUGH_SOFT_EXPORTS   // the second compilation of this file, for libcough_amd_soft.so: the soft entry point alone
+#include "../../include/cough_amd_soft.h"
+
+extern "C" int cough_train_std_forward_backward_soft(const float* d_x, int n_clips, int height, int width,
+                                                     const float* d_soft_targets, const float* d_class_weights,
+                                                     const float* d_dropout_mask, unsigned long long seed,
+                                                     unsigned long long offset, float p_block, float p_fc,
+                                                     const float* d_params, float* d_grads, float* d_running,
+                                                     long long* d_num_batches, float momentum, float eps, float* d_loss,
+                                                     float* d_logits, float* d_mask_out, void* d_workspace,
+                                                     size_t workspace_bytes, void* stream) {
+    return cough::train_step(__func__, d_x, n_clips, height, width, nullptr, d_soft_targets, d_class_weights, d_dropout_mask,
+                             seed, offset, p_block, p_fc, d_params, d_grads, d_running, d_num_batches, momentum, eps, d_loss,
+                             d_logits, d_mask_out, d_workspace, workspace_bytes, stream);
+}
+#else
+extern "C" size_t cough_train_std_workspace_bytes(int n_clips, int height, int width) {
+    using namespace cough;
+    if (!trainable(n_clips, height, width)) return 0;
+    return carve(nullptr, n_clips, make_shapes(n_clips, height, width)).total;
+}
+
+extern "C" int cough_train_std_forward_backward(const float* d_x, int n_clips, int height, int width,
+                                                const long long* d_targets, const float* d_class_weights,
+                                                const float* d_dropout_mask, unsigned long long seed,
+                                                unsigned long long offset, float p_block, float p_fc,
+                                                const float* d_params, float* d_grads, float* d_running,
+                                                long long* d_num_batches, float momentum, float eps, float* d_loss,
+                                                float* d_logits, float* d_mask_out, void* d_workspace,
+                                                size_t workspace_bytes, void* stream) {
+    return cough::train_step(__func__, d_x, n_clips, height, width, d_targets, nullptr, d_class_weights, d_dropout_mask, seed,
+                             offset, p_block, p_fc, d_params, d_grads, d_running, d_num_batches, momentum, eps, d_loss,
+                             d_logits, d_mask_out, d_workspace, workspace_bytes, stream);
+}
+#endif

@@ -26,6 +26,10 @@ augmentation could run (the reference's ``cache_spectrograms`` would silently fr
 epoch's indices and ONE seed per epoch, and a batch is four launches -- draw, augment the rows in place in the bank,
 ``cough_prepare_rows``, the featuriser -- plus ``cough_mask_images`` when there are masks.  The draws then have the
 reference's distributions but are not its random stream (the masks are drawn in float64, the reference's in float32).
+
+``mixup=MixUp(alpha)`` mixes every training batch with a permutation of itself after the features and the SpecAugment
+masks (one more launch, ``cough_mix_batch``), and the loader then yields ``(features, soft targets (B, 2) float32)``,
+which the trainers' soft-target steps, ``train_epoch_async`` and ``fit`` take as they are.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ from torch.utils.data import RandomSampler, WeightedRandomSampler
 from . import _lib
 from . import draws as _draws
 from ._native import cuda_device
-from .augmentation import AudioAugmentor, SpecAugment, mask_images
+from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
 
 CLASSES = ["non_cough", "cough"]
 _AUDIO_EXTENSIONS = {".wav", ".mp3", ".flac", ".ogg", ".webm"}      # dataset.py:86
@@ -61,6 +65,23 @@ def _upload(dev: torch.device, i64: np.ndarray, i32: np.ndarray) -> Tuple[torch.
     raw[n64 * 8:n64 * 8 + n32 * 4].view(np.int32)[:] = i32
     d = host.to(dev, non_blocking=True)
     return d[:n64 * 8].view(torch.int64), d[n64 * 8:n64 * 8 + n32 * 4].view(torch.int32)
+
+
+def mix_draws(seed: int, b: int, alpha: float) -> Tuple[np.ndarray, np.ndarray]:
+    """``(perm int32 (b,), lam float64 (b,))`` of a ``draws="device"`` batch: a permutation, then ``Beta(alpha, alpha)``
+    variates, from ``numpy.random.Generator(Philox(key=seed mod 2^64))`` on the host."""
+    rng = np.random.Generator(np.random.Philox(key=int(seed) & (2**64 - 1)))
+    perm = rng.permutation(b).astype(np.int32)
+    return perm, rng.beta(alpha, alpha, size=b)
+
+
+def _mix_words(n_before: int, perm: np.ndarray, lam: np.ndarray) -> Tuple[np.ndarray, int]:
+    """The int32 words a mixed batch adds to its upload behind ``n_before`` words: padding to an 8-byte boundary, the
+    (b, 2) float32 coefficients, the permutation.  Returns them and the coefficients' word offset."""
+    pad = n_before & 1
+    words = np.concatenate([np.zeros(pad, np.int32), mix_coefficients(lam).reshape(-1).view(np.int32),
+                            np.asarray(perm, dtype=np.int32)])
+    return words, n_before + pad
 
 
 class DeviceClipBank:
@@ -172,12 +193,14 @@ class DeviceClipBank:
 class BatchPlan:
     """The host draws of one batch: ``clips`` (a ``CoughAugClip`` per item, or None without waveform augmentation),
     ``gaussian`` (the ``torch.randn`` rows of ``noise="host"``, or None), ``seed`` (the device generator's) and ``masks``
-    (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it)."""
+    (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it); with a
+    ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None."""
 
-    __slots__ = ("clips", "gaussian", "seed", "masks")
+    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam")
 
-    def __init__(self, clips=None, gaussian=None, seed=0, masks=None):
+    def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None):
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
+        self.perm, self.lam = perm, lam
 
 
 class DeviceDataLoader:
@@ -197,13 +220,21 @@ class DeviceDataLoader:
     and its gaussian noise under ``(epoch_seed + k) mod 2^64`` in ``launch_batch_drawn``; no per-clip Python runs and
     nothing is copied from pageable memory.  These draws have the reference's distributions, not its random stream
     (float64 masks where the reference draws float32): a seeded run repeats itself, not a reference loader.  A loader that
-    has nothing to draw (no augmentor, or not training) behaves the same in both modes."""
+    has nothing to draw (no augmentor, or not training) behaves the same in both modes.
+    ``mixup``: a ``MixUp``; a training loader then mixes every batch with a permutation of itself, after the features
+    and the SpecAugment masks, in one launch (``cough_mix_batch``) and yields ``(features, soft targets (B, 2) float32)``
+    instead of class indices; a batch of 1 mixes with itself.  With ``draws="host"`` the loader draws, after the batch's
+    per-item draws (and its noise seed), ``torch.randperm(B)`` and then ``np.random.beta(alpha, alpha, size=B)``:
+    ``MixUp.mix_batch``'s order.  With ``draws="device"`` the permutation and the λ of batch k come from
+    ``mix_draws((epoch_seed + k) mod 2^64, B, alpha)``, a Philox-keyed numpy generator ON THE HOST: drawing Beta variates
+    and a permutation on the device is out of scope.  In both modes they travel with the batch's index upload through
+    pinned memory, and nothing is read back.  A validation loader (``is_training=False``) never mixes."""
 
     def __init__(self, bank: DeviceClipBank, preprocessor, batch_size: int = 32,
                  audio_augmentor: Optional[AudioAugmentor] = None, spec_augmentor: Optional[SpecAugment] = None,
                  is_training: bool = True, use_weighted_sampler: bool = True, drop_last: Optional[bool] = None,
                  generator: Optional[torch.Generator] = None, noise: str = "device", cache_features: bool = False,
-                 draws: str = "host"):
+                 draws: str = "host", mixup: Optional[MixUp] = None):
         if batch_size < 1:
             raise ValueError(f"DeviceDataLoader: batch_size={batch_size} must be positive")
         if noise not in ("device", "host"):
@@ -220,6 +251,10 @@ class DeviceDataLoader:
         self.generator, self.noise, self.cache_features = generator, noise, bool(cache_features)
         self._augments = self.is_training and audio_augmentor is not None
         self._masks = self.is_training and spec_augmentor is not None
+        if mixup is not None and not (float(mixup.alpha) > 0):
+            raise ValueError(f"DeviceDataLoader: MixUp's alpha = {mixup.alpha} must be positive")
+        self.mixup = mixup
+        self._mixes = self.is_training and mixup is not None
         if self.cache_features and self._augments:
             raise ValueError("DeviceDataLoader: cache_features=True with a waveform augmentor on a training loader would "
                              "freeze the first epoch's augmentation; drop one of the two")
@@ -254,7 +289,13 @@ class DeviceDataLoader:
 
     def draw_batch(self, indices: Sequence[int]) -> BatchPlan:
         """One batch's host draws, item by item in batch order (what ``CoughDataset.__getitem__`` draws per item)."""
-        plan = BatchPlan()
+        plan = self._draw_items(BatchPlan(), indices)
+        if self._mixes:
+            plan.perm = torch.randperm(len(indices))
+            plan.lam = np.random.beta(self.mixup.alpha, self.mixup.alpha, size=len(indices))
+        return plan
+
+    def _draw_items(self, plan: BatchPlan, indices: Sequence[int]) -> BatchPlan:
         if not (self._augments or self._masks):
             return plan
         lengths = [int(self.bank.lengths[i]) for i in indices]
@@ -329,9 +370,12 @@ class DeviceDataLoader:
         host_lens = bank.lengths.numpy()[idx]
         row_len = int(host_lens.max())
         masks = self._mask_arrays(plan.masks) if plan.masks is not None and self._n_masks else np.zeros(0, np.int32)
+        words, mix_at = [host_lens, masks.reshape(-1)], 0
+        if plan.perm is not None:
+            mix, mix_at = _mix_words(b + masks.size, np.asarray(plan.perm), plan.lam)
+            words.append(mix)
         i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
-                                                bank.labels.numpy()[idx], idx]),
-                           np.concatenate([host_lens, masks.reshape(-1)]))
+                                                bank.labels.numpy()[idx], idx]), np.concatenate(words))
         targets = i64[2 * b:3 * b]
         if self.cache_features:
             if self._cache is None:
@@ -340,9 +384,19 @@ class DeviceDataLoader:
         else:
             feats = self._features(indices, plan, i64, i32[:b])
         if masks.size:
-            m = i32[b:].view(3, b, self._n_masks)
+            m = i32[b:b + masks.size].view(3, b, self._n_masks)
             mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
+        if plan.perm is not None:
+            return self._mix(feats, targets, i32, mix_at)
         return feats.unsqueeze(1), targets
+
+    def _mix(self, feats: torch.Tensor, targets: torch.Tensor, i32: torch.Tensor, at: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The batch mixed by ``cough_mix_batch``; its coefficients and permutation are the ``_mix_words`` at word ``at``
+        of the batch's upload."""
+        b = feats.shape[0]
+        coef = i32[at:at + 2 * b].view(torch.float32).view(b, 2)
+        mixed, soft = mix_batch_rows(feats.contiguous(), targets, i32[at + 2 * b:at + 3 * b], coef)
+        return mixed.unsqueeze(1), soft
 
     def launch_batch_drawn(self, indices: Sequence[int], seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
@@ -357,8 +411,13 @@ class DeviceDataLoader:
         idx = np.asarray(indices, dtype=np.int64)
         host_lens = bank.lengths.numpy()[idx]
         row_len = int(host_lens.max())
-        i64, lens = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
-                                                 bank.labels.numpy()[idx], idx]), host_lens)
+        words, mix_at = [host_lens], 0
+        if self._mixes:
+            mix, mix_at = _mix_words(b, *mix_draws(seed, b, self.mixup.alpha))
+            words.append(mix)
+        i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
+                                                bank.labels.numpy()[idx], idx]), np.concatenate(words))
+        lens = i32[:b]
         targets = i64[2 * b:3 * b]
         clips, masks = _draws.draw_batch(seed, lens, self.audio_augmentor if self._augments else None,
                                          self.spec_augmentor if self._n_masks else None, self.feature_shape())
@@ -378,12 +437,14 @@ class DeviceDataLoader:
             feats = pre.featurize_batch(seg, normalize=False)
         if masks is not None:
             mask_images(feats, feats, masks[0], masks[1], masks[2], self._n_masks)
+        if self._mixes:
+            return self._mix(feats, targets, i32, mix_at)
         return feats.unsqueeze(1), targets
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         indices = self.epoch_indices()
         stop = len(self) * self.batch_size if self.drop_last else len(indices)
-        drawn = self.draws == "device" and (self._augments or self._masks)
+        drawn = self.draws == "device" and (self._augments or self._masks or self._mixes)
         if drawn:
             self.last_epoch_seed = int(torch.randint(0, 2**62, (1,), generator=self.generator).item())
         for k, lo in enumerate(range(0, stop, self.batch_size)):
@@ -396,14 +457,15 @@ class DeviceDataLoader:
 
 def create_data_loaders(train_bank: DeviceClipBank, val_bank: DeviceClipBank, preprocessor, batch_size: int = 32,
                         use_weighted_sampler: bool = True, audio_augmentor: Optional[AudioAugmentor] = None,
-                        spec_augmentor: Optional[SpecAugment] = None, **kw) -> Tuple[DeviceDataLoader, DeviceDataLoader]:
+                        spec_augmentor: Optional[SpecAugment] = None, mixup: Optional[MixUp] = None,
+                        **kw) -> Tuple[DeviceDataLoader, DeviceDataLoader]:
     """(train_loader, val_loader) as the reference's ``create_data_loaders`` (dataset.py:368-418): the training loader
     samples with ``WeightedRandomSampler`` (or shuffles), augments and drops the last ragged batch; the validation
-    loader is sequential, unaugmented and keeps it.  ``kw`` goes to the training loader (``generator``, ``noise``,
+    loader is sequential, unaugmented and keeps it.  ``mixup`` goes to the training loader only.  ``kw`` goes to the training loader (``generator``, ``noise``,
     ``cache_features``, ``draws``); ``cache_features`` also to the validation loader."""
     train = DeviceDataLoader(train_bank, preprocessor, batch_size=batch_size, audio_augmentor=audio_augmentor,
                              spec_augmentor=spec_augmentor, is_training=True, use_weighted_sampler=use_weighted_sampler,
-                             **kw)
+                             mixup=mixup, **kw)
     val = DeviceDataLoader(val_bank, preprocessor, batch_size=batch_size, is_training=False,
                            cache_features=kw.get("cache_features", False))
     return train, val

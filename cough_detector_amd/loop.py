@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ._native import cuda_device
 from .model import CoughDetector, CoughDetectorResidual, CoughDetectorSmall
+from .training import soft_class
 
 CHECKPOINT_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict", "metrics", "config")
 _METER_FIELDS = ("n_batches", "total", "correct", "tp", "fp", "fn", "tn")
@@ -88,12 +89,22 @@ class EpochMeter:
         """One batch: ``logits`` (B, 2), ``targets`` (B,) class indices.  ``batch_loss`` (a 1-element float32 device
         tensor, e.g. the loss a trainer's ``step`` returned) is added as it is; without it the batch's
         ``CrossEntropyLoss(weight=class_weights)`` is computed by the kernel.  ``preds_out`` (B,) int64 device tensor,
-        optional, receives the predictions."""
+        optional, receives the predictions.  Soft ``targets`` (B, 2) floating are accepted with a ``batch_loss``: the
+        class index counted is their argmax (first of equal values), taken on the device.  Without a ``batch_loss``
+        they are refused: the meter's own loss is the class-index loss."""
         dev = self.device
         z = logits.detach().to(device=dev, dtype=torch.float32).contiguous()
         if z.dim() != 2 or z.shape[1] != 2 or z.shape[0] < 1:
             raise ValueError(f"EpochMeter.update: expected logits (B, 2) with B >= 1, got {tuple(logits.shape)}")
-        t = torch.as_tensor(targets).detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        t = torch.as_tensor(targets).detach()
+        if t.dim() == 2 and t.dtype.is_floating_point:
+            if tuple(t.shape) != (z.shape[0], 2):
+                raise ValueError(f"EpochMeter.update: soft targets {tuple(t.shape)} for {z.shape[0]} clips")
+            if batch_loss is None:
+                raise ValueError("EpochMeter.update: soft targets need the step's batch_loss (the meter computes the "
+                                 "class-index loss only)")
+            t = soft_class(t.to(dev))
+        t = t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
         if t.numel() != z.shape[0]:
             raise ValueError(f"EpochMeter.update: {t.numel()} targets for {z.shape[0]} clips")
         cw = loss = None

@@ -12,6 +12,12 @@ gradients (``p.grad``) and BatchNorm buffers views of flat device buffers that t
 ``model.state_dict()`` holds the trained state after every step and ``model.eval()(x)`` runs the inference kernels on it.
 ``model.train()(x)`` still refuses: training goes through the trainer.
 
+Targets come in two forms.  ``(B,)`` integer class indices take the entry points above.  ``(B, 2)`` floating class
+probabilities -- ``MixUp``'s mixed one-hot labels, smoothed labels, a teacher's probabilities -- take the same steps'
+``*_soft`` entry points of ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``): the same kernels with the soft-target
+loss of ``F.cross_entropy(outputs, probabilities, weight=class_weights)``, whose mean divides by the batch size B and not
+by the sum of the clips' class weights as the class-index loss does.
+
 Non-finite input gives a NaN loss; the step then leaves NaN gradients and parameters (as torch's own step does: the clip
 coefficient of a NaN norm does not rescue them).  The residual net trains with its shipped channels ``(32, 64, 128)``
 only, the standard net with ``channels=(32, 64, 128, 256)`` and ``fc_hidden=128``; ``create_trainer`` picks the trainer of a
@@ -143,7 +149,7 @@ class _FlatTrainer:
     _model_cls = None
     _name = ""
     _n_tensors = _n_params = _n_running = _n_bns = _mask_width = 0
-    _ws_fn = _fb_fn = ""
+    _ws_fn = _fb_fn = _soft_fn = ""         # _soft_fn: the step's entry point for soft targets (libcough_amd_soft.so)
 
     def __init__(self, model, lr: float = 1e-3, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
                  class_weights=None, max_norm: float = 1.0, seed: int = 0):
@@ -222,9 +228,19 @@ class _FlatTrainer:
             raise ValueError(f"expected inputs (B, 1, F, T), got {tuple(inputs.shape)}")
         x = inputs.detach().to(device=dev, dtype=torch.float32).contiguous()
         b, _, hgt, wid = x.shape
-        t = torch.as_tensor(targets).detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-        if t.numel() != b:
-            raise ValueError(f"targets: {t.numel()} values for a batch of {b}")
+        t = torch.as_tensor(targets).detach()
+        if t.dtype.is_floating_point:
+            # class probabilities; a floating (B,) would be truncated to class indices, so it is refused
+            if tuple(t.shape) != (b, 2):
+                raise ValueError(f"targets: floating targets are class probabilities of shape ({b}, 2), got "
+                                 f"{tuple(t.shape)}; class indices are integers of shape ({b},)")
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+        elif t.dtype.is_complex:
+            raise ValueError(f"targets: {t.dtype} targets")
+        else:
+            t = t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+            if t.numel() != b:
+                raise ValueError(f"targets: {t.numel()} values for a batch of {b}")
         mask = None
         if dropout_mask is not None:
             mask = torch.as_tensor(dropout_mask).detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -243,8 +259,9 @@ class _FlatTrainer:
 
     def forward_backward(self, inputs: torch.Tensor, targets: torch.Tensor, dropout_mask=None, mask_out=None):
         """The forward and backward half of ``step``: writes ``p.grad`` of every parameter (unclipped), the BN running
-        statistics and counters; returns ``(loss, logits)``.  ``mask_out`` (B, mask width) float32 device tensor,
-        optional, receives the keep mask used."""
+        statistics and counters; returns ``(loss, logits)``.  ``targets``: ``(B,)`` integer class indices, or ``(B, 2)``
+        floating class probabilities (the soft-target step; anything else raises ``ValueError`` before any launch).
+        ``mask_out`` (B, mask width) float32 device tensor, optional, receives the keep mask used."""
         x, t, mask = self._prepare(inputs, targets, dropout_mask)
         self.optimizer.bind_grads()          # after a torch-style zero_grad(set_to_none=True) on the module
         b, _, hgt, wid = x.shape
@@ -253,12 +270,15 @@ class _FlatTrainer:
         if mask is None:
             self._draws += 1
         dev = self.device
-        _lib.check(getattr(_lib.load(), self._fb_fn)(
+        soft = t.dtype == torch.float32
+        lib, check, fn = ((_lib.load_soft(), _lib.check_soft, self._soft_fn) if soft
+                          else (_lib.load(), _lib.check, self._fb_fn))
+        check(getattr(lib, fn)(
             x.data_ptr(), b, hgt, wid, t.data_ptr(), _ptr(self.class_weights), _ptr(mask), self.seed, offset, *ps,
             self._params.data_ptr(), self._grads.data_ptr(), self._running.data_ptr(), self._nbt.data_ptr(),
             self._momentum, self._bn_eps, self._loss.data_ptr(), self._logits.data_ptr(), _ptr(mask_out),
             self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
-            self._fb_fn)
+            fn)
         # the kernels wrote the parameters / buffers behind torch's back (no _version bump): drop the inference handles
         # so the next eval-mode call re-reads them
         self.model.invalidate()
@@ -278,12 +298,20 @@ class ResidualTrainer(_FlatTrainer):
     int64 class indices; ``dropout_mask`` (B, 128) of 0 / 1 keeps, or ``None`` for the device generator (Philox keyed by
     ``seed``, one new draw per step).  ``loss`` is a 0-d device tensor, ``logits`` the train-mode outputs; both are
     buffers of the trainer, overwritten by the next step at the same shape (read them, e.g. ``loss.item()``, first).
-    No host synchronisation; no allocation after the first step at a given (B, F, T)."""
+    No host synchronisation; no allocation after the first step at a given (B, F, T).
+
+    Soft targets: ``targets`` (B, 2) floating class probabilities (cast to float32) run ``cough_train_forward_backward_soft``.
+    Per clip ``l_b = -(w0 y_b0 lp_b0 + w1 y_b1 lp_b1)`` with ``lp = log_softmax(outputs)`` and ``w`` the class weights
+    (1 without), and ``loss = sum(l_b) / B``: the mean over the batch, NOT over the summed class weights as with class
+    indices, so with class weights a one-hot soft batch's loss is the class-index loss times ``sum(w_y) / B``.  Rows need
+    not sum to 1, an all-zero row contributes nothing, values are not validated (no synchronisation) and a NaN in a row
+    gives a NaN loss.  Without class weights, one-hot rows give the class-index step bit for bit."""
 
     _model_cls = CoughDetectorResidual
     _name = "ResidualTrainer"
     _n_tensors, _n_params, _n_running, _n_bns, _mask_width = 30, _lib.TRAIN_NUM_PARAMS, _lib.TRAIN_NUM_RUNNING, 7, 128
     _ws_fn, _fb_fn = "cough_train_workspace_bytes", "cough_train_forward_backward"
+    _soft_fn = "cough_train_forward_backward_soft"
 
     def _check(self, model) -> None:
         if tuple(model.channels) != SHIPPED_CHANNELS:
@@ -297,13 +325,16 @@ class ResidualTrainer(_FlatTrainer):
 class SmallTrainer(_FlatTrainer):
     """Trains a ``CoughDetectorSmall`` with the reference's ``train_epoch`` step (``csrc/train_small.hip``,
     ``cough_train_small_forward_backward``): the contract of ``ResidualTrainer``, with the dropout keep mask of the
-    hidden layer (``classifier[3]``) ``(B, 64)``.  Trainable shapes: F, T >= 8 and B * (F // 8) * (T // 8) > 1."""
+    hidden layer (``classifier[3]``) ``(B, 64)``.  Trainable shapes: F, T >= 8 and B * (F // 8) * (T // 8) > 1.
+    Soft targets (B, 2) floating run ``cough_train_small_forward_backward_soft`` under ``ResidualTrainer``'s soft contract:
+    the loss is the sum of the clips' terms over B, not over the summed class weights."""
 
     _model_cls = CoughDetectorSmall
     _name = "SmallTrainer"
     _n_tensors, _n_params, _n_running, _n_bns, _mask_width = (26, _lib.TRAIN_SMALL_NUM_PARAMS,
                                                               _lib.TRAIN_SMALL_NUM_RUNNING, 4, 64)
     _ws_fn, _fb_fn = "cough_train_small_workspace_bytes", "cough_train_small_forward_backward"
+    _soft_fn = "cough_train_small_forward_backward_soft"
 
     def _dropout_p(self) -> float:
         return float(self.model.classifier[3].p)
@@ -314,13 +345,16 @@ class StandardTrainer(_FlatTrainer):
     ``train_epoch`` step (``csrc/train_std.hip``, ``cough_train_std_forward_backward``): the contract of
     ``SmallTrainer``, with the dropout keep mask ``(B, 608)``: one Dropout2d keep per (clip, channel) of the four
     ConvBlocks (32 + 64 + 128 + 256 columns, in block order), then the 128 hidden units of ``fc[2]``.  The blocks'
-    Dropout2d layers share one p, the head has its own.  Trainable shapes: F >= 16 and T >= 16."""
+    Dropout2d layers share one p, the head has its own.  Trainable shapes: F >= 16 and T >= 16.
+    Soft targets (B, 2) floating run ``cough_train_std_forward_backward_soft`` under ``ResidualTrainer``'s soft contract:
+    the loss is the sum of the clips' terms over B, not over the summed class weights."""
 
     _model_cls = CoughDetector
     _name = "StandardTrainer"
     _n_tensors, _n_params, _n_running, _n_bns, _mask_width = (20, _lib.TRAIN_STD_NUM_PARAMS, _lib.TRAIN_STD_NUM_RUNNING,
                                                               4, 608)
     _ws_fn, _fb_fn = "cough_train_std_workspace_bytes", "cough_train_std_forward_backward"
+    _soft_fn = "cough_train_std_forward_backward_soft"
 
     def _check(self, model) -> None:
         chans = tuple(int(b.conv.out_channels) for b in model.conv_layers)
@@ -350,9 +384,16 @@ def create_trainer(model, **kwargs):
     raise TypeError(f"no HIP trainer for {type(model).__name__}")
 
 
+def soft_class(targets: torch.Tensor) -> torch.Tensor:
+    """The class index of (B, 2) soft targets: ``targets.argmax(1)`` by torch's first-of-equals rule (a tie is class 0),
+    computed where the targets live."""
+    return (targets[:, 1] > targets[:, 0]).to(torch.int64)
+
+
 def train_epoch(trainer: _FlatTrainer, train_loader: Iterable, epoch: int) -> Dict[str, float]:
     """The reference's ``train_epoch`` (``src/train.py:54-112``) on a ``ResidualTrainer``, a ``SmallTrainer``
-    (``create_trainer``) or a ``StandardTrainer``: ``{'loss', 'accuracy'}``, the mean batch loss and the percentage of train-mode predictions equal to the target."""
+    (``create_trainer``) or a ``StandardTrainer``: ``{'loss', 'accuracy'}``, the mean batch loss and the percentage of train-mode predictions equal to the target.
+    The target of a soft (B, 2) floating row is its ``argmax(1)``: the first of equal values, so a tie counts as class 0."""
     trainer.model.train()
     running_loss, correct, total, n_batches = 0.0, 0, 0, 0
     for inputs, targets in train_loader:
@@ -360,6 +401,9 @@ def train_epoch(trainer: _FlatTrainer, train_loader: Iterable, epoch: int) -> Di
         running_loss += loss.item()
         predicted = outputs.argmax(1)
         total += int(targets.shape[0])
-        correct += int(predicted.eq(torch.as_tensor(targets).to(outputs.device)).sum().item())
+        t = torch.as_tensor(targets).to(outputs.device)
+        if t.dim() == 2 and t.dtype.is_floating_point:
+            t = soft_class(t)
+        correct += int(predicted.eq(t).sum().item())
         n_batches += 1
     return {"loss": running_loss / max(n_batches, 1), "accuracy": 100.0 * correct / max(total, 1)}
