@@ -145,14 +145,22 @@ class CoughDetectorResidual(NativeModule):
 
     # ------------------------------------------------------------------ forward
     def effective_dtype(self, height: int = 90, width: int = 101) -> str:
-        """The arithmetic that actually runs for a ``(height, width)`` feature image.  The fused reduced-precision
-        kernels are compiled for the shipped ``channels=(32, 64, 128)`` (``cough_resnet_create``); any other tuple
-        goes through ``cough_resnet_create_ex`` onto the exact-f32 MFMA kernels, and the split-bf16 residual blocks
-        are compiled for the images the reference's own flags produce at 101 frames -- 90 rows (shipped; block inputs
-        22x25 and 11x13), 103 rows (constructor defaults: delta-delta on; 26x25 / 13x13), 110 rows (+ contrast and
-        centroid rows; 27x25 / 14x13), 91..98 rows (contrast rows on the shipped set) and 63..70 rows (use_mfcc=False, 64 rows + contrast rows)
-        -- another image size runs them in exact f32 as well.  Results are at least as
-        accurate as asked for; throughput is the f32 path's."""
+        """The accuracy class and throughput a ``(height, width)`` feature image gets: ``"bf16x3"`` / ``"bf16_approx"``
+        when every stage runs the fused kernels of that mode, ``"fp32"`` when the f32 MFMA kernels carry block 0.  The
+        fused reduced-precision kernels are compiled for the shipped ``channels=(32, 64, 128)``
+        (``cough_resnet_create``); any other tuple goes through ``cough_resnet_create_ex`` onto the exact-f32 MFMA
+        kernels, stem and head included.  The split-bf16 residual blocks are compiled for the images the reference's own
+        flags produce at 101 frames -- 90 rows (shipped; block inputs 22x25 and 11x13), 103 rows (constructor defaults:
+        delta-delta on; 26x25 / 13x13), 110 rows (+ contrast and centroid rows; 27x25 / 14x13), 91..98 rows (contrast
+        rows on the shipped set) and 63..70 rows (use_mfcc=False, 64 rows + contrast rows).
+
+        ``"fp32"`` for a ``bf16x3`` model with the shipped channels is NOT "every kernel in exact f32": the kernels are
+        picked per stage (``csrc/resnet.hip: forward_impl``; restated as ``plan()`` in ``tests/resnet_layer_ref.py``).
+        The stem is the split-bf16 kernel whenever the image has at most 11 264 pixels and fits its LDS image, and
+        block 1 is the fused split-bf16 kernel (with its head) whenever ITS input is one of the compiled 8..14 x 13
+        shapes, whatever ran block 0 -- e.g. 71..74, 83..86 and 99..102 rows at 99..102 frames, or 103..106 frames at a
+        compiled height.  What is guaranteed for such an image is split-bf16 accuracy or better at every stage (each
+        within the per-pixel budget of its kernel family) and no more than the f32 path's time."""
         if self.compute_dtype == "fp32":
             return self.compute_dtype
         if self.channels != (32, 64, 128):
@@ -173,9 +181,12 @@ class CoughDetectorResidual(NativeModule):
         if eff != self.compute_dtype and (height, width) not in self._warned_fallback:
             self._warned_fallback.add((height, width))
             why = (f"channels={self.channels}" if self.channels != (32, 64, 128) else f"a {height}x{width} feature image")
+            how = ("running the exact-f32 MFMA kernels instead (same or better accuracy"
+                   if self.channels != (32, 64, 128) else
+                   "the f32 MFMA kernels run every stage that has no kernel of that mode for it (each stage at "
+                   "split-bf16 accuracy or better")
             warnings.warn(f"CoughDetectorResidual: compute_dtype={self.compute_dtype!r} is not compiled for {why}; "
-                          f"running the exact-f32 MFMA kernels instead (same or better accuracy, several times slower). "
-                          f"See effective_dtype().", UserWarning, stacklevel=4)
+                          f"{how}, several times slower). See effective_dtype().", UserWarning, stacklevel=4)
 
     def _run(self, x: torch.Tensor, want_probs: bool):
         src_dev = x.device

@@ -207,8 +207,10 @@ int cough_resnet_create(cough_resnet** out, const cough_resnet_weights* w, int d
 /* The fused split-bf16 kernels of cough_resnet_create are compiled for every feature image the reference's own flags
  * produce at 99..102 frames -- 13 instantiations, selected by the stem's output height ((rows - 1) / 2 + 1) / 2:
  * 63..70 rows (use_mfcc = 0: 64 mel rows + contrast rows), 87..98 rows (shipped 90; + contrast rows) and 103..110 rows
- * (delta-delta; + contrast rows: the constructor's defaults); any other image size runs the exact-f32 kernels (same entry
- * points, same results or better).
+ * (delta-delta; + contrast rows: the constructor's defaults); for any other image size the kernels are picked per stage
+ * (same entry points): the f32 MFMA kernels for a block whose input has no instantiation, the split-bf16 stem for every
+ * image of at most 11 264 pixels, the fused split-bf16 block 1 whenever its own input is 8..14 x 13 -- split-bf16
+ * accuracy or better at every stage.
  *
  * The same for any `channels` tuple of CoughDetectorResidual.__init__ (/root/reference/src/model.py:216-247):
  * channels[0 .. n_blocks] = (stem out, block 0 out, ..., block n_blocks-1 out); blocks[i] holds res_blocks.i;
