@@ -4,7 +4,8 @@
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``)
 and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``) and
 ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``)
-and ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``: the training steps on soft targets; ``load_soft`` / ``check_soft``).
+and ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``: the training steps on soft targets; ``load_soft`` / ``check_soft``)
+and ``libcough_amd_warp.so`` (``include/cough_amd_warp.h``: speed perturbation; ``load_warp`` / ``check_warp``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -97,6 +98,12 @@ SOFT_LIB_PATH = os.environ.get("COUGH_AMD_SOFT_LIB") or os.path.join(HERE, "libc
 SOFT_SYMBOLS = ("cough_soft_abi_version", "cough_soft_last_error", "cough_train_forward_backward_soft",
                 "cough_train_small_forward_backward_soft", "cough_train_std_forward_backward_soft", "cough_mix_batch")
 
+# every symbol include/cough_amd_warp.h declares (the companion library of speed perturbation)
+WARP_LIB_PATH = os.environ.get("COUGH_AMD_WARP_LIB") or os.path.join(HERE, "libcough_amd_warp.so")
+WARP_SYMBOLS = ("cough_warp_abi_version", "cough_warp_last_error", "cough_warp_rows", "cough_draw_speed",
+                "cough_clear_shifts")
+WARP_MAX_RATE, WARP_MAX_RATIO = 1 << 20, 4   # COUGH_WARP_MAX_RATE / COUGH_WARP_MAX_RATIO
+
 
 MAX_CONTRAST_BANDS = 16
 TRAIN_NUM_PARAMS, TRAIN_NUM_RUNNING = 290370, 1216   # COUGH_TRAIN_NUM_PARAMS / COUGH_TRAIN_NUM_RUNNING
@@ -141,6 +148,11 @@ class CoughAugClip(C.Structure):
     """cough_aug_clip: one clip's draws of AudioAugmentor.augment."""
     _fields_ = [("shift", C.c_int), ("gain", C.c_float), ("gaussian", C.c_int), ("bank_index", C.c_int),
                 ("gaussian_snr_db", C.c_double), ("bank_snr_db", C.c_double), ("bank_start", C.c_longlong)]
+
+
+class CoughWarpPlan(C.Structure):
+    """cough_warp_plan: one row's time shift and rate pair."""
+    _fields_ = [("shift", C.c_int), ("orig", C.c_int), ("new_rate", C.c_int)]
 
 
 _lib = None
@@ -412,6 +424,34 @@ def load_soft() -> C.CDLL:
     return _soft_lib
 
 
+_warp_lib = None
+
+
+def load_warp() -> C.CDLL:
+    """Load (once) and type the companion library of speed perturbation; raise loudly if it is not built."""
+    global _warp_lib
+    if _warp_lib is not None:
+        return _warp_lib
+    with _lock:
+        if _warp_lib is not None:
+            return _warp_lib
+        if not os.path.exists(WARP_LIB_PATH):
+            raise RuntimeError(
+                f"{WARP_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(WARP_LIB_PATH)
+        vp, i, d, ull = C.c_void_p, C.c_int, C.c_double, C.c_ulonglong
+        lib.cough_warp_abi_version.restype = i
+        lib.cough_warp_last_error.restype = C.c_char_p
+        lib.cough_warp_rows.argtypes = [vp, vp, vp, i, vp, vp, i, vp, vp]
+        lib.cough_draw_speed.argtypes = [ull, i, vp, d, d, d, i, vp, vp, vp]
+        lib.cough_clear_shifts.argtypes = [vp, i, vp]
+        if lib.cough_warp_abi_version() != 1:
+            raise RuntimeError("libcough_amd_warp.so ABI version mismatch; rebuild it")
+        _warp_lib = lib
+    return _warp_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -452,6 +492,12 @@ def check_soft(status: int, what: str) -> None:
     """``check`` for a call into the soft-target library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_soft().cough_soft_last_error().decode("utf-8", "replace"))
+
+
+def check_warp(status: int, what: str) -> None:
+    """``check`` for a call into the speed-perturbation library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_warp().cough_warp_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:

@@ -13,6 +13,12 @@
   a Dataset that calls SpecAugment per item does, and applies them in one pass of ``cough_mask_images``.
 * ``MixUp`` (:334-369) and ``create_augmentation_pipeline`` (:372-398); the mixing runs in ``cough_mix_rows``.
 
+``AudioAugmentor(speed=True)`` makes ``speed_perturbation`` real (the reference disabled it: torchaudio's resampler
+needs a polyphase table of about 1 GB for a pair such as 15999 -> 16000).  ``cough_warp_rows``
+(``cough_detector_amd/warp.py``) evaluates the filter per tap instead, with the time shift fused into its read, and the
+rest of the chain then runs on the warped clip of ``n' = ceil(n * sample_rate / int(factor * sample_rate))`` samples.
+The default ``speed=False`` draws nothing for it and changes no result.
+
 Differences a caller can observe: results come back where the input lives, as float32.  ``pitch_shift`` draws its coin
 and semitones as the reference does and returns its input unchanged -- the reference's own result when sox is absent
 (its ``except`` branch); ``augment`` never calls it.  The noise bank decodes WAVE files only (``load_wave``); other files
@@ -30,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib, _tables
+from . import warp as _warp
 from ._native import cuda_device
 from .preprocessing import load_wave
 
@@ -136,9 +143,14 @@ def _repeated_length(entry_len: int, target_len: int) -> int:
 
 
 class AudioAugmentor:
-    def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5):
+    def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
+                 speed: bool = False, speed_range: Tuple[float, float] = (0.9, 1.1)):
         self.sample_rate = sample_rate
         self.p_augment = p_augment
+        self.speed = bool(speed)
+        self.speed_range = (float(speed_range[0]), float(speed_range[1]))
+        if self.speed:
+            _warp.check_speed_range(self.speed_range, sample_rate, "AudioAugmentor")
         self.noise_samples: List[torch.Tensor] = []      # (1, L) float32 on the host, as the reference keeps them
         self._bank_host = torch.zeros(0, dtype=torch.float32)
         self._bank_offsets: List[int] = []
@@ -215,6 +227,12 @@ class AudioAugmentor:
     def _draw_shift(self, n: int, shift_limit: float = _SHIFT_LIMIT) -> int:
         return int(n * random.uniform(-shift_limit, shift_limit)) if self._coin() else 0
 
+    def _draw_speed(self, speed_range=None) -> Optional[Tuple[int, int]]:
+        """speed_perturbation's draws: coin, factor; the rate pair of torchaudio's ``speed``."""
+        if not self._coin():
+            return None
+        return _warp.speed_rate_pair(random.uniform(*(speed_range or self.speed_range)), self.sample_rate)
+
     def _draw_gain(self, gain_range=_GAIN_RANGE) -> Optional[float]:
         return random.uniform(*gain_range) if self._coin() else None
 
@@ -230,11 +248,20 @@ class AudioAugmentor:
         return k, start, random.uniform(*snr_range)
 
     def draw_clip(self, n: int) -> _lib.CoughAugClip:
-        """One ``augment`` call's draws for a clip of ``n`` samples (reference :249-268)."""
+        """One ``augment`` call's draws for a clip of ``n`` samples (reference :249-268): ``draw_item``'s record."""
+        return self.draw_item(n)[0]
+
+    def draw_item(self, n: int) -> Tuple[_lib.CoughAugClip, Optional[Tuple[int, int]], int]:
+        """``(record, rate pair, n')`` of one ``augment`` call on a clip of ``n`` samples.  With ``speed=True`` the speed
+        step draws between the shift and the gain -- its place in the chain -- and the noise-bank step, which crops
+        ``n'`` samples, is drawn for the warped length ``n'``; the record's shift is the one drawn for ``n``.  The pair is
+        None (and ``n' = n``) when the step is switched off or its coin did not fire."""
         c = _lib.CoughAugClip(shift=0, gain=1.0, gaussian=0, bank_index=-1, gaussian_snr_db=0.0, bank_snr_db=0.0,
                               bank_start=0)
         c.shift = self._draw_shift(n)
-        gain = self._draw_gain()                                  # speed_perturbation draws nothing
+        pair = self._draw_speed() if self.speed else None         # speed=False: speed_perturbation draws nothing
+        n = n if pair is None else _warp.warped_length(n, *pair)
+        gain = self._draw_gain()
         if gain is not None:
             c.gain = gain
         snr = self._draw_gauss()
@@ -244,7 +271,7 @@ class AudioAugmentor:
             d = self._draw_bank(n)
             if d is not None:
                 c.bank_index, c.bank_start, c.bank_snr_db = d
-        return c
+        return c, pair, n
 
     def draw_batch(self, lengths: Sequence[int]) -> List[_lib.CoughAugClip]:
         """The draws of ``augment_batch``: ``draw_clip`` for each clip in order, as a Dataset calls ``augment`` per item."""
@@ -280,6 +307,27 @@ class AudioAugmentor:
                    "cough_augment_waveforms")
         return out.to(x.device)
 
+    def _run_warped(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
+                    pairs: Sequence[Optional[Tuple[int, int]]], gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
+        """``_run`` with the speed step: ``cough_warp_rows`` (shift and resampling; a row without a pair is copied), then
+        ``cough_augment_waveforms`` on the warped rows with the records' shifts zeroed and the lengths ``n'``.  Returns
+        (B, max n').  When no row has a pair the warp launch is skipped and the path is ``_run``'s."""
+        b, n = x.shape
+        lens = [int(v) for v in lengths] if lengths is not None else [n] * b
+        new_lens = [l if p is None else _warp.warped_length(l, *p) for l, p in zip(lens, pairs)]
+        width = max(new_lens, default=0)
+        if all(p is None for p in pairs):
+            return self._run(x, clips, lengths, gaussian, seed)[:, :width].contiguous()
+        dev = cuda_device()
+        src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        plans = _warp.plan_array([(c.shift,) + (p if p is not None else (1, 1)) for c, p in zip(clips, pairs)])
+        warped = _warp.warp_rows(src, (torch.arange(b, dtype=torch.int64) * n).to(dev),
+                                 torch.tensor(lens, dtype=torch.int32).to(dev), torch.from_numpy(plans).to(dev), width)
+        unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in clips]
+        for c in unshifted:
+            c.shift = 0
+        return self._run(warped, unshifted, new_lens, gaussian, seed).to(x.device)
+
     @staticmethod
     def _one_clip(waveform: torch.Tensor, who: str) -> None:
         if not isinstance(waveform, torch.Tensor) or not waveform.dtype.is_floating_point:
@@ -305,9 +353,19 @@ class AudioAugmentor:
         c.shift = int(waveform.shape[1] * random.uniform(-shift_limit, shift_limit))
         return waveform if c.shift == 0 else self._single(waveform, c)
 
-    def speed_perturbation(self, waveform: torch.Tensor, speed_range: Tuple[float, float] = (0.9, 1.1)) -> torch.Tensor:
-        """The identity, as in the reference (:107-117)."""
-        return waveform
+    def speed_perturbation(self, waveform: torch.Tensor, speed_range: Optional[Tuple[float, float]] = None) -> torch.Tensor:
+        """With ``speed=False`` the identity, as in the reference (:107-117), and no draw.  With ``speed=True`` what the
+        reference meant to run: coin, ``factor = random.uniform(*speed_range)`` (the augmentor's range by default), then
+        ``torchaudio.functional.speed``'s resampling by ``(int(factor * sample_rate), sample_rate)``: (1, n')."""
+        if not self.speed:
+            return waveform
+        if speed_range is not None:
+            _warp.check_speed_range(speed_range, self.sample_rate, "speed_perturbation")
+        pair = self._draw_speed(speed_range)
+        if pair is None:
+            return waveform
+        self._one_clip(waveform, "speed_perturbation")
+        return self._run_warped(waveform, [self._blank()], None, [pair], None, 0).to(waveform.dtype)
 
     def add_noise(self, waveform: torch.Tensor, snr_range: Tuple[float, float] = _BANK_SNR) -> torch.Tensor:
         self._one_clip(waveform, "add_noise")
@@ -347,18 +405,24 @@ class AudioAugmentor:
     def augment(self, waveform: torch.Tensor) -> torch.Tensor:
         """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
         self._one_clip(waveform, "augment")
-        c = self.draw_clip(waveform.shape[1])
+        c, pair, n_new = self.draw_item(waveform.shape[1])
+        if pair is not None:                                     # the speed step fired: (1, n')
+            gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
+            return self._run_warped(waveform, [c], None, [pair], gaussian, 0).to(waveform.dtype)
         if c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
             return waveform
         return self._single(waveform, c)
 
     def augment_batch(self, waveforms: torch.Tensor, lengths=None, noise: str = "device",
-                      seed: Optional[int] = None) -> torch.Tensor:
+                      seed: Optional[int] = None, return_lengths: bool = False):
         """``augment`` of every row of a (B, N) batch in ONE launch: clip b is its first ``lengths[b]`` samples (all N
         when ``lengths`` is None), gets its own draws (in row order, as a Dataset calls ``augment`` per item) and its tail
         is written as 0.  ``noise="device"``: the gaussian noise comes from the seeded counter-based generator on the GPU
         (``seed``: 64-bit; None draws one from torch's CPU generator); ``noise="host"``: ``torch.randn`` on the CPU
-        generator, one clip after the other, as the reference's ``randn_like``.  Returns (B, N) where the input lives."""
+        generator, one clip after the other, as the reference's ``randn_like``.  Returns (B, N) where the input lives.
+        With ``speed=True`` a clip whose speed step fired has ``n'`` samples instead of its ``n``: the result is
+        (B, max n'), and ``noise="host"`` draws ``randn(n')``.  ``return_lengths=True`` returns ``(result, lengths)``
+        with the clips' lengths after the chain as an int32 (B,) host tensor."""
         if noise not in ("device", "host"):
             raise ValueError(f"augment_batch: noise must be 'device' or 'host', got {noise!r}")
         if not isinstance(waveforms, torch.Tensor) or not waveforms.dtype.is_floating_point:
@@ -370,17 +434,29 @@ class AudioAugmentor:
             lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
             if len(lengths) != b or any(v < 1 or v > n for v in lengths):
                 raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
-        clips = self.draw_batch(lengths if lengths is not None else [n] * b)
+        if not self.speed:
+            clips = self.draw_batch(lengths if lengths is not None else [n] * b)
+            pairs, new_lens = None, list(lengths) if lengths is not None else [n] * b
+        else:
+            items = [self.draw_item(v) for v in (lengths if lengths is not None else [n] * b)]
+            clips, pairs, new_lens = [it[0] for it in items], [it[1] for it in items], [it[2] for it in items]
         gaussian = None
         if noise == "host":
-            gaussian = torch.zeros((b, n), dtype=torch.float32)
+            # rows of n' samples; the matrix is cut to (B, max n') below when a speed step fired
+            gaussian = torch.zeros((b, max(new_lens + [n])), dtype=torch.float32)
             for i, c in enumerate(clips):
                 if c.gaussian:
-                    li = lengths[i] if lengths is not None else n
-                    gaussian[i, :li] = torch.randn(li)
+                    gaussian[i, :new_lens[i]] = torch.randn(new_lens[i])
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
-        return self._run(waveforms, clips, lengths, gaussian, int(seed))
+        if pairs is None:
+            out = self._run(waveforms, clips, lengths, gaussian, int(seed))
+        else:
+            if gaussian is not None:
+                fired = any(p is not None for p in pairs)
+                gaussian = gaussian[:, :max(new_lens) if fired else n].contiguous()
+            out = self._run_warped(waveforms, clips, lengths, pairs, gaussian, int(seed))
+        return (out, torch.tensor(new_lens, dtype=torch.int32)) if return_lengths else out
 
 
 def _mix(x1: torch.Tensor, x2: torch.Tensor, lam: np.ndarray, index: Optional[torch.Tensor], who: str) -> torch.Tensor:
@@ -472,8 +548,10 @@ class MixUp:
 
 
 def create_augmentation_pipeline(sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
-                                 use_spec_augment: bool = True) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
-    """(AudioAugmentor, SpecAugment or None), reference :372-398."""
-    audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment)
+                                 use_spec_augment: bool = True, speed: bool = False,
+                                 speed_range: Tuple[float, float] = (0.9, 1.1)) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
+    """(AudioAugmentor, SpecAugment or None), reference :372-398; ``speed`` / ``speed_range`` go to the augmentor."""
+    audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment, speed=speed,
+                               speed_range=speed_range)
     spec_aug = SpecAugment(p=p_augment) if use_spec_augment else None
     return audio_aug, spec_aug

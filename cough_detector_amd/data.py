@@ -30,6 +30,13 @@ reference's distributions but are not its random stream (the masks are drawn in 
 ``mixup=MixUp(alpha)`` mixes every training batch with a permutation of itself after the features and the SpecAugment
 masks (one more launch, ``cough_mix_batch``), and the loader then yields ``(features, soft targets (B, 2) float32)``,
 which the trainers' soft-target steps, ``train_epoch_async`` and ``fit`` take as they are.
+
+An ``AudioAugmentor(speed=True)`` adds the speed step to a training batch (``cough_detector_amd/warp.py``): one more
+launch, ``cough_warp_rows``, reads the clips in place from the bank, shifts and resamples each by its own rate pair, and
+the rest of the chain and ``cough_prepare_rows`` then work on the warped rows and their new lengths ``n'``.  With
+``draws="host"`` the per-row plans and ``n'`` travel with the batch's pinned upload (a batch in which no speed coin
+fired runs the launches it ran before); with ``draws="device"`` ``cough_draw_speed`` draws them first, the output is as
+wide as the slowest factor can make the longest row, and nothing is read back.
 """
 from __future__ import annotations
 
@@ -44,6 +51,7 @@ from torch.utils.data import RandomSampler, WeightedRandomSampler
 
 from . import _lib
 from . import draws as _draws
+from . import warp as _warp
 from ._native import cuda_device
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
 
@@ -194,13 +202,20 @@ class BatchPlan:
     """The host draws of one batch: ``clips`` (a ``CoughAugClip`` per item, or None without waveform augmentation),
     ``gaussian`` (the ``torch.randn`` rows of ``noise="host"``, or None), ``seed`` (the device generator's) and ``masks``
     (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it); with a
-    ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None."""
+    ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None.  With an augmentor that
+    has ``speed=True``, ``pairs`` (per item the speed step's ``(orig, new)``, None when its coin did not fire) and
+    ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples."""
 
-    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam")
+    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths")
 
-    def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None):
+    def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None, pairs=None, new_lengths=None):
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
         self.perm, self.lam = perm, lam
+        self.pairs, self.new_lengths = pairs, new_lengths
+
+    def warps(self) -> bool:
+        """Whether a speed step fired in this batch."""
+        return self.pairs is not None and any(p is not None for p in self.pairs)
 
 
 class DeviceDataLoader:
@@ -300,16 +315,24 @@ class DeviceDataLoader:
             return plan
         lengths = [int(self.bank.lengths[i]) for i in indices]
         f, t = self.feature_shape()
+        speed = self._augments and self.audio_augmentor.speed
         if self._augments:
             plan.clips = []
+            if speed:
+                plan.pairs, plan.new_lengths = [], []
             if self.noise == "host":
-                plan.gaussian = torch.zeros((len(indices), max(lengths)), dtype=torch.float32, pin_memory=self._pinned())
+                aug = self.audio_augmentor
+                wide = _warp.drawn_width(max(lengths), aug.speed_range, aug.sample_rate) if speed else max(lengths)
+                plan.gaussian = torch.zeros((len(indices), wide), dtype=torch.float32, pin_memory=self._pinned())
         if self._masks:
             plan.masks = []
         for row, n in enumerate(lengths):
             if self._augments:
-                c = self.audio_augmentor.draw_clip(n)
+                c, pair, n = self.audio_augmentor.draw_item(n)       # n' from here on; n itself without a speed step
                 plan.clips.append(c)
+                if speed:
+                    plan.pairs.append(pair)
+                    plan.new_lengths.append(n)
                 if c.gaussian and plan.gaussian is not None:
                     plan.gaussian[row, :n] = torch.randn(n)
             if self._masks:
@@ -331,20 +354,35 @@ class DeviceDataLoader:
                 arr[:, b, k] = m
         return arr
 
-    def _features(self, indices: Sequence[int], plan: BatchPlan, i64: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    def _features(self, indices: Sequence[int], plan: BatchPlan, i64: torch.Tensor, lens: torch.Tensor,
+                  warp: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None) -> torch.Tensor:
         """Unmasked features (B, F, T) of the clips ``indices``; ``i64`` holds their bank offsets, then B matrix-row
-        offsets, on the device."""
+        offsets, on the device.  ``warp``: ``(plans, new lengths, width)`` of a batch in which a speed step fired, the
+        first two on the device; the matrix rows are then ``width`` apart."""
         bank, pre, dev = self.bank, self.preprocessor, self.bank.device
         lib, b = _lib.load_data(), len(indices)
         seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
         src, offsets = bank.data, i64[:b]
-        if plan.clips is not None:
+        if plan.clips is not None and warp is not None:
+            plans, lens_new, width = warp
+            warped = _warp.warp_rows(bank.data, offsets, lens, plans, width)
+            unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in plan.clips]
+            for c in unshifted:
+                c.shift = 0                                          # the resampler's read has shifted the row
+            gaussian = (plan.gaussian[:, :width].contiguous().to(dev, non_blocking=True) if plan.gaussian is not None
+                        else None)
+            src = self.audio_augmentor._run(warped, unshifted, plan.new_lengths, gaussian, plan.seed)
+            offsets, lens = i64[b:2 * b], lens_new
+        elif plan.clips is not None:
             host_lens = [int(bank.lengths[i]) for i in indices]
             row_len = max(host_lens)
             rows = torch.empty((b, row_len), dtype=torch.float32, device=dev)
             _lib.check_data(lib.cough_gather_rows(bank.data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
                                                   rows.data_ptr(), row_len, row_len, _stream(dev)), "cough_gather_rows")
-            gaussian = plan.gaussian.to(dev, non_blocking=True) if plan.gaussian is not None else None
+            gaussian = plan.gaussian
+            if gaussian is not None and gaussian.shape[1] != row_len:    # drawn for a speed step that did not fire
+                gaussian = gaussian[:, :row_len].contiguous()
+            gaussian = gaussian.to(dev, non_blocking=True) if gaussian is not None else None
             src = self.audio_augmentor._run(rows, plan.clips, host_lens, gaussian, plan.seed)
             offsets = i64[b:2 * b]
         _lib.check_data(lib.cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b, seg.data_ptr(),
@@ -374,6 +412,13 @@ class DeviceDataLoader:
         if plan.perm is not None:
             mix, mix_at = _mix_words(b + masks.size, np.asarray(plan.perm), plan.lam)
             words.append(mix)
+        warps, warp_at = plan.clips is not None and plan.warps(), 0
+        if warps:                                # the speed step's plans and new lengths ride behind the other words
+            row_len = max(plan.new_lengths)
+            warp_at = sum(int(w.size) for w in words)
+            words.append(_warp.plan_array([(c.shift,) + (p if p is not None else (1, 1))
+                                           for c, p in zip(plan.clips, plan.pairs)]).reshape(-1))
+            words.append(np.asarray(plan.new_lengths, dtype=np.int32))
         i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
                                                 bank.labels.numpy()[idx], idx]), np.concatenate(words))
         targets = i64[2 * b:3 * b]
@@ -382,7 +427,12 @@ class DeviceDataLoader:
                 self._fill_cache()
             feats = self._cache[i64[3 * b:4 * b]]
         else:
-            feats = self._features(indices, plan, i64, i32[:b])
+            warp = None
+            if warps:
+                n_plan = b * _warp.PLAN_WORDS
+                warp = (i32[warp_at:warp_at + n_plan].view(b, _warp.PLAN_WORDS), i32[warp_at + n_plan:warp_at + n_plan + b],
+                        row_len)
+            feats = self._features(indices, plan, i64, i32[:b], warp)
         if masks.size:
             m = i32[b:b + masks.size].view(3, b, self._n_masks)
             mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
@@ -402,7 +452,10 @@ class DeviceDataLoader:
         """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
         gaussian noise): draw, augment the rows in place in the bank, ``cough_prepare_rows``, the featuriser, and
         ``cough_mask_images`` when there are masks.  The result equals ``launch_batch(indices, plan)`` for the
-        ``BatchPlan`` that holds the same records and masks with ``seed`` as its noise seed."""
+        ``BatchPlan`` that holds the same records and masks with ``seed`` as its noise seed.  With an augmentor that has
+        ``speed=True``, ``cough_draw_speed`` runs first and the records are drawn for the new lengths; ``cough_warp_rows``
+        then shifts and resamples the rows from the bank, and the augmentation runs on its output with the shifts
+        cleared."""
         bank, pre, dev = self.bank, self.preprocessor, self.bank.device
         if dev.type != "cuda":
             raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
@@ -415,19 +468,30 @@ class DeviceDataLoader:
         if self._mixes:
             mix, mix_at = _mix_words(b, *mix_draws(seed, b, self.mixup.alpha))
             words.append(mix)
+        aug = self.audio_augmentor if self._augments else None
+        speed = aug is not None and aug.speed and not self.cache_features
+        if speed:                                # wide enough for the slowest factor: the draws are never read back
+            row_len = _warp.drawn_width(row_len, aug.speed_range, aug.sample_rate)
         i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
                                                 bank.labels.numpy()[idx], idx]), np.concatenate(words))
         lens = i32[:b]
         targets = i64[2 * b:3 * b]
-        clips, masks = _draws.draw_batch(seed, lens, self.audio_augmentor if self._augments else None,
-                                         self.spec_augmentor if self._n_masks else None, self.feature_shape())
+        plans, lens_new = (_warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) if speed
+                           else (None, lens))
+        clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,
+                                         self.feature_shape())
         if self.cache_features:
             if self._cache is None:
                 self._fill_cache()
             feats = self._cache[i64[3 * b:4 * b]]
         else:
             src, offsets = bank.data, i64[:b]
-            if clips is not None:
+            if speed:
+                _warp.clear_shifts(clips)
+                warped = _warp.warp_rows(bank.data, offsets, lens, plans, row_len)
+                src = _draws.augment_rows_drawn(warped, i64[b:2 * b], lens_new, row_len, clips, aug, seed)
+                offsets, lens = i64[b:2 * b], lens_new
+            elif clips is not None:
                 src = _draws.augment_rows_drawn(bank.data, offsets, lens, row_len, clips, self.audio_augmentor, seed)
                 offsets = i64[b:2 * b]
             seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
