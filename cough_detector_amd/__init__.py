@@ -13,6 +13,7 @@ from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, lo
 from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
 from .draws import augment_rows_drawn, draw_batch
 from .warp import draw_speed, speed_rate_pair, warp_rows
+from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
                     sweep_thresholds)
@@ -26,4 +27,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders",
            "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
            "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report",
-           "draw_batch", "augment_rows_drawn", "warp_rows", "draw_speed", "speed_rate_pair"]
+           "draw_batch", "augment_rows_drawn", "warp_rows", "draw_speed", "speed_rate_pair",
+           "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length"]

@@ -5,7 +5,8 @@
 and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``) and
 ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``)
 and ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``: the training steps on soft targets; ``load_soft`` / ``check_soft``)
-and ``libcough_amd_warp.so`` (``include/cough_amd_warp.h``: speed perturbation; ``load_warp`` / ``check_warp``).
+and ``libcough_amd_warp.so`` (``include/cough_amd_warp.h``: speed perturbation; ``load_warp`` / ``check_warp``)
+and ``libcough_amd_pitch.so`` (``include/cough_amd_pitch.h``: the pitch shift's time stretch; ``load_pitch`` / ``check_pitch``).
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -104,6 +105,11 @@ WARP_SYMBOLS = ("cough_warp_abi_version", "cough_warp_last_error", "cough_warp_r
                 "cough_clear_shifts")
 WARP_MAX_RATE, WARP_MAX_RATIO = 1 << 20, 4   # COUGH_WARP_MAX_RATE / COUGH_WARP_MAX_RATIO
 
+# every symbol include/cough_amd_pitch.h declares (the companion library of pitch shift)
+PITCH_LIB_PATH = os.environ.get("COUGH_AMD_PITCH_LIB") or os.path.join(HERE, "libcough_amd_pitch.so")
+PITCH_SYMBOLS = ("cough_pitch_abi_version", "cough_pitch_last_error", "cough_stretch_rows", "cough_draw_pitch")
+PITCH_MAX_LENGTH, PITCH_MAX_SAMPLES, PITCH_MAX_STEPS = 1 << 20, 1 << 21, 12   # COUGH_PITCH_MAX_LENGTH / _SAMPLES / _STEPS
+
 
 MAX_CONTRAST_BANDS = 16
 TRAIN_NUM_PARAMS, TRAIN_NUM_RUNNING = 290370, 1216   # COUGH_TRAIN_NUM_PARAMS / COUGH_TRAIN_NUM_RUNNING
@@ -153,6 +159,16 @@ class CoughAugClip(C.Structure):
 class CoughWarpPlan(C.Structure):
     """cough_warp_plan: one row's time shift and rate pair."""
     _fields_ = [("shift", C.c_int), ("orig", C.c_int), ("new_rate", C.c_int)]
+
+
+class CoughStretchPlan(C.Structure):
+    """cough_stretch_plan: one row's time shift and stretch rate."""
+    _fields_ = [("shift", C.c_int), ("reserved", C.c_int), ("rate", C.c_double)]
+
+
+class CoughPitchStep(C.Structure):
+    """cough_pitch_step: the draw table's entry for one number of semitones."""
+    _fields_ = [("rate", C.c_double), ("orig", C.c_int), ("reserved", C.c_int)]
 
 
 _lib = None
@@ -452,6 +468,33 @@ def load_warp() -> C.CDLL:
     return _warp_lib
 
 
+_pitch_lib = None
+
+
+def load_pitch() -> C.CDLL:
+    """Load (once) and type the companion library of pitch shift; raise loudly if it is not built."""
+    global _pitch_lib
+    if _pitch_lib is not None:
+        return _pitch_lib
+    with _lock:
+        if _pitch_lib is not None:
+            return _pitch_lib
+        if not os.path.exists(PITCH_LIB_PATH):
+            raise RuntimeError(
+                f"{PITCH_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+        lib = C.CDLL(PITCH_LIB_PATH)
+        vp, i, d, ull = C.c_void_p, C.c_int, C.c_double, C.c_ulonglong
+        lib.cough_pitch_abi_version.restype = i
+        lib.cough_pitch_last_error.restype = C.c_char_p
+        lib.cough_stretch_rows.argtypes = [vp, vp, vp, i, vp, vp, i, vp, vp]
+        lib.cough_draw_pitch.argtypes = [ull, i, vp, d, i, i, vp, i, vp, vp, vp, vp]
+        if lib.cough_pitch_abi_version() != 1:
+            raise RuntimeError("libcough_amd_pitch.so ABI version mismatch; rebuild it")
+        _pitch_lib = lib
+    return _pitch_lib
+
+
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
@@ -498,6 +541,12 @@ def check_warp(status: int, what: str) -> None:
     """``check`` for a call into the speed-perturbation library (it keeps a last-error message of its own)."""
     if status != OK:
         _raise(status, what, load_warp().cough_warp_last_error().decode("utf-8", "replace"))
+
+
+def check_pitch(status: int, what: str) -> None:
+    """``check`` for a call into the pitch-shift library (it keeps a last-error message of its own)."""
+    if status != OK:
+        _raise(status, what, load_pitch().cough_pitch_last_error().decode("utf-8", "replace"))
 
 
 def check(status: int, what: str) -> None:

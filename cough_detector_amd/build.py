@@ -1,6 +1,6 @@
 """Build libcough_amd.so and its companions libcough_amd_loop.so, libcough_amd_data.so, libcough_amd_segments.so,
-libcough_amd_score.so, libcough_amd_draws.so, libcough_amd_warp.so and libcough_amd_soft.so (HIP, gfx950 only) in-tree
-with hipcc.
+libcough_amd_score.so, libcough_amd_draws.so, libcough_amd_warp.so, libcough_amd_pitch.so and libcough_amd_soft.so (HIP,
+gfx950 only) in-tree with hipcc.
 
 Every translation unit is compiled to an object file of its own (in parallel, cached under ``build/`` by the newest
 source / header time) and the objects are linked into the shared libraries: ``SOURCES`` into ``libcough_amd.so`` (the
@@ -8,7 +8,8 @@ C-ABI of ``include/cough_amd.h``), ``LOOP_SOURCES`` into ``libcough_amd_loop.so`
 ``DATA_SOURCES`` into ``libcough_amd_data.so`` (``include/cough_amd_data.h``), ``SEGMENTS_SOURCES`` into
 ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``), ``SCORE_SOURCES`` into ``libcough_amd_score.so``
 (``include/cough_amd_score.h``), ``DRAWS_SOURCES`` into ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``), ``WARP_SOURCES`` into
-``libcough_amd_warp.so`` (``include/cough_amd_warp.h``), ``SOFT_SOURCES`` and the three training
+``libcough_amd_warp.so`` (``include/cough_amd_warp.h``), ``PITCH_SOURCES`` into ``libcough_amd_pitch.so``
+(``include/cough_amd_pitch.h``), ``SOFT_SOURCES`` and the three training
 translation units compiled a second time with ``SOFT_FLAGS`` into ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``).  The libraries are build products and stay out of git.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
@@ -46,6 +47,9 @@ DRAWS_SOURCES = ("draws.hip",)
 # the companion library of speed perturbation (the tableless per-row sinc resampler and its draws), on the same terms
 WARP_LIB = os.path.join(HERE, "libcough_amd_warp.so")
 WARP_SOURCES = ("warp.hip",)
+# the companion library of pitch shift (the per-row float64 phase vocoder and its draws), on the same terms
+PITCH_LIB = os.path.join(HERE, "libcough_amd_pitch.so")
+PITCH_SOURCES = ("pitch.hip",)
 # the companion library of the soft-target training steps and the batch MixUp, on the same terms.  Its three steps are
 # the training translation units of libcough_amd.so compiled a second time: SOFT_FLAGS only selects which extern "C"
 # functions they emit (the *_forward_backward_soft entry points instead of the v5 ones), so the step code exists once
@@ -75,22 +79,22 @@ def _headers_mtime() -> float:
     deps += [os.path.join(HERE, "..", "include", h) for h in ("cough_amd.h", "cough_amd_loop.h", "cough_amd_data.h",
                                                                    "cough_amd_segments.h", "cough_amd_score.h",
                                                                    "cough_amd_draws.h", "cough_amd_soft.h",
-                                                                   "cough_amd_warp.h")]
+                                                                   "cough_amd_warp.h", "cough_amd_pitch.h")]
     deps.append(os.path.abspath(__file__))   # the flags live here
     deps += [os.path.join(CSRC, m) for m in ("exports.map", "exports_loop.map", "exports_data.map", "exports_segments.map",
                                              "exports_score.map", "exports_draws.map", "exports_soft.map",
-                                             "exports_warp.map")]
+                                             "exports_warp.map", "exports_pitch.map")]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB, SOFT_LIB, WARP_LIB)
+    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB, SOFT_LIB, WARP_LIB, PITCH_LIB)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t
                                        for s in SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                       + DRAWS_SOURCES + SOFT_SOURCES + WARP_SOURCES)
+                                       + DRAWS_SOURCES + SOFT_SOURCES + WARP_SOURCES + PITCH_SOURCES)
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB) -> str:
@@ -122,7 +126,7 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
 
     variant = bool(extra_flags) or out != LIB
     sources = SOURCES if variant else (SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                      + DRAWS_SOURCES + WARP_SOURCES + SOFT_SOURCES
+                                      + DRAWS_SOURCES + WARP_SOURCES + PITCH_SOURCES + SOFT_SOURCES
                                       + tuple((src, SOFT_FLAGS, "_soft") for src in SOFT_SHARED_SOURCES))
     with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, sources))
@@ -139,7 +143,9 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
         link(objs[score_end:draws_end], "exports_draws.map", DRAWS_LIB)
         warp_end = draws_end + len(WARP_SOURCES)
         link(objs[draws_end:warp_end], "exports_warp.map", WARP_LIB)
-        link(objs[warp_end:], "exports_soft.map", SOFT_LIB)
+        pitch_end = warp_end + len(PITCH_SOURCES)
+        link(objs[warp_end:pitch_end], "exports_pitch.map", PITCH_LIB)
+        link(objs[pitch_end:], "exports_soft.map", SOFT_LIB)
     return out
 
 

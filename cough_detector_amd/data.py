@@ -37,6 +37,13 @@ the rest of the chain and ``cough_prepare_rows`` then work on the warped rows an
 ``draws="host"`` the per-row plans and ``n'`` travel with the batch's pinned upload (a batch in which no speed coin
 fired runs the launches it ran before); with ``draws="device"`` ``cough_draw_speed`` draws them first, the output is as
 wide as the slowest factor can make the longest row, and nothing is read back.
+
+An ``AudioAugmentor(pitch=True)`` adds the pitch step behind it (``cough_detector_amd/pitch.py``): two more launches,
+``cough_stretch_rows`` and ``cough_warp_rows``, which keep every row's length.  Without a speed step the stretch reads
+the clips in place from the bank and applies the time shift.  With ``draws="host"`` the two plans per row travel with
+the pinned upload (a batch in which no pitch coin fired runs the launches it ran before); with ``draws="device"``
+``cough_draw_pitch`` draws them, and the stretched rows are as wide as the largest number of semitones can make the
+longest row.
 """
 from __future__ import annotations
 
@@ -51,6 +58,7 @@ from torch.utils.data import RandomSampler, WeightedRandomSampler
 
 from . import _lib
 from . import draws as _draws
+from . import pitch as _pitch
 from . import warp as _warp
 from ._native import cuda_device
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
@@ -89,6 +97,16 @@ def _mix_words(n_before: int, perm: np.ndarray, lam: np.ndarray) -> Tuple[np.nda
     pad = n_before & 1
     words = np.concatenate([np.zeros(pad, np.int32), mix_coefficients(lam).reshape(-1).view(np.int32),
                             np.asarray(perm, dtype=np.int32)])
+    return words, n_before + pad
+
+
+def _pitch_words(n_before: int, stretch: np.ndarray, back: np.ndarray) -> Tuple[np.ndarray, int]:
+    """The int32 words a batch with a pitch step adds to its upload behind ``n_before`` words: padding to an 8-byte
+    boundary, the (b, 16)-byte stretch plans, the (b, 3) int32 plans of the resampling that follows.  Returns them and
+    the stretch plans' word offset."""
+    pad = n_before & 1
+    words = np.concatenate([np.zeros(pad, np.int32), np.ascontiguousarray(stretch).reshape(-1).view(np.int32),
+                            np.asarray(back, dtype=np.int32).reshape(-1)])
     return words, n_before + pad
 
 
@@ -204,14 +222,21 @@ class BatchPlan:
     (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it); with a
     ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None.  With an augmentor that
     has ``speed=True``, ``pairs`` (per item the speed step's ``(orig, new)``, None when its coin did not fire) and
-    ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples."""
+    ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples.  With an augmentor that
+    has ``pitch=True``, ``steps`` (per item the pitch step's semitones, None when its coin did not fire); else None."""
 
-    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths")
+    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps")
 
-    def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None, pairs=None, new_lengths=None):
+    def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None, pairs=None, new_lengths=None,
+                 steps=None):
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
         self.perm, self.lam = perm, lam
         self.pairs, self.new_lengths = pairs, new_lengths
+        self.steps = steps
+
+    def pitches(self) -> bool:
+        """Whether a pitch step fired (with semitones other than 0) in this batch."""
+        return self.steps is not None and any(self.steps)
 
     def warps(self) -> bool:
         """Whether a speed step fired in this batch."""
@@ -279,6 +304,7 @@ class DeviceDataLoader:
         self._cache: Optional[torch.Tensor] = None
         self.draws = draws
         self.last_epoch_seed: Optional[int] = None
+        self._pitch_table: Optional[torch.Tensor] = None     # cough_draw_pitch's table, on the device
 
     def _mask_slots(self) -> List[int]:
         s = self.spec_augmentor
@@ -316,10 +342,13 @@ class DeviceDataLoader:
         lengths = [int(self.bank.lengths[i]) for i in indices]
         f, t = self.feature_shape()
         speed = self._augments and self.audio_augmentor.speed
+        pitch = self._augments and self.audio_augmentor.pitch
         if self._augments:
             plan.clips = []
             if speed:
                 plan.pairs, plan.new_lengths = [], []
+            if pitch:
+                plan.steps = []
             if self.noise == "host":
                 aug = self.audio_augmentor
                 wide = _warp.drawn_width(max(lengths), aug.speed_range, aug.sample_rate) if speed else max(lengths)
@@ -328,8 +357,10 @@ class DeviceDataLoader:
             plan.masks = []
         for row, n in enumerate(lengths):
             if self._augments:
-                c, pair, n = self.audio_augmentor.draw_item(n)       # n' from here on; n itself without a speed step
+                c, pair, n, steps = self.audio_augmentor.draw_item_pitched(n)    # n' from here on; n without a speed step
                 plan.clips.append(c)
+                if pitch:
+                    plan.steps.append(steps)
                 if speed:
                     plan.pairs.append(pair)
                     plan.new_lengths.append(n)
@@ -355,24 +386,32 @@ class DeviceDataLoader:
         return arr
 
     def _features(self, indices: Sequence[int], plan: BatchPlan, i64: torch.Tensor, lens: torch.Tensor,
-                  warp: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None) -> torch.Tensor:
+                  warp: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
+                  pitch: Optional[Tuple[torch.Tensor, torch.Tensor, int, int]] = None) -> torch.Tensor:
         """Unmasked features (B, F, T) of the clips ``indices``; ``i64`` holds their bank offsets, then B matrix-row
         offsets, on the device.  ``warp``: ``(plans, new lengths, width)`` of a batch in which a speed step fired, the
-        first two on the device; the matrix rows are then ``width`` apart."""
+        first two on the device; the matrix rows are then ``width`` apart.  ``pitch``: ``(stretch plans, resampling
+        plans, stretch width, width)`` of a batch in which a pitch step fired, the first two on the device."""
         bank, pre, dev = self.bank, self.preprocessor, self.bank.device
         lib, b = _lib.load_data(), len(indices)
         seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
         src, offsets = bank.data, i64[:b]
-        if plan.clips is not None and warp is not None:
-            plans, lens_new, width = warp
-            warped = _warp.warp_rows(bank.data, offsets, lens, plans, width)
+        if plan.clips is not None and (warp is not None or pitch is not None):
+            host_lens = [int(bank.lengths[i]) for i in indices]
+            if warp is not None:                                     # shift and speed, read in place from the bank
+                plans, lens_new, width = warp
+                src = _warp.warp_rows(bank.data, offsets, lens, plans, width)
+                offsets, lens, host_lens = i64[b:2 * b], lens_new, plan.new_lengths
+            if pitch is not None:                                    # the shift rides in the stretch's read if not in the warp's
+                stretch, back, stretch_width, width = pitch
+                src = _pitch.pitch_shift_rows(src.reshape(-1), offsets, lens, stretch, back, width, stretch_width)
+                offsets = i64[b:2 * b]
             unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in plan.clips]
             for c in unshifted:
-                c.shift = 0                                          # the resampler's read has shifted the row
+                c.shift = 0                                          # the first kernel's read has shifted the row
             gaussian = (plan.gaussian[:, :width].contiguous().to(dev, non_blocking=True) if plan.gaussian is not None
                         else None)
-            src = self.audio_augmentor._run(warped, unshifted, plan.new_lengths, gaussian, plan.seed)
-            offsets, lens = i64[b:2 * b], lens_new
+            src = self.audio_augmentor._run(src, unshifted, host_lens, gaussian, plan.seed)
         elif plan.clips is not None:
             host_lens = [int(bank.lengths[i]) for i in indices]
             row_len = max(host_lens)
@@ -419,6 +458,17 @@ class DeviceDataLoader:
             words.append(_warp.plan_array([(c.shift,) + (p if p is not None else (1, 1))
                                            for c, p in zip(plan.clips, plan.pairs)]).reshape(-1))
             words.append(np.asarray(plan.new_lengths, dtype=np.int32))
+        pitched, pitch_at, stretch_width = plan.clips is not None and plan.pitches() and not self.cache_features, 0, 0
+        if pitched:                              # the pitch step's two plans per row ride behind those
+            lens_now = plan.new_lengths if warps else host_lens.tolist()
+            rates = [_pitch.pitch_rate(s) if s else 1.0 for s in plan.steps]
+            sr = self.audio_augmentor.sample_rate
+            stretch_width = max(_pitch.stretched_length(n, r) for n, r in zip(lens_now, rates))
+            pitch_words, pitch_at = _pitch_words(
+                sum(int(w.size) for w in words),
+                _pitch.plan_array([(0 if warps else c.shift, r) for c, r in zip(plan.clips, rates)]),
+                _warp.plan_array([(0,) + (_pitch.pitch_rate_pair(s, sr) if s else (1, 1)) for s in plan.steps]))
+            words.append(pitch_words)
         i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
                                                 bank.labels.numpy()[idx], idx]), np.concatenate(words))
         targets = i64[2 * b:3 * b]
@@ -432,7 +482,13 @@ class DeviceDataLoader:
                 n_plan = b * _warp.PLAN_WORDS
                 warp = (i32[warp_at:warp_at + n_plan].view(b, _warp.PLAN_WORDS), i32[warp_at + n_plan:warp_at + n_plan + b],
                         row_len)
-            feats = self._features(indices, plan, i64, i32[:b], warp)
+            pitch = None
+            if pitched:
+                n_plan = b * _pitch.PLAN_BYTES // 4
+                pitch = (i32[pitch_at:pitch_at + n_plan].view(torch.uint8).view(b, _pitch.PLAN_BYTES),
+                         i32[pitch_at + n_plan:pitch_at + n_plan + b * _warp.PLAN_WORDS].view(b, _warp.PLAN_WORDS),
+                         stretch_width, row_len)
+            feats = self._features(indices, plan, i64, i32[:b], warp, pitch)
         if masks.size:
             m = i32[b:b + masks.size].view(3, b, self._n_masks)
             mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
@@ -455,7 +511,9 @@ class DeviceDataLoader:
         ``BatchPlan`` that holds the same records and masks with ``seed`` as its noise seed.  With an augmentor that has
         ``speed=True``, ``cough_draw_speed`` runs first and the records are drawn for the new lengths; ``cough_warp_rows``
         then shifts and resamples the rows from the bank, and the augmentation runs on its output with the shifts
-        cleared."""
+        cleared.  With ``pitch=True``, ``cough_draw_pitch`` draws the two plans of the pitch step for the (new) lengths;
+        ``cough_stretch_rows`` and ``cough_warp_rows`` run behind the speed step -- the time shift rides in the stretch's
+        read when there is no speed step: its word is copied from the records into the stretch plans on the device."""
         bank, pre, dev = self.bank, self.preprocessor, self.bank.device
         if dev.type != "cuda":
             raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
@@ -478,6 +536,12 @@ class DeviceDataLoader:
         targets = i64[2 * b:3 * b]
         plans, lens_new = (_warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) if speed
                            else (None, lens))
+        pitch = aug is not None and aug.pitch and not self.cache_features
+        if pitch:
+            if self._pitch_table is None:
+                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate)).to(dev)
+            stretch, back, _ = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
+                                                 self._pitch_table)
         clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,
                                          self.feature_shape())
         if self.cache_features:
@@ -486,11 +550,19 @@ class DeviceDataLoader:
             feats = self._cache[i64[3 * b:4 * b]]
         else:
             src, offsets = bank.data, i64[:b]
-            if speed:
+            if speed or pitch:
+                if speed:
+                    src = _warp.warp_rows(bank.data, offsets, lens, plans, row_len)
+                    offsets, lens = i64[b:2 * b], lens_new
+                else:                            # the records' shift words into the stretch plans' (both lead their struct)
+                    stretch.view(torch.int32).view(b, _pitch.PLAN_BYTES // 4)[:, 0] = \
+                        clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
                 _warp.clear_shifts(clips)
-                warped = _warp.warp_rows(bank.data, offsets, lens, plans, row_len)
-                src = _draws.augment_rows_drawn(warped, i64[b:2 * b], lens_new, row_len, clips, aug, seed)
-                offsets, lens = i64[b:2 * b], lens_new
+                if pitch:
+                    src = _pitch.pitch_shift_rows(src.reshape(-1), offsets, lens, stretch, back, row_len,
+                                                  _pitch.drawn_width(row_len, aug.pitch_range))
+                    offsets = i64[b:2 * b]
+                src = _draws.augment_rows_drawn(src, offsets, lens, row_len, clips, aug, seed)
             elif clips is not None:
                 src = _draws.augment_rows_drawn(bank.data, offsets, lens, row_len, clips, self.audio_augmentor, seed)
                 offsets = i64[b:2 * b]

@@ -9,7 +9,7 @@
 * ``speed_rate_pair``: ``torchaudio.functional.speed``'s rule, ``(int(factor * sample_rate), sample_rate)``.
 
 The arithmetic and the draw contract are stated in ``include/cough_amd_warp.h`` and restated in numpy in
-``tests/warp_ref.py``.  Pitch shift is not part of this: ``AudioAugmentor.pitch_shift`` still returns its input.
+``tests/warp_ref.py``.  Pitch shift (``cough_detector_amd/pitch.py``) runs ``warp_rows`` behind its time stretch.
 """
 from __future__ import annotations
 
