@@ -1,12 +1,10 @@
-"""ctypes binding of ``libcough_amd.so`` (the C-ABI declared in ``include/cough_amd.h``) and of its companion
-``libcough_amd_loop.so`` (``include/cough_amd_loop.h``: what the epoch loop adds; ``load_loop`` / ``check_loop``) and
-``libcough_amd_data.so`` (``include/cough_amd_data.h``: the input pipeline; ``load_data`` / ``check_data``) and
-``libcough_amd_segments.so`` (``include/cough_amd_segments.h``: corpus curation; ``load_segments`` / ``check_segments``)
-and ``libcough_amd_score.so`` (``include/cough_amd_score.h``: offline scoring; ``load_score`` / ``check_score``) and
-``libcough_amd_draws.so`` (``include/cough_amd_draws.h``: a batch's draws on the device; ``load_draws`` / ``check_draws``)
-and ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``: the training steps on soft targets; ``load_soft`` / ``check_soft``)
-and ``libcough_amd_warp.so`` (``include/cough_amd_warp.h``: speed perturbation; ``load_warp`` / ``check_warp``)
-and ``libcough_amd_pitch.so`` (``include/cough_amd_pitch.h``: the pitch shift's time stretch; ``load_pitch`` / ``check_pitch``).
+"""ctypes binding of the native libraries: one ``Library`` record per shared object, in ``LIBRARIES``.
+
+A record's name gives everything regular about it: the file ``libcough_amd[_NAME].so`` beside this module (or the path in
+the environment variable ``COUGH_AMD[_NAME]_LIB``), the C-ABI header ``include/cough_amd[_NAME].h`` and the entry points
+``cough_NAME_abi_version`` / ``cough_NAME_last_error`` (``amd``, the main library, carries no suffix).  What is its own is
+the ABI version it must report and its prototypes.  ``load`` / ``check`` bind the main library's record, ``load_NAME`` /
+``check_NAME`` a companion's; ``NAME_SYMBOLS`` are the prototypes' names.
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -17,8 +15,6 @@ import os
 import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# COUGH_AMD_LIB: alternative build of the same ABI (same-box A/B timing of kernel variants)
-LIB_PATH = os.environ.get("COUGH_AMD_LIB") or os.path.join(HERE, "libcough_amd.so")
 
 OK, EINVAL, EUNSUPPORTED, EHIP, EWORKSPACE = 0, 1, 2, 3, 4
 FEAT_NORMALIZE = 1
@@ -42,75 +38,16 @@ def normalize_dtype(compute_dtype: str, allowed) -> str:
         raise ValueError(f"compute_dtype must be one of {names}, got {compute_dtype!r}")
     return compute_dtype
 
-# every symbol include/cough_amd.h declares (tests check the library exports all of them)
-SYMBOLS = (
-    "cough_amd_abi_version", "cough_amd_arch", "cough_amd_last_error",
-    "cough_featurizer_create", "cough_featurizer_destroy", "cough_featurizer_num_features",
-    "cough_featurizer_num_frames", "cough_featurizer_path", "cough_featurize", "cough_featurizer_workspace_bytes", "cough_featurize_ws",
-    "cough_spectrogram", "cough_featurizer_num_frames_for", "cough_featurizer_workspace_bytes_for", "cough_featurize_any",
-    "cough_spectrogram_any",
-    "cough_resnet_create", "cough_resnet_create_ex", "cough_resnet_destroy", "cough_resnet_workspace_bytes",
-    "cough_resblock_create", "cough_resblock_destroy", "cough_resblock_workspace_bytes", "cough_resblock_out_shape",
-    "cough_resblock_forward",
-    "cough_resnet_forward", "cough_resnet_read_activation",
-    "cough_cnn_create", "cough_cnn_destroy", "cough_cnn_workspace_bytes", "cough_cnn_forward", "cough_cnn_conv_output",
-    "cough_pipeline_workspace_bytes", "cough_pipeline_forward",
-    "cough_mask_axes", "cough_prepare_clip", "cough_resample", "cough_ring_write", "cough_window_gather",
-    "cough_synth_clips", "cough_pre_emphasis", "cough_compute_deltas", "cough_pcen",
-    "cough_augment_workspace_bytes", "cough_augment_waveforms", "cough_mix_rows",
-    "cough_train_workspace_bytes", "cough_train_forward_backward", "cough_adamw_step",
-    "cough_train_small_workspace_bytes", "cough_train_small_forward_backward",
-    "cough_train_std_workspace_bytes", "cough_train_std_forward_backward",
-)
 
-# every symbol include/cough_amd_loop.h declares (the companion library of the epoch loop; cough_amd.h stays at ABI v5)
-LOOP_LIB_PATH = os.environ.get("COUGH_AMD_LOOP_LIB") or os.path.join(HERE, "libcough_amd_loop.so")
-LOOP_SYMBOLS = ("cough_loop_abi_version", "cough_loop_last_error", "cough_epoch_meter_update")
 EPOCH_METER_BYTES = 64   # COUGH_EPOCH_METER_BYTES
-
-# every symbol include/cough_amd_data.h declares (the companion library of the input pipeline)
-DATA_LIB_PATH = os.environ.get("COUGH_AMD_DATA_LIB") or os.path.join(HERE, "libcough_amd_data.so")
-DATA_SYMBOLS = ("cough_data_abi_version", "cough_data_last_error", "cough_gather_rows", "cough_prepare_rows",
-                "cough_mask_images")
 PREP_NORMALIZE = 1       # COUGH_PREP_NORMALIZE
 MAX_MASKS = 16           # COUGH_MAX_MASKS
-
-# every symbol include/cough_amd_segments.h declares (the companion library of corpus curation)
-SEGMENTS_LIB_PATH = os.environ.get("COUGH_AMD_SEGMENTS_LIB") or os.path.join(HERE, "libcough_amd_segments.so")
-SEGMENTS_SYMBOLS = ("cough_segments_abi_version", "cough_segments_last_error", "cough_frame_energy_tile_frames",
-                    "cough_frame_energy", "cough_pick_segments", "cough_copy_segments")
 MAX_SEGMENTS = 16        # COUGH_MAX_SEGMENTS
 MAX_FRAME_LENGTH = 4096  # COUGH_MAX_FRAME_LENGTH
-
-# every symbol include/cough_amd_score.h declares (the companion library of offline scoring)
-SCORE_LIB_PATH = os.environ.get("COUGH_AMD_SCORE_LIB") or os.path.join(HERE, "libcough_amd_score.so")
-SCORE_SYMBOLS = ("cough_score_abi_version", "cough_score_last_error", "cough_smooth_windows", "cough_sweep_thresholds",
-                 "cough_list_events")
 MAX_SMOOTHING = 32       # COUGH_MAX_SMOOTHING
 MAX_THRESHOLDS = 1024    # COUGH_MAX_THRESHOLDS
-
-# every symbol include/cough_amd_draws.h declares (the companion library of the device-side draws)
-DRAWS_LIB_PATH = os.environ.get("COUGH_AMD_DRAWS_LIB") or os.path.join(HERE, "libcough_amd_draws.so")
-DRAWS_SYMBOLS = ("cough_draws_abi_version", "cough_draws_last_error", "cough_draw_batch",
-                 "cough_augment_rows_drawn_workspace_bytes", "cough_augment_rows_drawn")
-
-# every symbol include/cough_amd_soft.h declares (the companion library of the soft-target steps and the batch MixUp)
-SOFT_LIB_PATH = os.environ.get("COUGH_AMD_SOFT_LIB") or os.path.join(HERE, "libcough_amd_soft.so")
-SOFT_SYMBOLS = ("cough_soft_abi_version", "cough_soft_last_error", "cough_train_forward_backward_soft",
-                "cough_train_small_forward_backward_soft", "cough_train_std_forward_backward_soft", "cough_mix_batch")
-
-# every symbol include/cough_amd_warp.h declares (the companion library of speed perturbation)
-WARP_LIB_PATH = os.environ.get("COUGH_AMD_WARP_LIB") or os.path.join(HERE, "libcough_amd_warp.so")
-WARP_SYMBOLS = ("cough_warp_abi_version", "cough_warp_last_error", "cough_warp_rows", "cough_draw_speed",
-                "cough_clear_shifts")
 WARP_MAX_RATE, WARP_MAX_RATIO = 1 << 20, 4   # COUGH_WARP_MAX_RATE / COUGH_WARP_MAX_RATIO
-
-# every symbol include/cough_amd_pitch.h declares (the companion library of pitch shift)
-PITCH_LIB_PATH = os.environ.get("COUGH_AMD_PITCH_LIB") or os.path.join(HERE, "libcough_amd_pitch.so")
-PITCH_SYMBOLS = ("cough_pitch_abi_version", "cough_pitch_last_error", "cough_stretch_rows", "cough_draw_pitch")
 PITCH_MAX_LENGTH, PITCH_MAX_SAMPLES, PITCH_MAX_STEPS = 1 << 20, 1 << 21, 12   # COUGH_PITCH_MAX_LENGTH / _SAMPLES / _STEPS
-
-
 MAX_CONTRAST_BANDS = 16
 TRAIN_NUM_PARAMS, TRAIN_NUM_RUNNING = 290370, 1216   # COUGH_TRAIN_NUM_PARAMS / COUGH_TRAIN_NUM_RUNNING
 TRAIN_SMALL_NUM_PARAMS, TRAIN_SMALL_NUM_RUNNING = 21122, 480   # COUGH_TRAIN_SMALL_NUM_PARAMS / _NUM_RUNNING
@@ -171,390 +108,191 @@ class CoughPitchStep(C.Structure):
     _fields_ = [("rate", C.c_double), ("orig", C.c_int), ("reserved", C.c_int)]
 
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load() -> C.CDLL:
-    """Load (once) and type the library; raise loudly if it is not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(LIB_PATH)
-        vp, ll, i = C.c_void_p, C.c_longlong, C.c_int
-        lib.cough_amd_abi_version.restype = i
-        lib.cough_amd_arch.restype = C.c_char_p
-        lib.cough_amd_last_error.restype = C.c_char_p
-        lib.cough_featurizer_create.argtypes = [C.POINTER(vp), C.POINTER(FeatConfig), _FP, _FP, _FP]
-        lib.cough_featurizer_destroy.argtypes = [vp]
-        lib.cough_featurizer_destroy.restype = None
-        lib.cough_featurizer_num_features.argtypes = [vp]
-        lib.cough_featurizer_num_frames.argtypes = [vp]
-        lib.cough_featurizer_path.argtypes = [vp]
-        lib.cough_featurize.argtypes = [vp, vp, ll, vp, i, i, vp]
-        lib.cough_spectrogram.argtypes = [vp, vp, ll, vp, i, i, vp]
-        lib.cough_featurizer_workspace_bytes.argtypes = [vp, i]
-        lib.cough_featurizer_workspace_bytes.restype = C.c_size_t
-        lib.cough_featurize_ws.argtypes = [vp, vp, ll, vp, i, i, vp, C.c_size_t, vp]
-        lib.cough_featurizer_num_frames_for.argtypes = [vp, i]
-        lib.cough_featurizer_workspace_bytes_for.argtypes = [vp, i, i]
-        lib.cough_featurizer_workspace_bytes_for.restype = C.c_size_t
-        lib.cough_featurize_any.argtypes = [vp, vp, ll, i, vp, i, i, vp, C.c_size_t, vp]
-        lib.cough_spectrogram_any.argtypes = [vp, vp, ll, i, vp, i, i, vp]
-        lib.cough_resnet_create.argtypes = [C.POINTER(vp), C.POINTER(ResNetWeights), i]
-        lib.cough_resnet_create_ex.argtypes = [C.POINTER(vp), i, C.POINTER(i), C.POINTER(ConvBN), C.POINTER(ResBlockWeights),
-                                               _FP, _FP, C.c_float, i]
-        lib.cough_resblock_create.argtypes = [C.POINTER(vp), i, i, i, C.POINTER(ConvBN), C.POINTER(ConvBN), C.POINTER(ConvBN),
-                                              C.c_float]
-        lib.cough_resblock_destroy.argtypes = [vp]
-        lib.cough_resblock_destroy.restype = None
-        lib.cough_resblock_workspace_bytes.argtypes = [vp, i, i, i]
-        lib.cough_resblock_workspace_bytes.restype = C.c_size_t
-        lib.cough_resblock_out_shape.argtypes = [vp, i, i, C.POINTER(i), C.POINTER(i)]
-        lib.cough_resblock_forward.argtypes = [vp, vp, i, i, i, vp, vp, C.c_size_t, vp]
-        lib.cough_resnet_destroy.argtypes = [vp]
-        lib.cough_resnet_destroy.restype = None
-        lib.cough_resnet_workspace_bytes.argtypes = [vp, i, i, i]
-        lib.cough_resnet_workspace_bytes.restype = C.c_size_t
-        lib.cough_resnet_forward.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, C.c_size_t, vp]
-        lib.cough_resnet_read_activation.argtypes = [vp, vp, i, i, i, i, vp, vp]
-        lib.cough_cnn_create.argtypes = [C.POINTER(vp), C.POINTER(CnnWeights), i]
-        lib.cough_cnn_destroy.argtypes = [vp]
-        lib.cough_cnn_destroy.restype = None
-        lib.cough_cnn_workspace_bytes.argtypes = [vp, i, i, i]
-        lib.cough_cnn_workspace_bytes.restype = C.c_size_t
-        lib.cough_cnn_forward.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, C.c_size_t, vp]
-        lib.cough_cnn_conv_output.argtypes = [vp, vp, i, i, i, vp, vp, C.c_size_t, vp]
-        lib.cough_pipeline_workspace_bytes.argtypes = [vp, vp, i]
-        lib.cough_pipeline_workspace_bytes.restype = C.c_size_t
-        lib.cough_pipeline_forward.argtypes = [vp, vp, vp, ll, i, i, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
-        lib.cough_mask_axes.argtypes = [vp, vp, ll, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), vp]
-        lib.cough_prepare_clip.argtypes = [vp, ll, i, i, vp, i, i, vp]
-        lib.cough_resample.argtypes = [vp, ll, i, i, vp, i, i, i, vp, ll, i, vp]
-        lib.cough_ring_write.argtypes = [vp, i, vp, i, vp, vp, i, vp]
-        lib.cough_window_gather.argtypes = [vp, i, vp, vp, i, i, vp, vp]
-        lib.cough_synth_clips.argtypes = [vp, ll, i, ll, ll, vp]
-        lib.cough_pre_emphasis.argtypes = [vp, ll, vp, ll, i, i, C.c_float, vp]
-        lib.cough_compute_deltas.argtypes = [vp, vp, ll, i, vp]
-        lib.cough_pcen.argtypes = [vp, vp, ll, i, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-        lib.cough_augment_workspace_bytes.argtypes = [i]
-        lib.cough_augment_workspace_bytes.restype = C.c_size_t
-        lib.cough_augment_waveforms.argtypes = [vp, ll, vp, i, i, C.POINTER(i), C.POINTER(CoughAugClip), vp, ll,
-                                                C.POINTER(ll), C.POINTER(i), i, vp, C.c_ulonglong, vp, C.c_size_t, vp]
-        lib.cough_mix_rows.argtypes = [vp, vp, vp, vp, ll, ll, vp, vp]
-        f, ull = C.c_float, C.c_ulonglong
-        lib.cough_train_workspace_bytes.argtypes = [i, i, i]
-        lib.cough_train_workspace_bytes.restype = C.c_size_t
-        lib.cough_train_forward_backward.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, vp, vp, vp, vp, f, f, vp, vp,
-                                                     vp, vp, C.c_size_t, vp]
-        lib.cough_train_small_workspace_bytes.argtypes = [i, i, i]
-        lib.cough_train_small_workspace_bytes.restype = C.c_size_t
-        lib.cough_train_small_forward_backward.argtypes = lib.cough_train_forward_backward.argtypes
-        lib.cough_train_std_workspace_bytes.argtypes = [i, i, i]
-        lib.cough_train_std_workspace_bytes.restype = C.c_size_t
-        lib.cough_train_std_forward_backward.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, f, vp, vp, vp, vp, f, f,
-                                                         vp, vp, vp, vp, C.c_size_t, vp]
-        lib.cough_adamw_step.argtypes = [vp, vp, vp, vp, ll, f, f, f, f, f, f, C.c_double, C.c_double, vp, vp]
-        if lib.cough_amd_abi_version() != 5:
-            raise RuntimeError("libcough_amd.so ABI version mismatch; rebuild it")
-        _lib = lib
-    return _lib
-
-
-_loop_lib = None
-
-
-def load_loop() -> C.CDLL:
-    """Load (once) and type the companion library of the epoch loop; raise loudly if it is not built."""
-    global _loop_lib
-    if _loop_lib is not None:
-        return _loop_lib
-    with _lock:
-        if _loop_lib is not None:
-            return _loop_lib
-        if not os.path.exists(LOOP_LIB_PATH):
-            raise RuntimeError(
-                f"{LOOP_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(LOOP_LIB_PATH)
-        vp, i = C.c_void_p, C.c_int
-        lib.cough_loop_abi_version.restype = i
-        lib.cough_loop_last_error.restype = C.c_char_p
-        lib.cough_epoch_meter_update.argtypes = [vp, vp, i, vp, vp, vp, vp, vp]
-        if lib.cough_loop_abi_version() != 1:
-            raise RuntimeError("libcough_amd_loop.so ABI version mismatch; rebuild it")
-        _loop_lib = lib
-    return _loop_lib
-
-
-_data_lib = None
-
-
-def load_data() -> C.CDLL:
-    """Load (once) and type the companion library of the input pipeline; raise loudly if it is not built."""
-    global _data_lib
-    if _data_lib is not None:
-        return _data_lib
-    with _lock:
-        if _data_lib is not None:
-            return _data_lib
-        if not os.path.exists(DATA_LIB_PATH):
-            raise RuntimeError(
-                f"{DATA_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(DATA_LIB_PATH)
-        vp, ll, i = C.c_void_p, C.c_longlong, C.c_int
-        lib.cough_data_abi_version.restype = i
-        lib.cough_data_last_error.restype = C.c_char_p
-        lib.cough_gather_rows.argtypes = [vp, vp, vp, i, vp, ll, i, vp]
-        lib.cough_prepare_rows.argtypes = [vp, vp, vp, i, vp, i, i, vp]
-        lib.cough_mask_images.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp]
-        if lib.cough_data_abi_version() != 1:
-            raise RuntimeError("libcough_amd_data.so ABI version mismatch; rebuild it")
-        _data_lib = lib
-    return _data_lib
-
-
-_segments_lib = None
-
-
-def load_segments() -> C.CDLL:
-    """Load (once) and type the companion library of corpus curation; raise loudly if it is not built."""
-    global _segments_lib
-    if _segments_lib is not None:
-        return _segments_lib
-    with _lock:
-        if _segments_lib is not None:
-            return _segments_lib
-        if not os.path.exists(SEGMENTS_LIB_PATH):
-            raise RuntimeError(
-                f"{SEGMENTS_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(SEGMENTS_LIB_PATH)
-        vp, i, d = C.c_void_p, C.c_int, C.c_double
-        lib.cough_segments_abi_version.restype = i
-        lib.cough_segments_last_error.restype = C.c_char_p
-        lib.cough_frame_energy_tile_frames.argtypes = [i, i]
-        lib.cough_frame_energy.argtypes = [vp, vp, vp, vp, i, vp, i, i, i, vp, vp]
-        lib.cough_pick_segments.argtypes = [vp, vp, vp, i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp]
-        lib.cough_copy_segments.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
-        if lib.cough_segments_abi_version() != 1:
-            raise RuntimeError("libcough_amd_segments.so ABI version mismatch; rebuild it")
-        _segments_lib = lib
-    return _segments_lib
-
-
-_score_lib = None
-
-
-def load_score() -> C.CDLL:
-    """Load (once) and type the companion library of offline scoring; raise loudly if it is not built."""
-    global _score_lib
-    if _score_lib is not None:
-        return _score_lib
-    with _lock:
-        if _score_lib is not None:
-            return _score_lib
-        if not os.path.exists(SCORE_LIB_PATH):
-            raise RuntimeError(
-                f"{SCORE_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(SCORE_LIB_PATH)
-        vp, ll, i, d = C.c_void_p, C.c_longlong, C.c_int, C.c_double
-        lib.cough_score_abi_version.restype = i
-        lib.cough_score_last_error.restype = C.c_char_p
-        lib.cough_smooth_windows.argtypes = [vp, vp, i, ll, i, vp, vp]
-        lib.cough_sweep_thresholds.argtypes = [vp, vp, i, ll, vp, i, i, vp, vp, vp, vp, vp]
-        lib.cough_list_events.argtypes = [vp, vp, i, ll, d, i, vp, ll, vp, vp, vp]
-        if lib.cough_score_abi_version() != 1:
-            raise RuntimeError("libcough_amd_score.so ABI version mismatch; rebuild it")
-        _score_lib = lib
-    return _score_lib
-
-
-_draws_lib = None
-
-
-def load_draws() -> C.CDLL:
-    """Load (once) and type the companion library of the device-side draws; raise loudly if it is not built."""
-    global _draws_lib
-    if _draws_lib is not None:
-        return _draws_lib
-    with _lock:
-        if _draws_lib is not None:
-            return _draws_lib
-        if not os.path.exists(DRAWS_LIB_PATH):
-            raise RuntimeError(
-                f"{DRAWS_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(DRAWS_LIB_PATH)
-        vp, ll, i, d, ull = C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_ulonglong
-        lib.cough_draws_abi_version.restype = i
-        lib.cough_draws_last_error.restype = C.c_char_p
-        lib.cough_draw_batch.argtypes = [ull, i, vp, d, i, vp, d, i, i, i, i, i, i, vp, vp, vp, vp, vp]
-        lib.cough_augment_rows_drawn_workspace_bytes.argtypes = [i]
-        lib.cough_augment_rows_drawn_workspace_bytes.restype = C.c_size_t
-        lib.cough_augment_rows_drawn.argtypes = [vp, vp, vp, i, i, vp, vp, ll, vp, vp, i, ull, vp, vp, C.c_size_t, vp]
-        if lib.cough_draws_abi_version() != 1:
-            raise RuntimeError("libcough_amd_draws.so ABI version mismatch; rebuild it")
-        _draws_lib = lib
-    return _draws_lib
-
-
-_soft_lib = None
-
-
-def load_soft() -> C.CDLL:
-    """Load (once) and type the companion library of the soft-target steps; raise loudly if it is not built."""
-    global _soft_lib
-    if _soft_lib is not None:
-        return _soft_lib
-    with _lock:
-        if _soft_lib is not None:
-            return _soft_lib
-        if not os.path.exists(SOFT_LIB_PATH):
-            raise RuntimeError(
-                f"{SOFT_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(SOFT_LIB_PATH)
-        vp, ll, i, f, ull = C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_ulonglong
-        lib.cough_soft_abi_version.restype = i
-        lib.cough_soft_last_error.restype = C.c_char_p
-        # the argument lists of the v5 steps, with the soft targets where the class indices were
-        lib.cough_train_forward_backward_soft.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, vp, vp, vp, vp, f, f, vp,
-                                                          vp, vp, vp, C.c_size_t, vp]
-        lib.cough_train_small_forward_backward_soft.argtypes = lib.cough_train_forward_backward_soft.argtypes
-        lib.cough_train_std_forward_backward_soft.argtypes = [vp, i, i, i, vp, vp, vp, ull, ull, f, f, vp, vp, vp, vp, f,
-                                                              f, vp, vp, vp, vp, C.c_size_t, vp]
-        lib.cough_mix_batch.argtypes = [vp, vp, vp, vp, i, ll, vp, vp, vp]
-        if lib.cough_soft_abi_version() != 1:
-            raise RuntimeError("libcough_amd_soft.so ABI version mismatch; rebuild it")
-        _soft_lib = lib
-    return _soft_lib
-
-
-_warp_lib = None
-
-
-def load_warp() -> C.CDLL:
-    """Load (once) and type the companion library of speed perturbation; raise loudly if it is not built."""
-    global _warp_lib
-    if _warp_lib is not None:
-        return _warp_lib
-    with _lock:
-        if _warp_lib is not None:
-            return _warp_lib
-        if not os.path.exists(WARP_LIB_PATH):
-            raise RuntimeError(
-                f"{WARP_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(WARP_LIB_PATH)
-        vp, i, d, ull = C.c_void_p, C.c_int, C.c_double, C.c_ulonglong
-        lib.cough_warp_abi_version.restype = i
-        lib.cough_warp_last_error.restype = C.c_char_p
-        lib.cough_warp_rows.argtypes = [vp, vp, vp, i, vp, vp, i, vp, vp]
-        lib.cough_draw_speed.argtypes = [ull, i, vp, d, d, d, i, vp, vp, vp]
-        lib.cough_clear_shifts.argtypes = [vp, i, vp]
-        if lib.cough_warp_abi_version() != 1:
-            raise RuntimeError("libcough_amd_warp.so ABI version mismatch; rebuild it")
-        _warp_lib = lib
-    return _warp_lib
-
-
-_pitch_lib = None
-
-
-def load_pitch() -> C.CDLL:
-    """Load (once) and type the companion library of pitch shift; raise loudly if it is not built."""
-    global _pitch_lib
-    if _pitch_lib is not None:
-        return _pitch_lib
-    with _lock:
-        if _pitch_lib is not None:
-            return _pitch_lib
-        if not os.path.exists(PITCH_LIB_PATH):
-            raise RuntimeError(
-                f"{PITCH_LIB_PATH} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
-                "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
-        lib = C.CDLL(PITCH_LIB_PATH)
-        vp, i, d, ull = C.c_void_p, C.c_int, C.c_double, C.c_ulonglong
-        lib.cough_pitch_abi_version.restype = i
-        lib.cough_pitch_last_error.restype = C.c_char_p
-        lib.cough_stretch_rows.argtypes = [vp, vp, vp, i, vp, vp, i, vp, vp]
-        lib.cough_draw_pitch.argtypes = [ull, i, vp, d, i, i, vp, i, vp, vp, vp, vp]
-        if lib.cough_pitch_abi_version() != 1:
-            raise RuntimeError("libcough_amd_pitch.so ABI version mismatch; rebuild it")
-        _pitch_lib = lib
-    return _pitch_lib
-
-
 def _raise(status: int, what: str, msg: str) -> None:
     if status in (EINVAL, EUNSUPPORTED):
         raise ValueError(f"{what}: {msg}")
     raise RuntimeError(f"{what}: {msg} (status {status})")
 
 
-def check_loop(status: int, what: str) -> None:
-    """``check`` for a call into the companion library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_loop().cough_loop_last_error().decode("utf-8", "replace"))
+VOID = object()   # a prototype's restype for a function that returns nothing (None leaves ctypes' default, int)
+_lock = threading.Lock()
 
 
-def check_data(status: int, what: str) -> None:
-    """``check`` for a call into the input pipeline's library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_data().cough_data_last_error().decode("utf-8", "replace"))
+class Library:
+    """One shared object: where it is, the ABI version it must report, and its prototypes, an ordered mapping
+    ``symbol -> (restype, argtypes)`` of every entry point its header declares.  ``None`` leaves ctypes' default.
+    ``handle`` is the loaded ``CDLL`` (``None`` until ``load``), ``path`` the file ``load`` opens."""
+
+    def __init__(self, name: str, abi: int, prototypes: dict):
+        tag = "" if name == "amd" else "_" + name
+        self.name, self.abi, self.prototypes = name, abi, prototypes
+        self.soname = f"libcough_amd{tag}.so"
+        # COUGH_AMD[_NAME]_LIB: alternative build of the same ABI (same-box A/B timing of kernel variants)
+        self.path = os.environ.get(f"COUGH_AMD{tag.upper()}_LIB") or os.path.join(HERE, self.soname)
+        self.abi_symbol, self.error_symbol = f"cough_{name}_abi_version", f"cough_{name}_last_error"
+        self.symbols = tuple(prototypes)
+        self.handle = None
+
+    def load(self) -> C.CDLL:
+        """Load (once) and type the library; raise loudly if it is not built."""
+        if self.handle is not None:
+            return self.handle
+        with _lock:
+            if self.handle is not None:
+                return self.handle
+            if not os.path.exists(self.path):
+                raise RuntimeError(
+                    f"{self.path} is missing: the HIP extension is not built. Run `python -m cough_detector_amd.build` "
+                    "(needs hipcc / ROCm, target gfx950). There is no CPU fallback.")
+            lib = C.CDLL(self.path)
+            for symbol, (restype, argtypes) in self.prototypes.items():
+                fn = getattr(lib, symbol)
+                if restype is not None:
+                    fn.restype = None if restype is VOID else restype
+                if argtypes is not None:
+                    fn.argtypes = argtypes
+            if getattr(lib, self.abi_symbol)() != self.abi:
+                raise RuntimeError(f"{self.soname} ABI version mismatch; rebuild it")
+            self.handle = lib
+        return self.handle
+
+    def check(self, status: int, what: str) -> None:
+        """Map a C status to the reference's exception convention (ValueError for argument/config errors, as
+        src/model.py:313-314; RuntimeError otherwise), with this library's own last-error message."""
+        if status != OK:
+            _raise(status, what, getattr(self.load(), self.error_symbol)().decode("utf-8", "replace"))
 
 
-def check_segments(status: int, what: str) -> None:
-    """``check`` for a call into the curation library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_segments().cough_segments_last_error().decode("utf-8", "replace"))
+def _libraries() -> dict:
+    vp, ll, i, f, d, ull, sz, s = (C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_double, C.c_ulonglong, C.c_size_t,
+                                   C.c_char_p)
+    P = C.POINTER
+    step = [vp, i, i, i, vp, vp, vp, ull, ull, f, vp, vp, vp, vp, f, f, vp, vp, vp, vp, sz, vp]
+    step_std = [vp, i, i, i, vp, vp, vp, ull, ull, f, f, vp, vp, vp, vp, f, f, vp, vp, vp, vp, sz, vp]
+    return {lib.name: lib for lib in (
+        # include/cough_amd.h, ABI v5: it stays at its 53 entry points, what came later lives in the companions
+        Library("amd", 5, {
+            "cough_amd_abi_version": (i, None), "cough_amd_arch": (s, None), "cough_amd_last_error": (s, None),
+            "cough_featurizer_create": (None, [P(vp), P(FeatConfig), _FP, _FP, _FP]),
+            "cough_featurizer_destroy": (VOID, [vp]),
+            "cough_featurizer_num_features": (None, [vp]),
+            "cough_featurizer_num_frames": (None, [vp]),
+            "cough_featurizer_path": (None, [vp]),
+            "cough_featurize": (None, [vp, vp, ll, vp, i, i, vp]),
+            "cough_featurizer_workspace_bytes": (sz, [vp, i]),
+            "cough_featurize_ws": (None, [vp, vp, ll, vp, i, i, vp, sz, vp]),
+            "cough_spectrogram": (None, [vp, vp, ll, vp, i, i, vp]),
+            "cough_featurizer_num_frames_for": (None, [vp, i]),
+            "cough_featurizer_workspace_bytes_for": (sz, [vp, i, i]),
+            "cough_featurize_any": (None, [vp, vp, ll, i, vp, i, i, vp, sz, vp]),
+            "cough_spectrogram_any": (None, [vp, vp, ll, i, vp, i, i, vp]),
+            "cough_resnet_create": (None, [P(vp), P(ResNetWeights), i]),
+            "cough_resnet_create_ex": (None, [P(vp), i, P(i), P(ConvBN), P(ResBlockWeights), _FP, _FP, f, i]),
+            "cough_resnet_destroy": (VOID, [vp]),
+            "cough_resnet_workspace_bytes": (sz, [vp, i, i, i]),
+            "cough_resblock_create": (None, [P(vp), i, i, i, P(ConvBN), P(ConvBN), P(ConvBN), f]),
+            "cough_resblock_destroy": (VOID, [vp]),
+            "cough_resblock_workspace_bytes": (sz, [vp, i, i, i]),
+            "cough_resblock_out_shape": (None, [vp, i, i, P(i), P(i)]),
+            "cough_resblock_forward": (None, [vp, vp, i, i, i, vp, vp, sz, vp]),
+            "cough_resnet_forward": (None, [vp, vp, i, i, i, vp, vp, vp, vp, sz, vp]),
+            "cough_resnet_read_activation": (None, [vp, vp, i, i, i, i, vp, vp]),
+            "cough_cnn_create": (None, [P(vp), P(CnnWeights), i]),
+            "cough_cnn_destroy": (VOID, [vp]),
+            "cough_cnn_workspace_bytes": (sz, [vp, i, i, i]),
+            "cough_cnn_forward": (None, [vp, vp, i, i, i, vp, vp, vp, vp, sz, vp]),
+            "cough_cnn_conv_output": (None, [vp, vp, i, i, i, vp, vp, sz, vp]),
+            "cough_pipeline_workspace_bytes": (sz, [vp, vp, i]),
+            "cough_pipeline_forward": (None, [vp, vp, vp, ll, i, i, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+            "cough_mask_axes": (None, [vp, vp, ll, i, i, i, P(i), P(i), P(i), vp]),
+            "cough_prepare_clip": (None, [vp, ll, i, i, vp, i, i, vp]),
+            "cough_resample": (None, [vp, ll, i, i, vp, i, i, i, vp, ll, i, vp]),
+            "cough_ring_write": (None, [vp, i, vp, i, vp, vp, i, vp]),
+            "cough_window_gather": (None, [vp, i, vp, vp, i, i, vp, vp]),
+            "cough_synth_clips": (None, [vp, ll, i, ll, ll, vp]),
+            "cough_pre_emphasis": (None, [vp, ll, vp, ll, i, i, f, vp]),
+            "cough_compute_deltas": (None, [vp, vp, ll, i, vp]),
+            "cough_pcen": (None, [vp, vp, ll, i, f, f, f, f, vp]),
+            "cough_augment_workspace_bytes": (sz, [i]),
+            "cough_augment_waveforms": (None, [vp, ll, vp, i, i, P(i), P(CoughAugClip), vp, ll, P(ll), P(i), i, vp, ull,
+                                               vp, sz, vp]),
+            "cough_mix_rows": (None, [vp, vp, vp, vp, ll, ll, vp, vp]),
+            "cough_train_workspace_bytes": (sz, [i, i, i]),
+            "cough_train_forward_backward": (None, step),
+            "cough_adamw_step": (None, [vp, vp, vp, vp, ll, f, f, f, f, f, f, d, d, vp, vp]),
+            "cough_train_small_workspace_bytes": (sz, [i, i, i]),
+            "cough_train_small_forward_backward": (None, step),
+            "cough_train_std_workspace_bytes": (sz, [i, i, i]),
+            "cough_train_std_forward_backward": (None, step_std),
+        }),
+        # include/cough_amd_loop.h: what the epoch loop adds
+        Library("loop", 1, {
+            "cough_loop_abi_version": (i, None), "cough_loop_last_error": (s, None),
+            "cough_epoch_meter_update": (None, [vp, vp, i, vp, vp, vp, vp, vp]),
+        }),
+        # include/cough_amd_data.h: the input pipeline
+        Library("data", 1, {
+            "cough_data_abi_version": (i, None), "cough_data_last_error": (s, None),
+            "cough_gather_rows": (None, [vp, vp, vp, i, vp, ll, i, vp]),
+            "cough_prepare_rows": (None, [vp, vp, vp, i, vp, i, i, vp]),
+            "cough_mask_images": (None, [vp, vp, i, i, i, i, vp, vp, vp, vp]),
+        }),
+        # include/cough_amd_segments.h: corpus curation
+        Library("segments", 1, {
+            "cough_segments_abi_version": (i, None), "cough_segments_last_error": (s, None),
+            "cough_frame_energy_tile_frames": (None, [i, i]),
+            "cough_frame_energy": (None, [vp, vp, vp, vp, i, vp, i, i, i, vp, vp]),
+            "cough_pick_segments": (None, [vp, vp, vp, i, i, i, i, i, i, d, d, vp, vp, vp, vp, vp]),
+            "cough_copy_segments": (None, [vp, vp, vp, vp, vp, i, i, vp, vp]),
+        }),
+        # include/cough_amd_score.h: offline scoring
+        Library("score", 1, {
+            "cough_score_abi_version": (i, None), "cough_score_last_error": (s, None),
+            "cough_smooth_windows": (None, [vp, vp, i, ll, i, vp, vp]),
+            "cough_sweep_thresholds": (None, [vp, vp, i, ll, vp, i, i, vp, vp, vp, vp, vp]),
+            "cough_list_events": (None, [vp, vp, i, ll, d, i, vp, ll, vp, vp, vp]),
+        }),
+        # include/cough_amd_draws.h: a batch's draws on the device
+        Library("draws", 1, {
+            "cough_draws_abi_version": (i, None), "cough_draws_last_error": (s, None),
+            "cough_draw_batch": (None, [ull, i, vp, d, i, vp, d, i, i, i, i, i, i, vp, vp, vp, vp, vp]),
+            "cough_augment_rows_drawn_workspace_bytes": (sz, [i]),
+            "cough_augment_rows_drawn": (None, [vp, vp, vp, i, i, vp, vp, ll, vp, vp, i, ull, vp, vp, sz, vp]),
+        }),
+        # include/cough_amd_soft.h: the training steps on soft targets and the batch MixUp.  The steps take the argument
+        # lists of the v5 steps, with the soft targets where the class indices were
+        Library("soft", 1, {
+            "cough_soft_abi_version": (i, None), "cough_soft_last_error": (s, None),
+            "cough_train_forward_backward_soft": (None, step),
+            "cough_train_small_forward_backward_soft": (None, step),
+            "cough_train_std_forward_backward_soft": (None, step_std),
+            "cough_mix_batch": (None, [vp, vp, vp, vp, i, ll, vp, vp, vp]),
+        }),
+        # include/cough_amd_warp.h: speed perturbation
+        Library("warp", 1, {
+            "cough_warp_abi_version": (i, None), "cough_warp_last_error": (s, None),
+            "cough_warp_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, vp]),
+            "cough_draw_speed": (None, [ull, i, vp, d, d, d, i, vp, vp, vp]),
+            "cough_clear_shifts": (None, [vp, i, vp]),
+        }),
+        # include/cough_amd_pitch.h: the pitch shift's time stretch
+        Library("pitch", 1, {
+            "cough_pitch_abi_version": (i, None), "cough_pitch_last_error": (s, None),
+            "cough_stretch_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, vp]),
+            "cough_draw_pitch": (None, [ull, i, vp, d, i, i, vp, i, vp, vp, vp, vp]),
+        }),
+    )}
 
 
-def check_score(status: int, what: str) -> None:
-    """``check`` for a call into the scoring library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_score().cough_score_last_error().decode("utf-8", "replace"))
+LIBRARIES = _libraries()
 
-
-def check_draws(status: int, what: str) -> None:
-    """``check`` for a call into the draws library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_draws().cough_draws_last_error().decode("utf-8", "replace"))
-
-
-def check_soft(status: int, what: str) -> None:
-    """``check`` for a call into the soft-target library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_soft().cough_soft_last_error().decode("utf-8", "replace"))
-
-
-def check_warp(status: int, what: str) -> None:
-    """``check`` for a call into the speed-perturbation library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_warp().cough_warp_last_error().decode("utf-8", "replace"))
-
-
-def check_pitch(status: int, what: str) -> None:
-    """``check`` for a call into the pitch-shift library (it keeps a last-error message of its own)."""
-    if status != OK:
-        _raise(status, what, load_pitch().cough_pitch_last_error().decode("utf-8", "replace"))
-
-
-def check(status: int, what: str) -> None:
-    """Map a C status to the reference's exception convention
-    (ValueError for argument/config errors, as src/model.py:313-314; RuntimeError otherwise)."""
-    if status == OK:
-        return
-    _raise(status, what, load().cough_amd_last_error().decode("utf-8", "replace"))
+# the names the rest of the package uses, bound to the records: the main library's carry no prefix
+load, check, SYMBOLS, LIB_PATH = (LIBRARIES["amd"].load, LIBRARIES["amd"].check, LIBRARIES["amd"].symbols,
+                                  LIBRARIES["amd"].path)
+for _r in list(LIBRARIES.values())[1:]:
+    globals().update({f"load_{_r.name}": _r.load, f"check_{_r.name}": _r.check,
+                      f"{_r.name.upper()}_SYMBOLS": _r.symbols, f"{_r.name.upper()}_LIB_PATH": _r.path})
+del _r
 
 
 def fptr(t):

@@ -1,16 +1,10 @@
-"""Build libcough_amd.so and its companions libcough_amd_loop.so, libcough_amd_data.so, libcough_amd_segments.so,
-libcough_amd_score.so, libcough_amd_draws.so, libcough_amd_warp.so, libcough_amd_pitch.so and libcough_amd_soft.so (HIP,
-gfx950 only) in-tree with hipcc.
+"""Build the native libraries (HIP, gfx950 only) in-tree with hipcc.
 
-Every translation unit is compiled to an object file of its own (in parallel, cached under ``build/`` by the newest
-source / header time) and the objects are linked into the shared libraries: ``SOURCES`` into ``libcough_amd.so`` (the
-C-ABI of ``include/cough_amd.h``), ``LOOP_SOURCES`` into ``libcough_amd_loop.so`` (``include/cough_amd_loop.h``),
-``DATA_SOURCES`` into ``libcough_amd_data.so`` (``include/cough_amd_data.h``), ``SEGMENTS_SOURCES`` into
-``libcough_amd_segments.so`` (``include/cough_amd_segments.h``), ``SCORE_SOURCES`` into ``libcough_amd_score.so``
-(``include/cough_amd_score.h``), ``DRAWS_SOURCES`` into ``libcough_amd_draws.so`` (``include/cough_amd_draws.h``), ``WARP_SOURCES`` into
-``libcough_amd_warp.so`` (``include/cough_amd_warp.h``), ``PITCH_SOURCES`` into ``libcough_amd_pitch.so``
-(``include/cough_amd_pitch.h``), ``SOFT_SOURCES`` and the three training
-translation units compiled a second time with ``SOFT_FLAGS`` into ``libcough_amd_soft.so`` (``include/cough_amd_soft.h``).  The libraries are build products and stay out of git.
+``UNITS`` is the table: library name -> its translation units.  Everything else about a library follows from its
+name: ``libcough_amd[_NAME].so`` beside this file, the version script ``csrc/exports[_NAME].map`` and the C-ABI header
+``include/cough_amd[_NAME].h`` (``amd``, the main library, carries no suffix).  Every translation unit is compiled to
+an object file of its own (in parallel, cached under ``build/`` by the newest source / header time) and each library
+is linked from the objects of its own units.  The libraries are build products and stay out of git.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
 from __future__ import annotations
@@ -24,39 +18,37 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
-LIB = os.path.join(HERE, "libcough_amd.so")
 SOURCES = ("api.hip", "featurize.hip", "featurize_generic.hip", "spectrogram.hip", "resnet.hip", "cnn.hip", "stream.hip", "synth.hip",
            "augment.hip", "train.hip", "train_small.hip", "train_std.hip")
-# the companion library of the epoch loop: include/cough_amd.h stays at ABI v5 with its 53 entry points, so what the
-# loop adds is exported from a library of its own (same flags, a version script of its own)
-LOOP_LIB = os.path.join(HERE, "libcough_amd_loop.so")
-LOOP_SOURCES = ("loop.hip",)
-# the companion library of the input pipeline (the device-resident dataset and batch loader), on the same terms
-DATA_LIB = os.path.join(HERE, "libcough_amd_data.so")
-DATA_SOURCES = ("data.hip",)
-# the companion library of corpus curation (frame energies, segment picking), on the same terms
-SEGMENTS_LIB = os.path.join(HERE, "libcough_amd_segments.so")
-SEGMENTS_SOURCES = ("segments.hip",)
-# the companion library of offline scoring (deque mean, threshold sweep, event list), on the same terms
-SCORE_LIB = os.path.join(HERE, "libcough_amd_score.so")
-SCORE_SOURCES = ("score.hip",)
-# the companion library of the device-side draws (a batch's augmentation records and masks, augmentation from them), on
-# the same terms; it compiles csrc/augment_kernel.h, the kernel augment.hip runs
-DRAWS_LIB = os.path.join(HERE, "libcough_amd_draws.so")
-DRAWS_SOURCES = ("draws.hip",)
-# the companion library of speed perturbation (the tableless per-row sinc resampler and its draws), on the same terms
-WARP_LIB = os.path.join(HERE, "libcough_amd_warp.so")
-WARP_SOURCES = ("warp.hip",)
-# the companion library of pitch shift (the per-row float64 phase vocoder and its draws), on the same terms
-PITCH_LIB = os.path.join(HERE, "libcough_amd_pitch.so")
-PITCH_SOURCES = ("pitch.hip",)
-# the companion library of the soft-target training steps and the batch MixUp, on the same terms.  Its three steps are
-# the training translation units of libcough_amd.so compiled a second time: SOFT_FLAGS only selects which extern "C"
-# functions they emit (the *_forward_backward_soft entry points instead of the v5 ones), so the step code exists once
-SOFT_LIB = os.path.join(HERE, "libcough_amd_soft.so")
-SOFT_SOURCES = ("soft.hip",)
+# The three steps of the soft-target library are the training translation units of libcough_amd.so compiled a second
+# time: SOFT_FLAGS only selects which extern "C" functions they emit (the *_forward_backward_soft entry points instead
+# of the v5 ones), so the step code exists once
 SOFT_SHARED_SOURCES = ("train.hip", "train_small.hip", "train_std.hip")
 SOFT_FLAGS = ("-DCOUGH_SOFT_EXPORTS",)
+# A unit is a source name, or (source, extra flags, object suffix).  include/cough_amd.h stays at ABI v5 with its 53
+# entry points, so what came after it is exported from companion libraries: same flags, a version script of their own
+UNITS = {
+    "amd": SOURCES,
+    "loop": ("loop.hip",),          # the epoch loop's meter
+    "data": ("data.hip",),          # the input pipeline: the device-resident dataset and batch loader
+    "segments": ("segments.hip",),  # corpus curation: frame energies, segment picking
+    "score": ("score.hip",),        # offline scoring: deque mean, threshold sweep, event list
+    # the device-side draws: a batch's augmentation records and masks, augmentation from them; it compiles
+    # csrc/augment_kernel.h, the kernel augment.hip runs
+    "draws": ("draws.hip",),
+    # the soft-target training steps and the batch MixUp
+    "soft": ("soft.hip",) + tuple((src, SOFT_FLAGS, "_soft") for src in SOFT_SHARED_SOURCES),
+    "warp": ("warp.hip",),          # speed perturbation: the tableless per-row sinc resampler and its draws
+    "pitch": ("pitch.hip",),        # pitch shift: the per-row float64 phase vocoder and its draws
+}
+
+
+def _named(stem: str, name: str, ext: str) -> str:
+    return stem + ("" if name == "amd" else "_" + name) + ext
+
+
+LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}
+LIB = LIBS["amd"]
 # -fno-slp-vectorize: left alone, -O3 packs adjacent f32 adds / multiplies of the FFT butterflies into v_pk_*_f32, which issue
 # slower than the two scalar operations they replace on gfx950 (same-box A/B: K1 -2.4 %, STFT stage -3.2 %, classifier unchanged;
 # profiles/r04_flag_ab.txt)
@@ -74,27 +66,24 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (need ROCm with gfx950 support)")
 
 
+def _version_script(name: str) -> str:
+    return os.path.join(CSRC, _named("exports", name, ".map"))
+
+
 def _headers_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps += [os.path.join(HERE, "..", "include", h) for h in ("cough_amd.h", "cough_amd_loop.h", "cough_amd_data.h",
-                                                                   "cough_amd_segments.h", "cough_amd_score.h",
-                                                                   "cough_amd_draws.h", "cough_amd_soft.h",
-                                                                   "cough_amd_warp.h", "cough_amd_pitch.h")]
+    deps += [os.path.join(HERE, "..", "include", _named("cough_amd", name, ".h")) for name in UNITS]
     deps.append(os.path.abspath(__file__))   # the flags live here
-    deps += [os.path.join(CSRC, m) for m in ("exports.map", "exports_loop.map", "exports_data.map", "exports_segments.map",
-                                             "exports_score.map", "exports_draws.map", "exports_soft.map",
-                                             "exports_warp.map", "exports_pitch.map")]
+    deps += [_version_script(name) for name in UNITS]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    libs = (LIB, LOOP_LIB, DATA_LIB, SEGMENTS_LIB, SCORE_LIB, DRAWS_LIB, SOFT_LIB, WARP_LIB, PITCH_LIB)
-    if not all(os.path.exists(p) for p in libs):
+    if not all(os.path.exists(p) for p in LIBS.values()):
         return True
-    t = min(os.path.getmtime(p) for p in libs)
-    return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t
-                                       for s in SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                       + DRAWS_SOURCES + SOFT_SOURCES + WARP_SOURCES + PITCH_SOURCES)
+    t = min(os.path.getmtime(p) for p in LIBS.values())
+    sources = {u if isinstance(u, str) else u[0] for units in UNITS.values() for u in units}
+    return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in sources)
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB) -> str:
@@ -107,8 +96,8 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
     os.makedirs(objdir, exist_ok=True)
     hdr = _headers_mtime()
 
-    def compile_one(job) -> str:
-        src, flags, suffix = job if isinstance(job, tuple) else (job, (), "")
+    def compile_one(unit) -> str:
+        src, flags, suffix = unit if isinstance(unit, tuple) else (unit, (), "")
         s, o = os.path.join(CSRC, src), os.path.join(objdir, src.replace(".hip", suffix + ".o"))
         if force or not os.path.exists(o) or os.path.getmtime(o) < max(hdr, os.path.getmtime(s)):
             cmd = [hipcc, *CFLAGS, *extra_flags, *flags, "-c", s, "-o", o]
@@ -117,35 +106,16 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
             subprocess.run(cmd, check=True)
         return o
 
-    def link(objs, version_script: str, target: str) -> None:
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-               "-Wl,--version-script=" + os.path.join(CSRC, version_script), "-o", target, *objs]
+    targets = {"amd": out} if extra_flags or out != LIB else LIBS
+    units = [u for name in targets for u in UNITS[name]]
+    with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1)) as pool:
+        obj = dict(zip(units, pool.map(compile_one, units)))
+    for name, target in targets.items():
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + _version_script(name),
+               "-o", target, *(obj[u] for u in UNITS[name])]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-
-    variant = bool(extra_flags) or out != LIB
-    sources = SOURCES if variant else (SOURCES + LOOP_SOURCES + DATA_SOURCES + SEGMENTS_SOURCES + SCORE_SOURCES
-                                      + DRAWS_SOURCES + WARP_SOURCES + PITCH_SOURCES + SOFT_SOURCES
-                                      + tuple((src, SOFT_FLAGS, "_soft") for src in SOFT_SHARED_SOURCES))
-    with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
-        objs = list(pool.map(compile_one, sources))
-    link(objs[:len(SOURCES)], "exports.map", out)
-    if not variant:
-        link(objs[len(SOURCES):len(SOURCES) + len(LOOP_SOURCES)], "exports_loop.map", LOOP_LIB)
-        data_end = len(SOURCES) + len(LOOP_SOURCES) + len(DATA_SOURCES)
-        link(objs[len(SOURCES) + len(LOOP_SOURCES):data_end], "exports_data.map", DATA_LIB)
-        segments_end = data_end + len(SEGMENTS_SOURCES)
-        link(objs[data_end:segments_end], "exports_segments.map", SEGMENTS_LIB)
-        score_end = segments_end + len(SCORE_SOURCES)
-        link(objs[segments_end:score_end], "exports_score.map", SCORE_LIB)
-        draws_end = score_end + len(DRAWS_SOURCES)
-        link(objs[score_end:draws_end], "exports_draws.map", DRAWS_LIB)
-        warp_end = draws_end + len(WARP_SOURCES)
-        link(objs[draws_end:warp_end], "exports_warp.map", WARP_LIB)
-        pitch_end = warp_end + len(PITCH_SOURCES)
-        link(objs[warp_end:pitch_end], "exports_pitch.map", PITCH_LIB)
-        link(objs[pitch_end:], "exports_soft.map", SOFT_LIB)
     return out
 
 

@@ -11,6 +11,26 @@ namespace cough {
 
 void set_error(const char* fmt, ...);
 
+// A library's last-error slot, defined once per shared library at global scope of the unit that owns it: the
+// thread-local message buffer, the set_error every unit of that library links against, and the C entry point that
+// reads the buffer.  Each library keeps a slot of its own, so the messages of two libraries stay apart.
+#define COUGH_DEFINE_LAST_ERROR(entry_point)                                  \
+    namespace cough {                                                         \
+    namespace {                                                               \
+    thread_local char g_last_error[512] = "";                                 \
+    }                                                                         \
+    void set_error(const char* fmt, ...) {                                    \
+        va_list ap;                                                           \
+        va_start(ap, fmt);                                                    \
+        vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);               \
+        va_end(ap);                                                           \
+    }                                                                         \
+    }                                                                         \
+    extern "C" const char* entry_point(void) { return cough::g_last_error; }
+
+// the address p is a multiple of a (a power of two); nullptr is aligned to everything
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
+
 #define COUGH_HIP_CHECK(expr)                                                              \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \

@@ -18,16 +18,6 @@
 
 namespace cough {
 
-thread_local char g_data_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_data_err, sizeof(g_data_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int GT = 256;        // threads of the gather and mask kernels
@@ -200,8 +190,6 @@ __global__ __launch_bounds__(GT) void mask_images_kernel(const float* in, float*
     if (gt < hw - done) one(done + gt);
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 // workgroups per row for `groups` float4 groups of GT threads each: all of them up to MAX_CHUNKS
 unsigned chunks_for(long long groups) { return unsigned(std::clamp<long long>((groups + GT - 1) / GT, 1, MAX_CHUNKS)); }
 
@@ -209,7 +197,8 @@ unsigned chunks_for(long long groups) { return unsigned(std::clamp<long long>((g
 }  // namespace cough
 
 extern "C" int cough_data_abi_version(void) { return COUGH_DATA_ABI_VERSION; }
-extern "C" const char* cough_data_last_error(void) { return cough::g_data_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_data_last_error)
 
 extern "C" int cough_gather_rows(const float* d_src, const long long* d_row_offsets, const int* d_lengths, int n_rows,
                                  float* d_out, long long out_stride, int row_len, void* stream) {

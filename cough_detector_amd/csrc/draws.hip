@@ -16,16 +16,6 @@
 
 namespace cough {
 
-thread_local char g_draws_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_draws_err, sizeof(g_draws_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 #include "augment_kernel.h"
@@ -151,13 +141,12 @@ __global__ __launch_bounds__(DT) void resolve_kernel(const cough_aug_clip* __res
     recs[b] = r;
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace cough
 
 extern "C" int cough_draws_abi_version(void) { return COUGH_DRAWS_ABI_VERSION; }
-extern "C" const char* cough_draws_last_error(void) { return cough::g_draws_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_draws_last_error)
 
 extern "C" int cough_draw_batch(unsigned long long seed, int n_rows, const int* d_lengths, double p_augment, int n_bank,
                                 const int* d_bank_lengths, double spec_p, int n_freq_masks, int freq_mask_param,

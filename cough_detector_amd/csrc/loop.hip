@@ -6,16 +6,6 @@
 
 namespace cough {
 
-thread_local char g_loop_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_loop_err, sizeof(g_loop_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 static_assert(sizeof(cough_epoch_meter) == COUGH_EPOCH_METER_BYTES, "cough_epoch_meter is 64 bytes");
@@ -81,13 +71,12 @@ __global__ __launch_bounds__(NT) void epoch_meter_kernel(const float* __restrict
     }
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace cough
 
 extern "C" int cough_loop_abi_version(void) { return COUGH_LOOP_ABI_VERSION; }
-extern "C" const char* cough_loop_last_error(void) { return cough::g_loop_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_loop_last_error)
 
 extern "C" int cough_epoch_meter_update(const float* d_logits, const long long* d_targets, int n_clips,
                                         const float* d_class_weights, const float* d_batch_loss,

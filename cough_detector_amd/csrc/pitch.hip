@@ -26,16 +26,6 @@
 
 namespace cough {
 
-thread_local char g_pitch_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_pitch_err, sizeof(g_pitch_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int PT = 256;                        // threads of the stretch kernel: one butterfly each
@@ -288,13 +278,12 @@ __global__ __launch_bounds__(DT) void draw_pitch_kernel(unsigned long long seed,
     stretch_lengths[row] = n_s;
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace cough
 
 extern "C" int cough_pitch_abi_version(void) { return COUGH_PITCH_ABI_VERSION; }
-extern "C" const char* cough_pitch_last_error(void) { return cough::g_pitch_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_pitch_last_error)
 
 extern "C" int cough_stretch_rows(const float* d_src, const long long* d_row_offsets, const int* d_lengths, int n_rows,
                                   const cough_stretch_plan* d_plans, float* d_out, int n_samples, int* d_new_lengths,

@@ -25,16 +25,6 @@
 
 namespace cough {
 
-thread_local char g_score_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_score_err, sizeof(g_score_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int ST = 256;                               // threads of the smoothing kernel
@@ -208,13 +198,12 @@ __global__ __launch_bounds__(64 * WPB) void list_events_kernel(const double* __r
     }
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace cough
 
 extern "C" int cough_score_abi_version(void) { return COUGH_SCORE_ABI_VERSION; }
-extern "C" const char* cough_score_last_error(void) { return cough::g_score_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_score_last_error)
 
 extern "C" int cough_smooth_windows(const float* d_prob, const long long* d_window_offsets, int n_clips, long long n_windows,
                                     int smoothing_window, double* d_smoothed, void* stream) {

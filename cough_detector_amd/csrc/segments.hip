@@ -27,16 +27,6 @@
 
 namespace cough {
 
-thread_local char g_segments_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_segments_err, sizeof(g_segments_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int ET = 256;              // threads of the energy kernel
@@ -313,8 +303,6 @@ __global__ __launch_bounds__(CT) void copy_segments_kernel(const float* __restri
     if (gt < len - done) o[done + gt] = in[done + gt];
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 bool frame_pair_ok(int frame_length, int hop_length) {
     return frame_length >= 1 && hop_length >= 1 && frame_length <= COUGH_MAX_FRAME_LENGTH;
 }
@@ -323,7 +311,8 @@ bool frame_pair_ok(int frame_length, int hop_length) {
 }  // namespace cough
 
 extern "C" int cough_segments_abi_version(void) { return COUGH_SEGMENTS_ABI_VERSION; }
-extern "C" const char* cough_segments_last_error(void) { return cough::g_segments_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_segments_last_error)
 
 extern "C" int cough_frame_energy_tile_frames(int frame_length, int hop_length) {
     using namespace cough;

@@ -18,16 +18,6 @@
 
 namespace cough {
 
-thread_local char g_soft_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_soft_err, sizeof(g_soft_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int MIX_THREADS = 256;
@@ -93,7 +83,8 @@ __global__ __launch_bounds__(MIX_THREADS) void mix_batch_kernel(const float* __r
 }  // namespace cough
 
 extern "C" int cough_soft_abi_version(void) { return COUGH_SOFT_ABI_VERSION; }
-extern "C" const char* cough_soft_last_error(void) { return cough::g_soft_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_soft_last_error)
 
 extern "C" int cough_mix_batch(const float* d_x, const long long* d_labels, const int* d_perm, const float* d_coef, int n_rows,
                                long long row_len, float* d_out, float* d_soft, void* stream) {

@@ -22,16 +22,6 @@
 
 namespace cough {
 
-thread_local char g_warp_err[512] = "";
-
-// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_warp_err, sizeof(g_warp_err), fmt, ap);
-    va_end(ap);
-}
-
 namespace {
 
 constexpr int WARP_THREADS = 256;
@@ -186,13 +176,12 @@ __global__ __launch_bounds__(DT) void clear_shifts_kernel(cough_aug_clip* __rest
     if (row < n_rows) clips[row].shift = 0;
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace cough
 
 extern "C" int cough_warp_abi_version(void) { return COUGH_WARP_ABI_VERSION; }
-extern "C" const char* cough_warp_last_error(void) { return cough::g_warp_err; }
+// this library's own last-error slot (libcough_amd.so keeps its own behind cough_amd_last_error)
+COUGH_DEFINE_LAST_ERROR(cough_warp_last_error)
 
 extern "C" int cough_warp_rows(const float* d_src, const long long* d_row_offsets, const int* d_lengths, int n_rows,
                                const cough_warp_plan* d_plans, float* d_out, int n_samples, int* d_new_lengths, void* stream) {

@@ -56,31 +56,6 @@ def test_the_other_libraries_are_untouched():
             assert s not in text, (header, s)
 
 
-def test_the_build_covers_the_data_sources(monkeypatch):
-    assert cbuild.DATA_SOURCES == ("data.hip",) and os.path.basename(cbuild.DATA_LIB) == "libcough_amd_data.so"
-    assert os.path.dirname(cbuild.DATA_LIB) == os.path.dirname(cbuild.LIB)
-    assert cbuild.LOOP_SOURCES == ("loop.hip",)
-    for s in cbuild.DATA_SOURCES + ("exports_data.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    assert os.path.exists(cbuild.DATA_LIB)
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("data.hip", "exports_data.map", "cough_amd_data.h", "common.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "DATA_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_data.so"))
-    assert cbuild.is_stale()
-
-
-def test_a_missing_data_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_data_lib", None)
-    monkeypatch.setattr(_lib, "DATA_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_data.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_data()
-
-
 FAKE = 1 << 20
 
 

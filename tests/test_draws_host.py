@@ -61,27 +61,6 @@ def test_the_other_five_libraries_are_untouched():
             assert s not in text, (header, s)
 
 
-def test_the_build_covers_the_draws_sources(monkeypatch):
-    assert cbuild.DRAWS_SOURCES == ("draws.hip",)
-    assert os.path.basename(cbuild.DRAWS_LIB) == "libcough_amd_draws.so"
-    assert os.path.dirname(cbuild.DRAWS_LIB) == os.path.dirname(cbuild.LIB)
-    assert cbuild.LOOP_SOURCES == ("loop.hip",) and cbuild.DATA_SOURCES == ("data.hip",) and len(cbuild.SOURCES) == 12
-    assert cbuild.SEGMENTS_SOURCES == ("segments.hip",) and cbuild.SCORE_SOURCES == ("score.hip",)
-    for s in cbuild.DRAWS_SOURCES + ("exports_draws.map", "augment_kernel.h"):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    for lib in (cbuild.LIB, cbuild.LOOP_LIB, cbuild.DATA_LIB, cbuild.SEGMENTS_LIB, cbuild.SCORE_LIB, cbuild.DRAWS_LIB):
-        assert os.path.exists(lib), lib
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("draws.hip", "exports_draws.map", "cough_amd_draws.h", "augment_kernel.h", "philox.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "DRAWS_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_draws.so"))
-    assert cbuild.is_stale()
-
-
 def test_both_libraries_compile_one_augment_kernel():
     src = lambda name: open(os.path.join(cbuild.CSRC, name)).read()      # noqa: E731
     for name in ("augment.hip", "draws.hip"):
@@ -89,13 +68,6 @@ def test_both_libraries_compile_one_augment_kernel():
         assert '#include "augment_kernel.h"' in text, name
         assert "void augment_kernel(" not in text and "struct AugRec" not in text, name
     assert src("augment_kernel.h").count("void augment_kernel(") == 1
-
-
-def test_a_missing_draws_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_draws_lib", None)
-    monkeypatch.setattr(_lib, "DRAWS_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_draws.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_draws()
 
 
 FAKE = 1 << 20

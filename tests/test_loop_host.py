@@ -46,31 +46,6 @@ def test_the_main_library_is_untouched_by_the_companion():
         assert s not in main_header
 
 
-def test_the_build_covers_the_new_sources(monkeypatch):
-    assert cbuild.LOOP_SOURCES == ("loop.hip",) and os.path.basename(cbuild.LOOP_LIB) == "libcough_amd_loop.so"
-    assert os.path.dirname(cbuild.LOOP_LIB) == os.path.dirname(cbuild.LIB)
-    for s in cbuild.LOOP_SOURCES + ("exports_loop.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    assert os.path.exists(cbuild.LIB) and os.path.exists(cbuild.LOOP_LIB)
-    # the staleness check: every file at time 1 is up to date; the new source, version script or header at time 2 is not
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("loop.hip", "exports_loop.map", "cough_amd_loop.h", "train_common.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "LOOP_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_loop.so"))
-    assert cbuild.is_stale()
-
-
-def test_a_missing_companion_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_loop_lib", None)
-    monkeypatch.setattr(_lib, "LOOP_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_loop.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_loop()
-
-
 def test_meter_update_refuses_bad_arguments_without_a_gpu():
     lib = _lib.load_loop()
     fake = 1 << 20

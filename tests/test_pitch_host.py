@@ -168,23 +168,6 @@ def test_pitch_library_exports_exactly_its_header():
         assert _exported(path) == set(names) and not set(names) & declared
 
 
-def test_the_build_covers_the_pitch_sources(monkeypatch):
-    assert cbuild.PITCH_SOURCES == ("pitch.hip",) and os.path.basename(cbuild.PITCH_LIB) == "libcough_amd_pitch.so"
-    assert os.path.dirname(cbuild.PITCH_LIB) == os.path.dirname(cbuild.LIB) and os.path.exists(cbuild.PITCH_LIB)
-    assert len(cbuild.SOURCES) == 12 and "pitch.hip" not in cbuild.SOURCES
-    for s in cbuild.PITCH_SOURCES + ("exports_pitch.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("pitch.hip", "exports_pitch.map", "cough_amd_pitch.h", "cough_amd_warp.h", "philox.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "PITCH_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_pitch.so"))
-    assert cbuild.is_stale()
-
-
 def test_every_library_links_its_own_objects(monkeypatch, tmp_path):
     # the link step's slices of the object list: each library gets exactly the objects of its sources
     links = []
@@ -203,13 +186,6 @@ def test_every_library_links_its_own_objects(monkeypatch, tmp_path):
     assert got["libcough_amd_warp.so"] == ["warp.o"] and got["libcough_amd_draws.so"] == ["draws.o"]
     assert got["libcough_amd_soft.so"] == ["soft.o", "train_soft.o", "train_small_soft.o", "train_std_soft.o"]
     assert len(got) == 9 and sum(len(v) for v in got.values()) == 12 + 7 + 4
-
-
-def test_a_missing_pitch_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_pitch_lib", None)
-    monkeypatch.setattr(_lib, "PITCH_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_pitch.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_pitch()
 
 
 FAKE = 1 << 20

@@ -60,34 +60,6 @@ def test_the_other_four_libraries_are_untouched():
             assert s not in text, (header, s)
 
 
-def test_the_build_covers_the_score_sources(monkeypatch):
-    assert cbuild.SCORE_SOURCES == ("score.hip",)
-    assert os.path.basename(cbuild.SCORE_LIB) == "libcough_amd_score.so"
-    assert os.path.dirname(cbuild.SCORE_LIB) == os.path.dirname(cbuild.LIB)
-    assert cbuild.LOOP_SOURCES == ("loop.hip",) and cbuild.DATA_SOURCES == ("data.hip",) and len(cbuild.SOURCES) == 12
-    assert cbuild.SEGMENTS_SOURCES == ("segments.hip",)
-    for s in cbuild.SCORE_SOURCES + ("exports_score.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    for lib in (cbuild.LIB, cbuild.LOOP_LIB, cbuild.DATA_LIB, cbuild.SEGMENTS_LIB, cbuild.SCORE_LIB):
-        assert os.path.exists(lib), lib
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("score.hip", "exports_score.map", "cough_amd_score.h", "common.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "SCORE_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_score.so"))
-    assert cbuild.is_stale()
-
-
-def test_a_missing_score_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_score_lib", None)
-    monkeypatch.setattr(_lib, "SCORE_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_score.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_score()
-
-
 FAKE = 1 << 20
 
 

@@ -54,33 +54,6 @@ def test_the_other_three_libraries_are_untouched():
             assert s not in text, (header, s)
 
 
-def test_the_build_covers_the_segments_sources(monkeypatch):
-    assert cbuild.SEGMENTS_SOURCES == ("segments.hip",)
-    assert os.path.basename(cbuild.SEGMENTS_LIB) == "libcough_amd_segments.so"
-    assert os.path.dirname(cbuild.SEGMENTS_LIB) == os.path.dirname(cbuild.LIB)
-    assert cbuild.LOOP_SOURCES == ("loop.hip",) and cbuild.DATA_SOURCES == ("data.hip",) and len(cbuild.SOURCES) == 12
-    for s in cbuild.SEGMENTS_SOURCES + ("exports_segments.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    for lib in (cbuild.LIB, cbuild.LOOP_LIB, cbuild.DATA_LIB, cbuild.SEGMENTS_LIB):
-        assert os.path.exists(lib), lib
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("segments.hip", "exports_segments.map", "cough_amd_segments.h", "common.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "SEGMENTS_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_segments.so"))
-    assert cbuild.is_stale()
-
-
-def test_a_missing_segments_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_segments_lib", None)
-    monkeypatch.setattr(_lib, "SEGMENTS_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_segments.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_segments()
-
-
 FAKE = 1 << 20
 
 

@@ -63,31 +63,6 @@ def test_the_other_six_libraries_are_untouched():
             assert s not in text, (header, s)
 
 
-def test_the_build_covers_the_soft_sources(monkeypatch):
-    assert cbuild.SOFT_SOURCES == ("soft.hip",) and os.path.basename(cbuild.SOFT_LIB) == "libcough_amd_soft.so"
-    assert cbuild.SOFT_SHARED_SOURCES == ("train.hip", "train_small.hip", "train_std.hip") and len(cbuild.SOURCES) == 12
-    assert set(cbuild.SOFT_SHARED_SOURCES) <= set(cbuild.SOURCES)         # the step code exists once
-    assert os.path.dirname(cbuild.SOFT_LIB) == os.path.dirname(cbuild.LIB) and os.path.exists(cbuild.SOFT_LIB)
-    for s in cbuild.SOFT_SOURCES + ("exports_soft.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("soft.hip", "exports_soft.map", "cough_amd_soft.h", "train_common.h", "train_std.hip"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "SOFT_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_soft.so"))
-    assert cbuild.is_stale()
-
-
-def test_a_missing_soft_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_soft_lib", None)
-    monkeypatch.setattr(_lib, "SOFT_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_soft.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_soft()
-
-
 @pytest.mark.parametrize("model", ["residual", "small", "standard"])
 def test_soft_steps_refuse_bad_arguments_without_a_gpu(model):
     lib, hard = _lib.load_soft(), _lib.load()

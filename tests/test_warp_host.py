@@ -154,34 +154,10 @@ def test_the_other_seven_libraries_are_untouched():
     assert _lib.load().cough_amd_abi_version() == 5 and _lib.load_draws().cough_draws_abi_version() == 1
 
 
-def test_the_build_covers_the_warp_sources(monkeypatch):
-    assert cbuild.WARP_SOURCES == ("warp.hip",) and os.path.basename(cbuild.WARP_LIB) == "libcough_amd_warp.so"
-    assert os.path.dirname(cbuild.WARP_LIB) == os.path.dirname(cbuild.LIB) and os.path.exists(cbuild.WARP_LIB)
-    assert len(cbuild.SOURCES) == 12 and "warp.hip" not in cbuild.SOURCES
-    for s in cbuild.WARP_SOURCES + ("exports_warp.map",):
-        assert os.path.exists(os.path.join(cbuild.CSRC, s)), s
-    newer = []
-    monkeypatch.setattr(cbuild.os.path, "getmtime", lambda p: 2.0 if os.path.basename(p) in newer else 1.0)
-    assert not cbuild.is_stale()
-    for name in ("warp.hip", "exports_warp.map", "cough_amd_warp.h", "philox.h"):
-        newer[:] = [name]
-        assert cbuild.is_stale(), name
-    newer[:] = []
-    monkeypatch.setattr(cbuild, "WARP_LIB", os.path.join(ROOT, "no_such_dir", "libcough_amd_warp.so"))
-    assert cbuild.is_stale()
-
-
 def test_the_augment_kernel_header_is_as_it_was():
     text = open(os.path.join(cbuild.CSRC, "augment_kernel.h")).read()
     assert "speed_perturbation is the identity" in text       # the resampler runs before it, with its shift; it is unchanged
     assert "augment_kernel" not in open(os.path.join(cbuild.CSRC, "warp.hip")).read()
-
-
-def test_a_missing_warp_library_is_an_error(monkeypatch):
-    monkeypatch.setattr(_lib, "_warp_lib", None)
-    monkeypatch.setattr(_lib, "WARP_LIB_PATH", os.path.join(ROOT, "no_such_dir", "libcough_amd_warp.so"))
-    with pytest.raises(RuntimeError, match=r"is missing: the HIP extension is not built\. Run `python -m cough_detector_amd\.build`"):
-        _lib.load_warp()
 
 
 FAKE = 1 << 20

@@ -29,7 +29,7 @@ def main():
         cmd = [build._hipcc(), *build.FLAGS, "-DCOUGH_K1_STAMPS", "-o", LIB] + \
               [os.path.join(build.CSRC, s) for s in build.SOURCES]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    _lib.LIB_PATH = LIB
+    _lib.LIBRARIES["amd"].path = LIB
     import cough_detector_amd as cda
     lib = _lib.load()
     B = 4096

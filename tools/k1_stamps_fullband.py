@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from cough_detector_amd import _lib, synth  # noqa: E402
 
-_lib.LIB_PATH = os.path.abspath(os.environ.get("K1_STAMPS_LIB", os.path.join(ROOT, "build_ab", "lib_stamps.so")))
+_lib.LIBRARIES["amd"].path = os.path.abspath(os.environ.get("K1_STAMPS_LIB", os.path.join(ROOT, "build_ab", "lib_stamps.so")))
 import cough_detector_amd as cda  # noqa: E402
 
 NAMES = ["prologue", "P1 frames (wave 0)", "P1 wait for slowest wave", "P2 floor + mel rows out", "P2 DCT + mean + std",

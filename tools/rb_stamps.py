@@ -9,7 +9,7 @@ LIB = os.path.join(ROOT, "gpurun_out", "libcough_amd_stamps.so")
 NAMES = ["stage (issue+LDS writes)", "barrier wait", "conv1 k-steps", "h write + barrier", "conv2 k-steps", "epilogue"]
 os.makedirs(os.path.dirname(LIB), exist_ok=True)
 subprocess.run([build._hipcc(), *build.FLAGS, "-DCOUGH_K1_STAMPS", "-o", LIB] + [os.path.join(build.CSRC, s) for s in build.SOURCES], check=True, stderr=subprocess.DEVNULL)
-_lib.LIB_PATH = LIB
+_lib.LIBRARIES["amd"].path = LIB
 import cough_detector_amd as cda
 lib = _lib.load()
 B = 4096

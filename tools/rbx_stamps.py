@@ -14,7 +14,7 @@ if os.environ.get("RBX_STAMPS_LIB"):      # a library prebuilt with -DCOUGH_K1_S
     print("==", os.path.basename(LIB))
 else:
     subprocess.run([build._hipcc(), *build.FLAGS, "-DCOUGH_K1_STAMPS", "-o", LIB] + [os.path.join(build.CSRC, s) for s in build.SOURCES], check=True, stderr=subprocess.DEVNULL)
-_lib.LIB_PATH = LIB
+_lib.LIBRARIES["amd"].path = LIB
 import cough_detector_amd as cda
 lib = _lib.load()
 B = int(os.environ.get("RBX_STAMPS_B", "4096"))

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from cough_detector_amd import _lib, synth  # noqa: E402
 
-_lib.LIB_PATH = os.path.abspath(os.environ["K1_STAMPS_LIB"])
+_lib.LIBRARIES["amd"].path = os.path.abspath(os.environ["K1_STAMPS_LIB"])
 import cough_detector_amd as cda  # noqa: E402
 
 NAMES = ["clip start -> round-0 samples landed (vmcnt)", "-> window, radix-16, twiddle, two transposes", "-> round-1 DMA issued",
