@@ -28,6 +28,24 @@ def _current_stream(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
+_stream = _current_stream           # what a launch takes as its stream
+
+
+def _on_gpu(who: str, **tensors) -> torch.device:
+    """The GPU on which every ``name=(tensor, dtype)`` lives; refuses a tensor that is not contiguous, not of its dtype or
+    not on the device of the others, and tensors that are not on a GPU."""
+    dev = None
+    for name, (t, dtype) in tensors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} lives on {t.device}, not on {dev}")
+        dev = t.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the tensors live on {dev}; the kernels need them on the GPU (there is no CPU fallback)")
+    return dev
+
+
 class StreamScratch:
     """A ``torch.uint8`` workspace per (device, current stream), at most ``MAX_STREAM_WORKSPACES`` of them, least recently
     used evicted first.  A buffer is allocated while its own stream is current, so when it is replaced or evicted torch's

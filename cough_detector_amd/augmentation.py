@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from . import _lib, _tables
+from . import chain as _chain
 from . import pitch as _pitch
 from . import warp as _warp
 from ._native import cuda_device
@@ -284,8 +285,7 @@ class AudioAugmentor:
         draws its coin and its semitones behind the speed step and before the gain -- shift, speed, pitch coin,
         semitones, gain, gaussian, bank -- and ``n_steps`` is None when the coin did not fire (0 is a drawn value that
         shifts nothing).  With ``pitch=False`` it draws nothing and ``n_steps`` is None.  The pitch step keeps ``n'``."""
-        c = _lib.CoughAugClip(shift=0, gain=1.0, gaussian=0, bank_index=-1, gaussian_snr_db=0.0, bank_snr_db=0.0,
-                              bank_start=0)
+        c = self._blank()
         c.shift = self._draw_shift(n)
         pair = self._draw_speed() if self.speed else None         # speed=False: speed_perturbation draws nothing
         n = n if pair is None else _warp.warped_length(n, *pair)
@@ -336,65 +336,33 @@ class AudioAugmentor:
                    "cough_augment_waveforms")
         return out.to(x.device)
 
-    def _run_warped(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
-                    pairs: Sequence[Optional[Tuple[int, int]]], gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
-        """``_run`` with the speed step: ``cough_warp_rows`` (shift and resampling; a row without a pair is copied), then
-        ``cough_augment_waveforms`` on the warped rows with the records' shifts zeroed and the lengths ``n'``.  Returns
-        (B, max n').  When no row has a pair the warp launch is skipped and the path is ``_run``'s."""
+    def _run_chain(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
+                   pairs: Optional[Sequence[Optional[Tuple[int, int]]]], steps: Optional[Sequence[Optional[int]]],
+                   gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
+        """``_run`` behind the speed and pitch steps (``cough_detector_amd/chain.py``): ``cough_warp_rows`` when a speed
+        coin fired (shift and resampling; a row without a pair is copied), ``cough_stretch_rows`` and ``cough_warp_rows``
+        when a row has semitones (a row without is copied by both), then ``cough_augment_waveforms`` on the result with
+        the records' shifts zeroed and the lengths ``n'``.  ``pairs`` / ``steps`` are None when the step is switched
+        off.  Returns (B, max n') with a speed step and (B, N) without.  ``gaussian`` is cut to the width of the rows that
+        ``_run`` gets.  When nothing fired the launches are skipped and the path is ``_run``'s."""
         b, n = x.shape
         lens = [int(v) for v in lengths] if lengths is not None else [n] * b
-        new_lens = [l if p is None else _warp.warped_length(l, *p) for l, p in zip(lens, pairs)]
-        width = max(new_lens, default=0)
-        if all(p is None for p in pairs):
-            return self._run(x, clips, lengths, gaussian, seed)[:, :width].contiguous()
-        dev = cuda_device()
-        src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        plans = _warp.plan_array([(c.shift,) + (p if p is not None else (1, 1)) for c, p in zip(clips, pairs)])
-        warped = _warp.warp_rows(src, (torch.arange(b, dtype=torch.int64) * n).to(dev),
-                                 torch.tensor(lens, dtype=torch.int32).to(dev), torch.from_numpy(plans).to(dev), width)
-        unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in clips]
-        for c in unshifted:
-            c.shift = 0
-        return self._run(warped, unshifted, new_lens, gaussian, seed).to(x.device)
-
-    def _run_pitched(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
-                     pairs: Optional[Sequence[Optional[Tuple[int, int]]]], steps: Sequence[Optional[int]],
-                     gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
-        """``_run`` with the pitch step (and the speed step before it): ``cough_warp_rows`` when a speed coin fired
-        (shift and resampling), then ``cough_stretch_rows`` and ``cough_warp_rows`` (a row without semitones is copied
-        by both; the time shift rides in the stretch's read when no speed step ran before it), then
-        ``cough_augment_waveforms`` on the result with the records' shifts zeroed.  Returns (B, max n') with
-        ``speed=True`` and (B, N) without.  When no row has semitones the path is ``_run_warped``'s or ``_run``'s."""
-        b, n = x.shape
-        pairs = list(pairs) if pairs is not None else [None] * b
-        if not any(steps):
-            if self.speed:
-                return self._run_warped(x, clips, lengths, pairs, gaussian, seed)
-            return self._run(x, clips, lengths, gaussian, seed)
-        lens = [int(v) for v in lengths] if lengths is not None else [n] * b
-        new_lens = [l if p is None else _warp.warped_length(l, *p) for l, p in zip(lens, pairs)]
-        width = max(new_lens) if self.speed else n
-        dev = cuda_device()
-        src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        offsets, shifts = (torch.arange(b, dtype=torch.int64) * n).to(dev), [c.shift for c in clips]
-        if any(p is not None for p in pairs):
-            plans = _warp.plan_array([(s,) + (p if p is not None else (1, 1)) for s, p in zip(shifts, pairs)])
-            src = _warp.warp_rows(src, offsets, torch.tensor(lens, dtype=torch.int32).to(dev), torch.from_numpy(plans).to(dev),
-                                  width)
-            offsets, shifts = (torch.arange(b, dtype=torch.int64) * width).to(dev), [0] * b
-        rates = [_pitch.pitch_rate(s) if s else 1.0 for s in steps]
-        stretch = _pitch.plan_array(list(zip(shifts, rates)))
-        back = _warp.plan_array([(0,) + (_pitch.pitch_rate_pair(s, self.sample_rate) if s else (1, 1)) for s in steps])
-        stretch_width = max(max(_pitch.stretched_length(l, r) for l, r in zip(new_lens, rates)), 1)
-        shifted = _pitch.pitch_shift_rows(src.reshape(-1), offsets, torch.tensor(new_lens, dtype=torch.int32).to(dev),
-                                          torch.from_numpy(stretch).to(dev), torch.from_numpy(back).to(dev), width,
-                                          stretch_width)
-        unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in clips]
-        for c in unshifted:
-            c.shift = 0
+        plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n)
+        width = plans.width if plans.arrays else n
         if gaussian is not None and gaussian.shape[1] != width:
             gaussian = gaussian[:, :width].contiguous()
-        return self._run(shifted, unshifted, new_lens, gaussian, seed).to(x.device)
+        if not plans.arrays:                             # nothing fired: the records keep their shifts
+            out = self._run(x, clips, lengths, gaussian, seed)
+            return out[:, :plans.width].contiguous() if pairs is not None else out
+        dev = cuda_device()
+        src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        a, put = plans.arrays, lambda v: torch.from_numpy(v).to(dev)      # noqa: E731
+        both = "warp" in a and "stretch" in a            # the pitch step then reads the speed step's (B, width) output
+        speed = (put(a["warp"]), put(a["new_lengths"]) if both else None, plans.width) if "warp" in a else None
+        pitch = (put(a["stretch"]), put(a["back"]), plans.stretch_width, plans.width) if "stretch" in a else None
+        rows, _, _ = _chain.run(src.reshape(-1), _chain.dense_offsets(b, n, dev), torch.tensor(lens, dtype=torch.int32).to(dev),
+                                speed, pitch, _chain.dense_offsets(b, plans.width, dev) if both else None)
+        return self._run(rows, _chain.unshifted(clips), plans.new_lengths, gaussian, seed).to(x.device)
 
     @staticmethod
     def _one_clip(waveform: torch.Tensor, who: str) -> None:
@@ -433,7 +401,7 @@ class AudioAugmentor:
         if pair is None:
             return waveform
         self._one_clip(waveform, "speed_perturbation")
-        return self._run_warped(waveform, [self._blank()], None, [pair], None, 0).to(waveform.dtype)
+        return self._run_chain(waveform, [self._blank()], None, [pair], None, None, 0).to(waveform.dtype)
 
     def add_noise(self, waveform: torch.Tensor, snr_range: Tuple[float, float] = _BANK_SNR) -> torch.Tensor:
         self._one_clip(waveform, "add_noise")
@@ -478,18 +446,16 @@ class AudioAugmentor:
         if not steps:
             return waveform
         self._one_clip(waveform, "pitch_shift")
-        return self._run_pitched(waveform, [self._blank()], None, None, [steps], None, 0).to(waveform.dtype)
+        return self._run_chain(waveform, [self._blank()], None, None, [steps], None, 0).to(waveform.dtype)
 
     def augment(self, waveform: torch.Tensor) -> torch.Tensor:
         """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
         self._one_clip(waveform, "augment")
         c, pair, n_new, steps = self.draw_item_pitched(waveform.shape[1])
-        if steps:                                                # the pitch step fired: (1, n')
+        if steps or pair is not None:                            # the pitch or the speed step fired: (1, n')
             gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
-            return self._run_pitched(waveform, [c], None, [pair], [steps], gaussian, 0).to(waveform.dtype)
-        if pair is not None:                                     # the speed step fired: (1, n')
-            gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
-            return self._run_warped(waveform, [c], None, [pair], gaussian, 0).to(waveform.dtype)
+            return self._run_chain(waveform, [c], None, [pair] if self.speed else None, [steps], gaussian,
+                                   0).to(waveform.dtype)
         if c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
             return waveform
         return self._single(waveform, c)
@@ -516,35 +482,20 @@ class AudioAugmentor:
             lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
             if len(lengths) != b or any(v < 1 or v > n for v in lengths):
                 raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
-        steps = None
-        if not self.speed and not self.pitch:
-            clips = self.draw_batch(lengths if lengths is not None else [n] * b)
-            pairs, new_lens = None, list(lengths) if lengths is not None else [n] * b
-        else:
-            items = [self.draw_item_pitched(v) for v in (lengths if lengths is not None else [n] * b)]
-            clips, pairs, new_lens = [it[0] for it in items], [it[1] for it in items], [it[2] for it in items]
-            if not self.speed:
-                pairs = None
-            if self.pitch and any(it[3] for it in items):
-                steps = [it[3] for it in items]
+        items = [self.draw_item_pitched(v) for v in (lengths if lengths is not None else [n] * b)]
+        clips, new_lens = [it[0] for it in items], [it[2] for it in items]
+        pairs = [it[1] for it in items] if self.speed else None
+        steps = [it[3] for it in items] if self.pitch else None
         gaussian = None
         if noise == "host":
-            # rows of n' samples; the matrix is cut to (B, max n') below when a speed step fired
+            # rows of n' samples; _run_chain cuts the matrix to (B, max n') when a speed step fired
             gaussian = torch.zeros((b, max(new_lens + [n])), dtype=torch.float32)
             for i, c in enumerate(clips):
                 if c.gaussian:
                     gaussian[i, :new_lens[i]] = torch.randn(new_lens[i])
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
-        if steps is not None:
-            out = self._run_pitched(waveforms, clips, lengths, pairs, steps, gaussian, int(seed))
-        elif pairs is None:
-            out = self._run(waveforms, clips, lengths, gaussian, int(seed))
-        else:
-            if gaussian is not None:
-                fired = any(p is not None for p in pairs)
-                gaussian = gaussian[:, :max(new_lens) if fired else n].contiguous()
-            out = self._run_warped(waveforms, clips, lengths, pairs, gaussian, int(seed))
+        out = self._run_chain(waveforms, clips, lengths, pairs, steps, gaussian, int(seed))
         return (out, torch.tensor(new_lens, dtype=torch.int32)) if return_lengths else out
 
 

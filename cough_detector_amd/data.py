@@ -57,18 +57,15 @@ import torch
 from torch.utils.data import RandomSampler, WeightedRandomSampler
 
 from . import _lib
+from . import chain as _chain
 from . import draws as _draws
 from . import pitch as _pitch
 from . import warp as _warp
-from ._native import cuda_device
+from ._native import _stream, cuda_device
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
 
 CLASSES = ["non_cough", "cough"]
 _AUDIO_EXTENSIONS = {".wav", ".mp3", ".flac", ".ogg", ".webm"}      # dataset.py:86
-
-
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _upload(dev: torch.device, i64: np.ndarray, i32: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -91,23 +88,50 @@ def mix_draws(seed: int, b: int, alpha: float) -> Tuple[np.ndarray, np.ndarray]:
     return perm, rng.beta(alpha, alpha, size=b)
 
 
-def _mix_words(n_before: int, perm: np.ndarray, lam: np.ndarray) -> Tuple[np.ndarray, int]:
-    """The int32 words a mixed batch adds to its upload behind ``n_before`` words: padding to an 8-byte boundary, the
-    (b, 2) float32 coefficients, the permutation.  Returns them and the coefficients' word offset."""
-    pad = n_before & 1
-    words = np.concatenate([np.zeros(pad, np.int32), mix_coefficients(lam).reshape(-1).view(np.int32),
-                            np.asarray(perm, dtype=np.int32)])
-    return words, n_before + pad
+_TORCH_DTYPE = {np.float32: torch.float32, np.uint8: torch.uint8}
 
 
-def _pitch_words(n_before: int, stretch: np.ndarray, back: np.ndarray) -> Tuple[np.ndarray, int]:
-    """The int32 words a batch with a pitch step adds to its upload behind ``n_before`` words: padding to an 8-byte
-    boundary, the (b, 16)-byte stretch plans, the (b, 3) int32 plans of the resampling that follows.  Returns them and
-    the stretch plans' word offset."""
-    pad = n_before & 1
-    words = np.concatenate([np.zeros(pad, np.int32), np.ascontiguousarray(stretch).reshape(-1).view(np.int32),
-                            np.asarray(back, dtype=np.int32).reshape(-1)])
-    return words, n_before + pad
+class UploadWords:
+    """The int32 side of a batch's pinned upload (``_upload``), assembled by name: ``add`` appends an array of 4-byte
+    words (int32, float32, or bytes in fours), behind one word of padding if it has to start on an 8-byte boundary;
+    ``array`` is what travels; ``view`` is an array again, dtype and shape, cut out of the uploaded tensor.  ``lengths``:
+    a flat int32 array that every batch leads with, under that name."""
+
+    def __init__(self, lengths: Optional[np.ndarray] = None):
+        self._parts: List[np.ndarray] = []
+        self._at: Dict[str, tuple] = {}                  # name -> (first word, end, torch dtype, shape); None: as it is
+        self.size = 0
+        if lengths is not None:
+            self._parts.append(lengths)
+            self.size = lengths.size
+            self._at["lengths"] = (0, self.size, None, None)
+
+    def add(self, name: str, array: np.ndarray, align8: bool = False) -> None:
+        words = array.reshape(-1)
+        if words.dtype != np.int32:
+            words = words.view(np.int32)
+        if align8 and self.size & 1:
+            self._parts.append(np.zeros(1, np.int32))
+            self.size += 1
+        self._at[name] = (self.size, self.size + words.size, None if array.dtype == np.int32 else _TORCH_DTYPE[array.dtype.type],
+                          array.shape if array.ndim > 1 else None)
+        self._parts.append(words)
+        self.size += words.size
+
+    def __contains__(self, name: str) -> bool:
+        return name in self._at
+
+    def at(self, name: str) -> int:
+        """The word offset of the array ``name``."""
+        return self._at[name][0]
+
+    def array(self) -> np.ndarray:
+        return self._parts[0] if len(self._parts) == 1 else np.concatenate(self._parts or [np.zeros(0, np.int32)])
+
+    def view(self, i32: torch.Tensor, name: str) -> torch.Tensor:
+        lo, hi, dtype, shape = self._at[name]
+        words = i32[lo:hi] if dtype is None else i32[lo:hi].view(dtype)
+        return words if shape is None else words.view(shape)
 
 
 class DeviceClipBank:
@@ -385,124 +409,104 @@ class DeviceDataLoader:
                 arr[:, b, k] = m
         return arr
 
-    def _features(self, indices: Sequence[int], plan: BatchPlan, i64: torch.Tensor, lens: torch.Tensor,
-                  warp: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
-                  pitch: Optional[Tuple[torch.Tensor, torch.Tensor, int, int]] = None) -> torch.Tensor:
-        """Unmasked features (B, F, T) of the clips ``indices``; ``i64`` holds their bank offsets, then B matrix-row
-        offsets, on the device.  ``warp``: ``(plans, new lengths, width)`` of a batch in which a speed step fired, the
-        first two on the device; the matrix rows are then ``width`` apart.  ``pitch``: ``(stretch plans, resampling
-        plans, stretch width, width)`` of a batch in which a pitch step fired, the first two on the device."""
-        bank, pre, dev = self.bank, self.preprocessor, self.bank.device
-        lib, b = _lib.load_data(), len(indices)
+    def _featurise(self, src: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """Unmasked features (B, F, T) of B rows of the flat buffer ``src``: ``cough_prepare_rows``, the featuriser."""
+        pre, dev, b = self.preprocessor, self.bank.device, lens.numel()
         seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
-        src, offsets = bank.data, i64[:b]
-        if plan.clips is not None and (warp is not None or pitch is not None):
-            host_lens = [int(bank.lengths[i]) for i in indices]
-            if warp is not None:                                     # shift and speed, read in place from the bank
-                plans, lens_new, width = warp
-                src = _warp.warp_rows(bank.data, offsets, lens, plans, width)
-                offsets, lens, host_lens = i64[b:2 * b], lens_new, plan.new_lengths
-            if pitch is not None:                                    # the shift rides in the stretch's read if not in the warp's
-                stretch, back, stretch_width, width = pitch
-                src = _pitch.pitch_shift_rows(src.reshape(-1), offsets, lens, stretch, back, width, stretch_width)
-                offsets = i64[b:2 * b]
-            unshifted = [_lib.CoughAugClip.from_buffer_copy(c) for c in plan.clips]
-            for c in unshifted:
-                c.shift = 0                                          # the first kernel's read has shifted the row
-            gaussian = (plan.gaussian[:, :width].contiguous().to(dev, non_blocking=True) if plan.gaussian is not None
-                        else None)
-            src = self.audio_augmentor._run(src, unshifted, host_lens, gaussian, plan.seed)
-        elif plan.clips is not None:
-            host_lens = [int(bank.lengths[i]) for i in indices]
-            row_len = max(host_lens)
-            rows = torch.empty((b, row_len), dtype=torch.float32, device=dev)
-            _lib.check_data(lib.cough_gather_rows(bank.data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
-                                                  rows.data_ptr(), row_len, row_len, _stream(dev)), "cough_gather_rows")
-            gaussian = plan.gaussian
-            if gaussian is not None and gaussian.shape[1] != row_len:    # drawn for a speed step that did not fire
-                gaussian = gaussian[:, :row_len].contiguous()
-            gaussian = gaussian.to(dev, non_blocking=True) if gaussian is not None else None
-            src = self.audio_augmentor._run(rows, plan.clips, host_lens, gaussian, plan.seed)
-            offsets = i64[b:2 * b]
-        _lib.check_data(lib.cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b, seg.data_ptr(),
-                                               pre.segment_samples, _lib.PREP_NORMALIZE, _stream(dev)), "cough_prepare_rows")
+        _lib.check_data(_lib.load_data().cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
+                                                            seg.data_ptr(), pre.segment_samples, _lib.PREP_NORMALIZE,
+                                                            _stream(dev)), "cough_prepare_rows")
         return pre.featurize_batch(seg, normalize=False)
 
     def _fill_cache(self) -> None:
         n, f_t = len(self.bank), self.feature_shape()
         self._cache = torch.empty((n,) + f_t, dtype=torch.float32, device=self.bank.device)
         for lo in range(0, n, self.batch_size):
-            idx = list(range(lo, min(lo + self.batch_size, n)))
-            self._cache[lo:lo + len(idx)] = self._features(idx, BatchPlan(), self.bank.offsets_dev[lo:lo + len(idx)],
-                                                            self.bank.lengths_dev[lo:lo + len(idx)])
+            hi = min(lo + self.batch_size, n)
+            self._cache[lo:hi] = self._featurise(self.bank.data, self.bank.offsets_dev[lo:hi], self.bank.lengths_dev[lo:hi])
 
-    def launch_batch(self, indices: Sequence[int], plan: BatchPlan) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Everything of a batch that runs on the device, stream-ordered; nothing here waits for the device."""
-        bank, dev = self.bank, self.bank.device
+    def _head(self, indices: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, UploadWords]:
+        """What both modes start with: the device check, the indices and the clips' lengths on the host, and the upload's
+        int32 words with the lengths in front."""
+        dev = self.bank.device
         if dev.type != "cuda":
             raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
                                "(there is no CPU fallback)")
-        b = len(indices)
         idx = np.asarray(indices, dtype=np.int64)
-        host_lens = bank.lengths.numpy()[idx]
-        row_len = int(host_lens.max())
-        masks = self._mask_arrays(plan.masks) if plan.masks is not None and self._n_masks else np.zeros(0, np.int32)
-        words, mix_at = [host_lens, masks.reshape(-1)], 0
-        if plan.perm is not None:
-            mix, mix_at = _mix_words(b + masks.size, np.asarray(plan.perm), plan.lam)
-            words.append(mix)
-        warps, warp_at = plan.clips is not None and plan.warps(), 0
-        if warps:                                # the speed step's plans and new lengths ride behind the other words
-            row_len = max(plan.new_lengths)
-            warp_at = sum(int(w.size) for w in words)
-            words.append(_warp.plan_array([(c.shift,) + (p if p is not None else (1, 1))
-                                           for c, p in zip(plan.clips, plan.pairs)]).reshape(-1))
-            words.append(np.asarray(plan.new_lengths, dtype=np.int32))
-        pitched, pitch_at, stretch_width = plan.clips is not None and plan.pitches() and not self.cache_features, 0, 0
-        if pitched:                              # the pitch step's two plans per row ride behind those
-            lens_now = plan.new_lengths if warps else host_lens.tolist()
-            rates = [_pitch.pitch_rate(s) if s else 1.0 for s in plan.steps]
-            sr = self.audio_augmentor.sample_rate
-            stretch_width = max(_pitch.stretched_length(n, r) for n, r in zip(lens_now, rates))
-            pitch_words, pitch_at = _pitch_words(
-                sum(int(w.size) for w in words),
-                _pitch.plan_array([(0 if warps else c.shift, r) for c, r in zip(plan.clips, rates)]),
-                _warp.plan_array([(0,) + (_pitch.pitch_rate_pair(s, sr) if s else (1, 1)) for s in plan.steps]))
-            words.append(pitch_words)
-        i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
-                                                bank.labels.numpy()[idx], idx]), np.concatenate(words))
+        host_lens = self.bank.lengths.numpy()[idx]
+        return idx, host_lens, UploadWords(host_lens)
+
+    def _send(self, idx: np.ndarray, row_len: int, words: UploadWords) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The batch's one upload: int64 bank offsets, offsets of the rows of a (B, row_len) matrix, labels and indices;
+        then the int32 words."""
+        bank = self.bank
+        return _upload(bank.device, np.concatenate([bank.offsets.numpy()[idx], np.arange(len(idx), dtype=np.int64) * row_len,
+                                                    bank.labels.numpy()[idx], idx]), words.array())
+
+    def _tail(self, i64: torch.Tensor, rows, masks, mix) -> Tuple[torch.Tensor, torch.Tensor]:
+        """What both modes end with: the features of ``rows`` -- ``(src, offsets, lens)``, the batch's waveforms after the
+        chain -- or, when ``rows`` is None, the cached ones; ``cough_mask_images`` with the device arrays ``masks`` (None:
+        no masks); ``cough_mix_batch`` with ``mix``, the upload's ``(coefficients, permutation)`` (None: no MixUp)."""
+        b = i64.numel() // 4
         targets = i64[2 * b:3 * b]
-        if self.cache_features:
+        if rows is None:
             if self._cache is None:
                 self._fill_cache()
             feats = self._cache[i64[3 * b:4 * b]]
         else:
-            warp = None
-            if warps:
-                n_plan = b * _warp.PLAN_WORDS
-                warp = (i32[warp_at:warp_at + n_plan].view(b, _warp.PLAN_WORDS), i32[warp_at + n_plan:warp_at + n_plan + b],
-                        row_len)
-            pitch = None
-            if pitched:
-                n_plan = b * _pitch.PLAN_BYTES // 4
-                pitch = (i32[pitch_at:pitch_at + n_plan].view(torch.uint8).view(b, _pitch.PLAN_BYTES),
-                         i32[pitch_at + n_plan:pitch_at + n_plan + b * _warp.PLAN_WORDS].view(b, _warp.PLAN_WORDS),
-                         stretch_width, row_len)
-            feats = self._features(indices, plan, i64, i32[:b], warp, pitch)
-        if masks.size:
-            m = i32[b:b + masks.size].view(3, b, self._n_masks)
-            mask_images(feats, feats, m[0], m[1], m[2], self._n_masks)
-        if plan.perm is not None:
-            return self._mix(feats, targets, i32, mix_at)
+            feats = self._featurise(*rows)
+        if masks is not None:
+            mask_images(feats, feats, masks[0], masks[1], masks[2], self._n_masks)
+        if mix is not None:
+            mixed, soft = mix_batch_rows(feats.contiguous(), targets, mix[1], mix[0])
+            return mixed.unsqueeze(1), soft
         return feats.unsqueeze(1), targets
 
-    def _mix(self, feats: torch.Tensor, targets: torch.Tensor, i32: torch.Tensor, at: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The batch mixed by ``cough_mix_batch``; its coefficients and permutation are the ``_mix_words`` at word ``at``
-        of the batch's upload."""
-        b = feats.shape[0]
-        coef = i32[at:at + 2 * b].view(torch.float32).view(b, 2)
-        mixed, soft = mix_batch_rows(feats.contiguous(), targets, i32[at + 2 * b:at + 3 * b], coef)
-        return mixed.unsqueeze(1), soft
+    def launch_batch(self, indices: Sequence[int], plan: BatchPlan) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Everything of a batch that runs on the device, stream-ordered; nothing here waits for the device."""
+        idx, host_lens, words = self._head(indices)
+        b, bank, dev = len(idx), self.bank, self.bank.device
+        row_len = int(host_lens.max())
+        n_masks = self._n_masks if plan.masks is not None else 0
+        if n_masks:
+            words.add("masks", self._mask_arrays(plan.masks))
+        if plan.perm is not None:
+            words.add("coef", mix_coefficients(plan.lam), align8=True)
+            words.add("perm", np.asarray(plan.perm).astype(np.int32))
+        plans = None
+        if plan.clips is not None and (plan.warps() or plan.pitches()):  # the plans ride behind the other words
+            plans = _chain.host_plans([c.shift for c in plan.clips], plan.pairs, plan.steps, host_lens,
+                                      self.audio_augmentor.sample_rate, row_len)
+            row_len = plans.width
+            for name, array in plans.arrays.items():
+                words.add(name, array, align8=name == "stretch")
+        i64, i32 = self._send(idx, row_len, words)
+
+        rows = None
+        if not self.cache_features:
+            src, offsets, lens, out_offsets = bank.data, i64[:b], words.view(i32, "lengths"), i64[b:2 * b]
+            if plan.clips is not None:
+                if plans is None:                # cough_augment_waveforms takes a matrix
+                    src = torch.empty((b, row_len), dtype=torch.float32, device=dev)
+                    _lib.check_data(_lib.load_data().cough_gather_rows(bank.data.data_ptr(), offsets.data_ptr(),
+                                                                       lens.data_ptr(), b, src.data_ptr(), row_len, row_len,
+                                                                       _stream(dev)), "cough_gather_rows")
+                    clips, lens_now = plan.clips, host_lens
+                else:                            # read in place from the bank; the first launch shifts the rows
+                    d = {name: words.view(i32, name) for name in plans.arrays}
+                    speed = (d["warp"], d["new_lengths"], row_len) if "warp" in d else None
+                    pitch = (d["stretch"], d["back"], plans.stretch_width, row_len) if "stretch" in d else None
+                    src, _, lens = _chain.run(src, offsets, lens, speed, pitch, out_offsets)
+                    clips, lens_now = _chain.unshifted(plan.clips), plans.new_lengths
+                gaussian = plan.gaussian
+                if gaussian is not None:
+                    if gaussian.shape[1] != row_len:                 # drawn for the widest that the speed step can give
+                        gaussian = gaussian[:, :row_len].contiguous()
+                    gaussian = gaussian.to(dev, non_blocking=True)
+                src, offsets = self.audio_augmentor._run(src, clips, lens_now, gaussian, plan.seed), out_offsets
+            rows = (src, offsets, lens)
+        return self._tail(i64, rows, words.view(i32, "masks") if n_masks else None,
+                          (words.view(i32, "coef"), words.view(i32, "perm")) if plan.perm is not None else None)
 
     def launch_batch_drawn(self, indices: Sequence[int], seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
@@ -514,68 +518,47 @@ class DeviceDataLoader:
         cleared.  With ``pitch=True``, ``cough_draw_pitch`` draws the two plans of the pitch step for the (new) lengths;
         ``cough_stretch_rows`` and ``cough_warp_rows`` run behind the speed step -- the time shift rides in the stretch's
         read when there is no speed step: its word is copied from the records into the stretch plans on the device."""
-        bank, pre, dev = self.bank, self.preprocessor, self.bank.device
-        if dev.type != "cuda":
-            raise RuntimeError(f"DeviceDataLoader: the bank lives on {dev}; the loader's kernels need it on the GPU "
-                               "(there is no CPU fallback)")
-        b = len(indices)
-        idx = np.asarray(indices, dtype=np.int64)
-        host_lens = bank.lengths.numpy()[idx]
+        idx, host_lens, words = self._head(indices)
+        b, bank = len(idx), self.bank
         row_len = int(host_lens.max())
-        words, mix_at = [host_lens], 0
         if self._mixes:
-            mix, mix_at = _mix_words(b, *mix_draws(seed, b, self.mixup.alpha))
-            words.append(mix)
+            perm, lam = mix_draws(seed, b, self.mixup.alpha)
+            words.add("coef", mix_coefficients(lam), align8=True)
+            words.add("perm", perm)
         aug = self.audio_augmentor if self._augments else None
-        speed = aug is not None and aug.speed and not self.cache_features
-        if speed:                                # wide enough for the slowest factor: the draws are never read back
+        if aug is not None and aug.speed:        # wide enough for the slowest factor: the draws are never read back
             row_len = _warp.drawn_width(row_len, aug.speed_range, aug.sample_rate)
-        i64, i32 = _upload(dev, np.concatenate([bank.offsets.numpy()[idx], np.arange(b, dtype=np.int64) * row_len,
-                                                bank.labels.numpy()[idx], idx]), np.concatenate(words))
-        lens = i32[:b]
-        targets = i64[2 * b:3 * b]
-        plans, lens_new = (_warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) if speed
-                           else (None, lens))
-        pitch = aug is not None and aug.pitch and not self.cache_features
-        if pitch:
+        i64, i32 = self._send(idx, row_len, words)
+        lens, out_offsets = words.view(i32, "lengths"), i64[b:2 * b]
+        speed = pitch = None
+        lens_new = lens
+        if aug is not None and aug.speed:
+            speed = _warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) + (row_len,)
+            lens_new = speed[1]
+        if aug is not None and aug.pitch:
             if self._pitch_table is None:
-                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate)).to(dev)
-            stretch, back, _ = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
-                                                 self._pitch_table)
+                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate)).to(bank.device)
+            pitch = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
+                                      self._pitch_table)[:2] + (_pitch.drawn_width(row_len, aug.pitch_range), row_len)
         clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,
                                          self.feature_shape())
-        if self.cache_features:
-            if self._cache is None:
-                self._fill_cache()
-            feats = self._cache[i64[3 * b:4 * b]]
-        else:
-            src, offsets = bank.data, i64[:b]
-            if speed or pitch:
-                if speed:
-                    src = _warp.warp_rows(bank.data, offsets, lens, plans, row_len)
-                    offsets, lens = i64[b:2 * b], lens_new
-                else:                            # the records' shift words into the stretch plans' (both lead their struct)
-                    stretch.view(torch.int32).view(b, _pitch.PLAN_BYTES // 4)[:, 0] = \
+
+        rows = None
+        if not self.cache_features:
+            src, offsets, lens_now = bank.data, i64[:b], lens
+            if clips is not None:
+                if speed is not None:
+                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, speed=speed, out_offsets=out_offsets)
+                elif pitch is not None:          # the records' shift words into the stretch plans' (both lead their struct)
+                    pitch[0].view(torch.int32).view(b, _pitch.PLAN_BYTES // 4)[:, 0] = \
                         clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
-                _warp.clear_shifts(clips)
-                if pitch:
-                    src = _pitch.pitch_shift_rows(src.reshape(-1), offsets, lens, stretch, back, row_len,
-                                                  _pitch.drawn_width(row_len, aug.pitch_range))
-                    offsets = i64[b:2 * b]
-                src = _draws.augment_rows_drawn(src, offsets, lens, row_len, clips, aug, seed)
-            elif clips is not None:
-                src = _draws.augment_rows_drawn(bank.data, offsets, lens, row_len, clips, self.audio_augmentor, seed)
-                offsets = i64[b:2 * b]
-            seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
-            _lib.check_data(_lib.load_data().cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
-                                                                seg.data_ptr(), pre.segment_samples, _lib.PREP_NORMALIZE,
-                                                                _stream(dev)), "cough_prepare_rows")
-            feats = pre.featurize_batch(seg, normalize=False)
-        if masks is not None:
-            mask_images(feats, feats, masks[0], masks[1], masks[2], self._n_masks)
-        if self._mixes:
-            return self._mix(feats, targets, i32, mix_at)
-        return feats.unsqueeze(1), targets
+                if speed is not None or pitch is not None:
+                    _warp.clear_shifts(clips)
+                if pitch is not None:            # in a call of its own: the records lose their shift between the steps
+                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, pitch=pitch, out_offsets=out_offsets)
+                src, offsets = _draws.augment_rows_drawn(src, offsets, lens_now, row_len, clips, aug, seed), out_offsets
+            rows = (src, offsets, lens_now)
+        return self._tail(i64, rows, masks, (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         indices = self.epoch_indices()

@@ -20,26 +20,10 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._native import _on_gpu, _stream
 from .augmentation import AudioAugmentor, SpecAugment
 
 CLIP_BYTES = C.sizeof(_lib.CoughAugClip)        # 40: one cough_aug_clip
-
-
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _on_gpu(who: str, **tensors) -> torch.device:
-    dev = None
-    for name, (t, dtype) in tensors.items():
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor")
-        if dev is not None and t.device != dev:
-            raise ValueError(f"{who}: {name} lives on {t.device}, not on {dev}")
-        dev = t.device
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who}: the tensors live on {dev}; the kernels need them on the GPU (there is no CPU fallback)")
-    return dev
 
 
 def mask_counts(spec: SpecAugment) -> Tuple[int, int]:

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from . import warp as _warp
-from .warp import _on_gpu, _stream
+from ._native import _on_gpu, _stream
 
 PLAN_BYTES = C.sizeof(_lib.CoughStretchPlan)       # 16: int32 shift, int32 reserved, float64 rate
 MAX_LENGTH = _lib.PITCH_MAX_LENGTH

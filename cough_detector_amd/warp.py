@@ -14,32 +14,16 @@ The arithmetic and the draw contract are stated in ``include/cough_amd_warp.h`` 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._native import _on_gpu, _stream
 
 PLAN_WORDS = C.sizeof(_lib.CoughWarpPlan) // 4     # 3 int32: shift, orig, new
 MAX_LENGTH = 1 << 30
-
-
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _on_gpu(who: str, **tensors) -> torch.device:
-    dev = None
-    for name, (t, dtype) in tensors.items():
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor")
-        if dev is not None and t.device != dev:
-            raise ValueError(f"{who}: {name} lives on {t.device}, not on {dev}")
-        dev = t.device
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who}: the tensors live on {dev}; the kernels need them on the GPU (there is no CPU fallback)")
-    return dev
 
 
 def speed_rate_pair(factor: float, sample_rate: int) -> Tuple[int, int]:

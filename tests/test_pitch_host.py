@@ -361,5 +361,14 @@ def test_the_loader_carries_the_pitch_draws():
     assert plain.steps is None and not plain.pitches()
     val = cda.DeviceDataLoader(bank, pre, batch_size=2, audio_augmentor=cda.AudioAugmentor(pitch=True), is_training=False)
     assert val.draw_batch([0, 1]).clips is None
-    words, at = cda.data._pitch_words(5, cpitch.plan_array([(3, 0.5), (-1, 2.0)]), cwarp.plan_array([(0, 9, 10), (0, 1, 1)]))
-    assert at == 6 and words.size == 1 + 8 + 6 and words[1] == 3 and words[5] == -1 and words[9:].tolist() == [0, 9, 10, 0, 1, 1]
+    packed = cda.data.UploadWords()
+    packed.add("lengths", np.zeros(5, np.int32))
+    packed.add("stretch", cpitch.plan_array([(3, 0.5), (-1, 2.0)]), align8=True)
+    packed.add("back", cwarp.plan_array([(0, 9, 10), (0, 1, 1)]))
+    words, at = packed.array(), packed.at("stretch")
+    assert at == 6 and words.size == 5 + 1 + 8 + 6 and words.dtype == np.int32 and not words[:6].any()
+    words = words[5:]
+    assert words[1] == 3 and words[5] == -1 and words[9:].tolist() == [0, 9, 10, 0, 1, 1]
+    sent = torch.from_numpy(packed.array())
+    assert np.array_equal(packed.view(sent, "stretch").numpy(), cpitch.plan_array([(3, 0.5), (-1, 2.0)]))
+    assert packed.view(sent, "back").tolist() == [[0, 9, 10], [0, 1, 1]]

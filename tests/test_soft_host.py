@@ -293,10 +293,18 @@ def test_device_mode_draws_are_philox_keyed_by_the_batch_seed(monkeypatch):
     # the words that travel with the upload: padding to 8 bytes, (lam, 1 - lam) as float32, the permutation
     perm, lam = cdata.mix_draws(3, 3, 0.2)
     for before in (3, 4):
-        words, at = cdata._mix_words(before, perm, lam)
-        assert at % 2 == 0 and at - before == before % 2 and words.dtype == np.int32 and len(words) == at - before + 9
-        body = words[at - before:]
+        packed = cdata.UploadWords()
+        packed.add("lengths", np.arange(before, dtype=np.int32))
+        packed.add("coef", mix_coefficients(lam), align8=True)
+        packed.add("perm", perm)
+        words, at = packed.array(), packed.at("coef")
+        assert at % 2 == 0 and at - before == before % 2 and words.dtype == np.int32 and len(words) == at + 9
+        assert words[:before].tolist() == list(range(before)) and not words[before:at].any()
+        body = words[at:]
         assert np.array_equal(body[:6].view(np.float32).reshape(3, 2), mix_coefficients(lam)) and np.array_equal(body[6:], perm)
+        sent = torch.from_numpy(words)                                 # the views the launches get after the upload
+        assert np.array_equal(packed.view(sent, "coef").numpy(), mix_coefficients(lam))
+        assert np.array_equal(packed.view(sent, "perm").numpy(), perm) and "coef" in packed and "warp" not in packed
     # batch k of an epoch is drawn under (epoch_seed + k) mod 2^64, with or without other draws
     bank, pre = _bank(), _pre()
     loader = cda.DeviceDataLoader(bank, pre, batch_size=4, use_weighted_sampler=False, drop_last=False, draws="device",
