@@ -129,7 +129,7 @@ __device__ __forceinline__ uint16_t f2bf(float f) {
     __hip_bfloat16 b = __float2bfloat16(f);
     return *reinterpret_cast<uint16_t*>(&b);
 }
-// geometry of the fused stem for the 90x101 feature image (resnet.hip: stem_bf16_kernel / stem_lds)
+// geometry of the fused stem for the 90x101 feature image (resnet.hip: stem_bf16_kernel; resnet_plan.h: stem_lds)
 constexpr int ST_P1H = 22, ST_P1W = 25, ST_ROWS = 94;   // image width = NFRAMES
 constexpr int ST_PER = ST_P1H * ST_P1W, ST_TILES = (ST_PER + 7) / 8;
 // Image pitch in bf16.  An A fragment is four ds_read_b32 at dword (2 (2 ph + dy) + sh) * pitch / 2 + 2 pw + dx (+ 0..3): a

@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "nn_common.h"
+#include "resnet_plan.h"   // rbx_t16: which body a block runs
 
 namespace cough {
 namespace {
@@ -74,16 +75,6 @@ struct RbxArgs {
     int* preds;           // [B] or nullptr
     const int* nanflag;   // fused head: [B] or nullptr; 1 = the clip's image holds a NaN -> NaN logits (nn_common.h: NaN rule)
 };
-
-// Which body a block runs.  The 16x16x32 body needs one or two 16-channel tiles per wave and at most two clips per
-// workgroup (block 0: 32 -> 64 channels, one clip; block 1: 64 -> 128 channels, one or two clips).  Block 0 runs it up
-// to 26 rows; at 27 rows (110-row images) the 32x32x16 body was faster (same-box kernel trace: 315 against 322 us;
-// 26 rows: 312 against 307 us; profiles/r06_block0_t16.txt).  Block 1 runs it at every compiled height: 2-16 % faster
-// than the 32x32x16 body at 8-14 rows (profiles/r07_block1_t16.txt).
-constexpr bool rbx_t16_shape(int cin, int cout) { return (cin == 32 && cout == 64) || (cin == 64 && cout == 128); }
-constexpr bool rbx_t16(int cin, int cout, int xh) {
-    return rbx_t16_shape(cin, cout) && (cin == 64 || xh <= 26);
-}
 
 template <int CIN, int COUT, int G, int XH, int XW>
 struct RbxCfg {

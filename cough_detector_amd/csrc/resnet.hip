@@ -17,6 +17,7 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+#include <array>
 #include <utility>
 #include <cmath>
 #include <cstdint>
@@ -30,25 +31,10 @@
 #include "nn_common.h"
 #include "conv_gemm.h"
 #include "resblock_x3.h"
+#include "resnet_plan.h"   // what a forward runs: plan_resnet decides, run_plan (below) launches
 
 namespace cough {
 namespace {
-
-struct Shapes {
-    int H, W;          // feature image
-    int P1h, P1w;      // after stem + maxpool
-    int B0h, B0w;      // after block 0
-    int B1h, B1w;      // after block 1
-};
-inline Shapes make_shapes(int H, int W) {
-    Shapes s;
-    s.H = H; s.W = W;
-    const int c1h = (H + 6 - 7) / 2 + 1, c1w = (W + 6 - 7) / 2 + 1;
-    s.P1h = c1h / 2; s.P1w = c1w / 2;
-    s.B0h = (s.P1h + 2 - 3) / 2 + 1; s.B0w = (s.P1w + 2 - 3) / 2 + 1;
-    s.B1h = (s.B0h + 2 - 3) / 2 + 1; s.B1w = (s.B0w + 2 - 3) / 2 + 1;
-    return s;
-}
 
 // ------------------------------------------------------------------------------------ K2 stem
 constexpr int STEM_K = 49, STEM_KS = 25, STEM_N = 32;
@@ -113,18 +99,7 @@ __device__ __forceinline__ int fdiv(int a, int b, float inv) {
 // with a zero border (rows/cols -3..), so every A fragment is 4 aligned ds_read_b32.  K is re-ordered as
 // 8 kernel rows x 8 taps (7 + one zero tap; the 8th row is all zero): MFMA step s, lane half h <-> kernel
 // row 2s+h, element jj <-> tap jj, i.e. 8 consecutive input pixels of one image row per lane.
-constexpr int STEM_SB_MAXL = 22;   // 2 * 256 * 22 = 11 264 pixels: the 110 x 101 image of the reference's default flags fits
-struct StemLds {
-    int nrows, pitch;   // bf16 image in LDS: row = ih + 3, col = iw + 3, pitch even
-    size_t bytes;
-};
-inline StemLds stem_lds(const Shapes& s) {
-    StemLds l;
-    l.nrows = std::max(4 * s.P1h + 6, s.H + 3);
-    l.pitch = (std::max(4 * s.P1w + 6, s.W + 3) + 1) & ~1;
-    l.bytes = size_t(l.nrows) * l.pitch * 2;
-    return l;
-}
+// The image geometry (nrows, pitch: stem_lds) and the pixel limit (STEM_SB_MAXL) are resnet_plan.h's.
 
 // X3: split-bf16 operands -- the image and the weights as hi + lo bf16 pairs, three MFMAs per step
 // (image_hi * w_hi + image_lo * w_hi + image_hi * w_lo, the order of the fused stem in featurize.hip), f32 output.
@@ -355,16 +330,10 @@ struct RbArgs {
 
 template <int CIN, int COUT, int G, int MW, int WAVES>
 struct RbCfg {
-    static constexpr int NT = COUT / 32, MG = WAVES / NT, MTMAX = MG * MW;
-    static constexpr int THREADS = WAVES * 64;
+    // tiles, threads and the LDS size (rb_lds_bytes) follow from the parameter tuple in resnet_plan.h (RB_CFG)
+    static constexpr int NT = COUT / 32, MTMAX = rb_mtmax(RbParams{CIN, COUT, G, MW, WAVES});
+    static constexpr int THREADS = rb_threads(RbParams{CIN, COUT, G, MW, WAVES});
     static constexpr int KS1 = 9 * CIN / 16, KS2 = (9 * COUT + CIN) / 16;   // 16-wide MFMA k-steps
-    static size_t lds_bytes(int XH, int XW, int OH, int OW) {
-        const size_t images = (size_t(G) * (XH + 2) * (XW + 2) * CIN + size_t(G) * (OH + 2) * (OW + 2) * COUT) * 2;
-        // the epilogue re-uses the region as a [MTMAX * 32][COUT + 8] bf16 output tile followed by the head's
-        // reduction scratch: for small images that is the larger of the two
-        const size_t tile = size_t(MTMAX) * 32 * (COUT + 8) * 2 + size_t(WAVES) * 2 * sizeof(float);
-        return images > tile ? images : tile;
-    }
 };
 
 __device__ __forceinline__ uint2 pack4_bf16(float a, float b, float c, float d) {
@@ -890,13 +859,10 @@ Workspace carve(const cough_resnet* m, char* base, int n, const Shapes& s) {
 }
 
 // ------------------------------------------------------------------------------ generic channel tuples (f32)
-struct GenShape { int h, w; };
 // spatial sizes: [0] after the stem + pool, [i + 1] after block i
-std::vector<GenShape> gen_shapes(const cough_resnet_generic* g, int H, int W) {
-    std::vector<GenShape> v;
-    const int c1h = (H + 6 - 7) / 2 + 1, c1w = (W + 6 - 7) / 2 + 1;
-    v.push_back({c1h / 2, c1w / 2});
-    for (int i = 0; i < g->n_blocks; ++i) v.push_back({(v.back().h + 2 - 3) / 2 + 1, (v.back().w + 2 - 3) / 2 + 1});
+std::vector<HW> gen_shapes(const cough_resnet_generic* g, int H, int W) {
+    std::vector<HW> v{stem_out({H, W})};
+    for (int i = 0; i < g->n_blocks; ++i) v.push_back(block_out(v.back()));
     return v;
 }
 // workspace: a[0] (stem out), then per block h[i] and a[i + 1]; NHWC f32 with padded channels
@@ -904,7 +870,7 @@ struct GenWorkspace {
     std::vector<float*> a, h;
     size_t total;
 };
-GenWorkspace gen_carve(const cough_resnet_generic* g, char* base, int n, const std::vector<GenShape>& sh) {
+GenWorkspace gen_carve(const cough_resnet_generic* g, char* base, int n, const std::vector<HW>& sh) {
     GenWorkspace w;
     size_t off = 0;
     auto take = [&](size_t elems) { float* p = reinterpret_cast<float*>(base + off); off += align256(elems * 4); return p; };
@@ -915,50 +881,6 @@ GenWorkspace gen_carve(const cough_resnet_generic* g, char* base, int n, const s
     }
     w.total = off;
     return w;
-}
-
-int gen_forward(const cough_resnet_generic* g, const float* d_feat, int n, int H, int W, float* d_logits, float* d_probs,
-                int* d_preds, char* ws, hipStream_t st) {
-    const std::vector<GenShape> sh = gen_shapes(g, H, W);
-    const GenWorkspace w = gen_carve(g, ws, n, sh);
-    {   // stem
-        const long long n_pool = (long long)n * sh[0].h * sh[0].w;
-        const long long tiles = (n_pool + 7) / 8;
-        long long blocks = (tiles + 3) / 4;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(stem_mfma_kernel<float>, dim3((unsigned)blocks, g->chp[0] / 32), dim3(256), 0, st, d_feat, H, W,
-                           sh[0].h, sh[0].w, n_pool, g->d_stem_w, g->d_stem_b, w.a[0], g->chp[0]);
-        COUGH_HIP_CHECK(hipGetLastError());
-    }
-    for (int i = 0; i < g->n_blocks; ++i) {
-        const int cin = g->chp[i], cout = g->chp[i + 1];
-        const long long M = (long long)n * sh[i + 1].h * sh[i + 1].w;
-        const int xh = i == 0 ? sh[0].h : sh[i].h, xw = i == 0 ? sh[0].w : sh[i].w;
-        ConvArgs<float> c1{};
-        c1.in = w.a[i]; c1.H = xh; c1.W = xw; c1.C = cin; c1.KH = 3; c1.KW = 3; c1.stride = 2; c1.pad = 1;
-        c1.in2 = nullptr; c1.C2 = 0; c1.H2 = c1.W2 = 0; c1.stride2 = 1;
-        c1.wp = g->d_w[2 * i]; c1.bias = g->d_b[2 * i]; c1.out = w.h[i];
-        c1.OH = sh[i + 1].h; c1.OW = sh[i + 1].w; c1.N = cout; c1.Ktot = g->ktot[2 * i]; c1.M = M;
-        ConvArgs<float> c2{};
-        c2.in = w.h[i]; c2.H = sh[i + 1].h; c2.W = sh[i + 1].w; c2.C = cout; c2.KH = 3; c2.KW = 3; c2.stride = 1; c2.pad = 1;
-        c2.in2 = w.a[i]; c2.H2 = xh; c2.W2 = xw; c2.C2 = cin; c2.stride2 = 2;
-        c2.wp = g->d_w[2 * i + 1]; c2.bias = g->d_b[2 * i + 1]; c2.out = w.a[i + 1];
-        c2.OH = sh[i + 1].h; c2.OW = sh[i + 1].w; c2.N = cout; c2.Ktot = g->ktot[2 * i + 1]; c2.M = M;
-        const long long tiles = (M + 31) / 32;
-        const dim3 grid((unsigned)((tiles + 3) / 4), cout / 32);
-        if (M > 0) {
-            hipLaunchKernelGGL((conv_mfma_kernel<float, 1>), grid, dim3(256), 0, st, c1);
-            hipLaunchKernelGGL((conv_mfma_kernel<float, 1>), grid, dim3(256), 0, st, c2);
-            COUGH_HIP_CHECK(hipGetLastError());
-        }
-    }
-    const int L = g->n_blocks;
-    hipLaunchKernelGGL(tail_generic_kernel, dim3(n), dim3(128), 0, st, w.a[L], sh[L].h * sh[L].w, g->ch[L], g->chp[L],
-                       g->d_fcw, g->d_fcb, d_logits, d_probs, d_preds);
-    COUGH_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nan_rule_kernel, dim3(n), dim3(256), 0, st, d_feat, (long long)H * W, nullptr, d_logits, d_probs, d_preds);
-    COUGH_HIP_CHECK(hipGetLastError());
-    return COUGH_OK;
 }
 
 void gen_destroy(cough_resnet_generic* g) {
@@ -982,174 +904,238 @@ void pad_folded(const FoldedConv& f, int Np, int Cp, std::vector<float>& w, int 
     (void)Np;
 }
 
+// ------------------------------------------------------------------------------ the instantiation tables
+// The split-bf16 block kernels: one per row of RBX_BLOCK0_ROWS / RBX_BLOCK1_ROWS (resnet_plan.h).  A launch takes its
+// entry by BlockPlan::row; cough_resnet_create raises the dynamic-LDS limit of every entry.
+struct RbxEntry {
+    void (*kernel)(RbxArgs);
+    int lds, threads;   // RbxCfg::LDS, RbxCfg::THREADS
+};
+template <int BLK, int XH>
+constexpr RbxEntry rbx_entry() {
+    constexpr int CIN = NET_CH[BLK], COUT = NET_CH[BLK + 1], G = rbx_clips(BLK, XH), XW = RBX_COLS[BLK];
+    using Cfg = RbxCfg<CIN, COUT, G, XH, XW>;
+    return {resblock_x3_kernel<CIN, COUT, G, XH, XW>, Cfg::LDS, Cfg::THREADS};
+}
+template <int BLK, int... I>
+constexpr std::array<RbxEntry, sizeof...(I)> rbx_table(std::integer_sequence<int, I...>) {
+    return {{rbx_entry<BLK, rbx_rows(BLK, I)>()...}};
+}
+constexpr auto RBX_TABLE0 = rbx_table<0>(std::make_integer_sequence<int, RBX_NROWS[0]>{});
+constexpr auto RBX_TABLE1 = rbx_table<1>(std::make_integer_sequence<int, RBX_NROWS[1]>{});
+constexpr const RbxEntry* RBX_TABLE[2] = {RBX_TABLE0.data(), RBX_TABLE1.data()};
+// The single-bf16 block kernels of RB_CFG: [block][0: geometry from RbArgs, 1: RB_FIXED compiled in]
+template <int BLK, bool FIXED>
+constexpr auto rb_kernel() {
+    constexpr RbParams P = RB_CFG[BLK];
+    return resblock_bf16_kernel<P.cin, P.cout, P.g, P.mw, P.waves, FIXED ? RB_FIXED[BLK].h : 0, FIXED ? RB_FIXED[BLK].w : 0>;
+}
+constexpr void (*RB_KERNEL[2][2])(RbArgs) = {{rb_kernel<0, false>(), rb_kernel<0, true>()},
+                                             {rb_kernel<1, false>(), rb_kernel<1, true>()}};
+
+// ------------------------------------------------------------------------------ running a plan
+// One residual block's activations and packed weights: of either net, or of a lone cough_resblock
+struct BlockIO {
+    const void* x;           // NHWC activations: block input,
+    void *h, *out;           //   ReLU(conv1) (the unfused kernels), block output
+    int cin, cout;           // channels as laid out in memory (the generic kernels: padded to a multiple of 32)
+    const void *w1, *w2;     // packed [cout][k1] conv1, [cout][k2] conv2 followed by the projection
+    const float *b1, *b2;    // folded biases: conv1, conv2 + projection
+    int k1, k2;
+};
+
+// h = ReLU(conv3x3 s(x)), out = ReLU(conv3x3 s1(h) + conv1x1 s(x)) as the two launches of the unfused kernels
 template <typename T>
-int launch_conv(const cough_resnet* m, const ConvArgs<T>& a, hipStream_t st) {
+std::pair<ConvArgs<T>, ConvArgs<T>> conv_pair(const BlockIO& k, HW in, HW out, int stride, int n) {
+    ConvArgs<T> c1{};
+    c1.in = static_cast<const T*>(k.x); c1.H = in.h; c1.W = in.w; c1.C = k.cin;
+    c1.KH = 3; c1.KW = 3; c1.stride = stride; c1.pad = 1;
+    c1.in2 = nullptr; c1.C2 = 0; c1.H2 = c1.W2 = 0; c1.stride2 = 1;
+    c1.wp = static_cast<const T*>(k.w1); c1.bias = k.b1;
+    c1.out = static_cast<T*>(k.h); c1.OH = out.h; c1.OW = out.w; c1.N = k.cout; c1.Ktot = k.k1;
+    c1.M = (long long)n * out.h * out.w;
+    ConvArgs<T> c2{};
+    c2.in = static_cast<const T*>(k.h); c2.H = out.h; c2.W = out.w; c2.C = k.cout;
+    c2.KH = 3; c2.KW = 3; c2.stride = 1; c2.pad = 1;
+    c2.in2 = static_cast<const T*>(k.x); c2.H2 = in.h; c2.W2 = in.w; c2.C2 = k.cin; c2.stride2 = stride;
+    c2.wp = static_cast<const T*>(k.w2); c2.bias = k.b2;
+    c2.out = static_cast<T*>(k.out); c2.OH = out.h; c2.OW = out.w; c2.N = k.cout; c2.Ktot = k.k2;
+    c2.M = c1.M;
+    return {c1, c2};
+}
+
+// nt: 32-channel tiles per wave (BlockPlan::nt); the f32 kernel tiles the remaining channels over blockIdx.y
+template <typename T>
+int launch_conv(const ConvArgs<T>& a, int nt, hipStream_t st) {
     if (a.M == 0) return COUGH_OK;
     if constexpr (sizeof(T) == 2) {
         const dim3 grid((unsigned)((a.M + CG_BM - 1) / CG_BM));
-        if (a.N == 64) hipLaunchKernelGGL((conv_gemm_bf16_kernel<2>), grid, dim3(256), 0, st, a);
+        if (nt == 2) hipLaunchKernelGGL((conv_gemm_bf16_kernel<2>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv_gemm_bf16_kernel<4>), grid, dim3(256), 0, st, a);
     } else {
         const long long tiles = (a.M + 31) / 32;
-        const dim3 grid((unsigned)((tiles + 3) / 4));
-        if (a.N == 64) hipLaunchKernelGGL((conv_mfma_kernel<T, 2>), grid, dim3(256), 0, st, a);
+        const dim3 grid((unsigned)((tiles + 3) / 4), a.N / (32 * nt));
+        if (nt == 1) hipLaunchKernelGGL((conv_mfma_kernel<T, 1>), grid, dim3(256), 0, st, a);
+        else if (nt == 2) hipLaunchKernelGGL((conv_mfma_kernel<T, 2>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv_mfma_kernel<T, 4>), grid, dim3(256), 0, st, a);
     }
     COUGH_HIP_CHECK(hipGetLastError());
     return COUGH_OK;
 }
 
-// clips per workgroup of block 1 at the 13x13 / 14x13 inputs: 1 (49-53 KB of LDS, three workgroups per CU; two clips per
-// workgroup = 95-102 KB, one workgroup per CU, measured the same: profiles/r04_heights.txt)
-constexpr int RBX_G_TALL = 1;
-// block-input geometries resblock_x3_kernel is instantiated for (block index, rows, columns): every feature image the
-// reference's flags produce at 99..102 frames.  Image rows -> block-0 rows -> block-1 rows:
-//   63..66 (use_mfcc = False: 64) 16 -> 8 | 67..70 (+ contrast rows) 17 -> 9 | 87..90 (shipped) 22 -> 11 | 91..94 (+ contrast rows) 23 -> 12 |
-//   95..98 24 -> 12 | 103..106 (delta-delta on) 26 -> 13 | 107..110 (+ contrast rows: the constructor's defaults) 27 -> 14
-#define RBX_BLOCK0_ROWS(X) X(16) X(17) X(22) X(23) X(24) X(26) X(27)
-#define RBX_BLOCK1_ROWS(X) X(8) X(9) X(11) X(12) X(13) X(14)
-// clips per workgroup of block 1: 2 up to 12 rows, RBX_G_TALL above.  The shipped 11x13 takes 81 440 B of LDS and 220
-// VGPRs: two workgroups per CU (12 rows: 89 632 B, one)
-constexpr int rbx_block1_clips(int xh) { return xh <= 12 ? 2 : RBX_G_TALL; }
-inline bool rbx_compiled(int blk, int xh, int xw) {
-#define RBX_HAS(R) || xh == R
-    return blk == 0 ? (xw == 25 && (false RBX_BLOCK0_ROWS(RBX_HAS))) : (xw == 13 && (false RBX_BLOCK1_ROWS(RBX_HAS)));
-#undef RBX_HAS
-}
-
-template <int CIN, int COUT, int G, int XH, int XW>
-void rbx_launch(int n, hipStream_t st, const RbxArgs& ra) {
-    using Cfg = RbxCfg<CIN, COUT, G, XH, XW>;
-    hipLaunchKernelGGL((resblock_x3_kernel<CIN, COUT, G, XH, XW>), dim3((n + G - 1) / G), dim3(Cfg::THREADS), Cfg::LDS, st, ra);
+template <typename T>
+int launch_conv_pair(const BlockIO& k, HW in, HW out, int stride, int n, int nt, hipStream_t st) {
+    const auto [c1, c2] = conv_pair<T>(k, in, out, stride, n);
+    if (int e = launch_conv(c1, nt, st)) return e;
+    return launch_conv(c2, nt, st);
 }
 
 template <typename T>
-int forward_impl(const cough_resnet* m, const float* d_feat, int n, const Shapes& s, float* d_logits, float* d_probs,
-                 int* d_preds, char* ws, hipStream_t st, bool stem_done = false) {
-    const Workspace w = carve(m, ws, n, s);
-    const long long n_pool = (long long)n * s.P1h * s.P1w;
-    const int* nanflag = nullptr;   // set when the stem's staging loop has looked at every pixel (nan_rule_kernel)
-    if (stem_done) {
-        // a1 was produced by the featurise kernel (cough_pipeline_forward), which also left its verdict on the clip's samples
-        nanflag = w.nanflag;
-    } else if (m->dtype == COUGH_DTYPE_BF16 && stem_lds(s).bytes <= 64 * 1024 && s.H * s.W <= 2 * 256 * STEM_SB_MAXL) {
-        if constexpr (sizeof(T) == 2) {
-            const StemLds l = stem_lds(s);
-            hipLaunchKernelGGL(stem_bf16_kernel<false>, dim3(n), dim3(256), l.bytes, st, d_feat, s.H, s.W, s.P1h, s.P1w,
-                               l.nrows, l.pitch, m->d_stem_wfrag, m->d_stem_b, reinterpret_cast<bf16_t*>(w.a1), w.nanflag);
-            nanflag = w.nanflag;
-        }
-    } else if (m->dtype == COUGH_DTYPE_BF16X3 && 2 * stem_lds(s).bytes <= 64 * 1024 && s.H * s.W <= 2 * 256 * STEM_SB_MAXL) {
-        if constexpr (sizeof(T) == 4) {
-            const StemLds l = stem_lds(s);
-            hipLaunchKernelGGL(stem_bf16_kernel<true>, dim3(n), dim3(256), 2 * l.bytes, st, d_feat, s.H, s.W, s.P1h, s.P1w,
-                               l.nrows, l.pitch, m->d_stem_wfrag, m->d_stem_b, reinterpret_cast<float*>(w.a1), w.nanflag);
-            nanflag = w.nanflag;
-        }
-    } else {
-        const long long tiles = (n_pool + 7) / 8;
-        long long blocks = (tiles + 3) / 4;
-        if (blocks > 256 * 8) blocks = 256 * 8;   // grid-stride over tiles: weights stay in registers
-        hipLaunchKernelGGL(stem_mfma_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, d_feat, s.H, s.W, s.P1h,
-                           s.P1w, n_pool, m->d_stem_w, m->d_stem_b, reinterpret_cast<T*>(w.a1), STEM_N);
+void launch_stem_mfma(const float* d_feat, int n, int H, int W, HW p1, const float* wk, const float* bias, void* a1, int channels,
+                      hipStream_t st) {
+    const long long n_pool = (long long)n * p1.h * p1.w;
+    const long long tiles = (n_pool + 7) / 8;
+    long long blocks = (tiles + 3) / 4;
+    if (blocks > 256 * 8) blocks = 256 * 8;   // grid-stride over tiles: weights stay in registers
+    hipLaunchKernelGGL(stem_mfma_kernel<T>, dim3((unsigned)blocks, channels / 32), dim3(256), 0, st, d_feat, H, W, p1.h, p1.w,
+                       n_pool, wk, bias, static_cast<T*>(a1), channels);
+}
+
+// The buffers (carved from the workspace) and weights a forward of either net reads and writes
+struct NetIO {
+    const float *stem_w, *stem_b;   // stem_mfma_kernel: [50][stem_ch], [stem_ch]
+    int stem_ch;                    // stem channels as laid out
+    char* a1;                       // stem + pool output
+    int* nanflag;                   // [n] written by the staged stems (or the featurise kernel); nullptr: the generic net
+    BlockIO blk[PLAN_MAX_BLOCKS];
+    const float *fcw, *fcb;
+    int c_last;                     // real channels of the last activation (tail_generic_kernel)
+};
+NetIO net_io(const cough_resnet* m, char* ws, int n, int H, int W) {
+    NetIO io{};
+    if (const cough_resnet_generic* g = m->gen) {
+        const GenWorkspace w = gen_carve(g, ws, n, gen_shapes(g, H, W));
+        io.stem_w = g->d_stem_w; io.stem_b = g->d_stem_b; io.stem_ch = g->chp[0];
+        io.a1 = reinterpret_cast<char*>(w.a[0]);
+        for (int i = 0; i < g->n_blocks; ++i)
+            io.blk[i] = {w.a[i], w.h[i], w.a[i + 1], g->chp[i], g->chp[i + 1], g->d_w[2 * i], g->d_w[2 * i + 1],
+                         g->d_b[2 * i], g->d_b[2 * i + 1], g->ktot[2 * i], g->ktot[2 * i + 1]};
+        io.fcw = g->d_fcw; io.fcb = g->d_fcb; io.c_last = g->ch[g->n_blocks];
+        return io;
+    }
+    const Workspace w = carve(m, ws, n, make_shapes(H, W));
+    char* const act[5] = {w.a1, w.h0, w.a2, w.h1, w.a3};
+    io.stem_w = m->d_stem_w; io.stem_b = m->d_stem_b; io.stem_ch = NET_CH[0];
+    io.a1 = w.a1;
+    io.nanflag = w.nanflag;
+    for (int i = 0; i < 2; ++i)
+        io.blk[i] = {act[2 * i], act[2 * i + 1], act[2 * i + 2], NET_CH[i], NET_CH[i + 1], m->d_w[2 * i], m->d_w[2 * i + 1],
+                     m->d_b[2 * i], m->d_b[2 * i + 1], m->ktot[2 * i], m->ktot[2 * i + 1]};
+    io.fcw = m->d_fcw; io.fcb = m->d_fcb; io.c_last = NET_CH[2];
+    return io;
+}
+
+// stem -> blocks -> tail (unless block 1 ran the head) -> nan_rule_kernel (unless block 1 applied the rule)
+int run_plan(const cough_resnet* m, const NetPlan& p, const NetIO& io, const float* d_feat, int n, int H, int W,
+             float* d_logits, float* d_probs, int* d_preds, hipStream_t st) {
+    // the per-clip flag is set when a staging loop has looked at every pixel (pipeline: every sample)
+    const int* nanflag = p.nan == NAN_FLAG ? io.nanflag : nullptr;
+    switch (p.stem) {
+        case STEM_FEATURIZER: break;   // a1 was produced by the featurise kernel (cough_pipeline_forward), which also left its verdict
+        case STEM_BF16:
+            hipLaunchKernelGGL(stem_bf16_kernel<false>, dim3(n), dim3(256), p.stem_lds.bytes, st, d_feat, H, W, p.stem_hw.h,
+                               p.stem_hw.w, p.stem_lds.nrows, p.stem_lds.pitch, m->d_stem_wfrag, io.stem_b,
+                               reinterpret_cast<bf16_t*>(io.a1), io.nanflag);
+            break;
+        case STEM_X3:
+            hipLaunchKernelGGL(stem_bf16_kernel<true>, dim3(n), dim3(256), p.stem_lds.bytes, st, d_feat, H, W, p.stem_hw.h,
+                               p.stem_hw.w, p.stem_lds.nrows, p.stem_lds.pitch, m->d_stem_wfrag, io.stem_b,
+                               reinterpret_cast<float*>(io.a1), io.nanflag);
+            break;
+        case STEM_MFMA_F32: launch_stem_mfma<float>(d_feat, n, H, W, p.stem_hw, io.stem_w, io.stem_b, io.a1, io.stem_ch, st); break;
+        case STEM_MFMA_BF16: launch_stem_mfma<bf16_t>(d_feat, n, H, W, p.stem_hw, io.stem_w, io.stem_b, io.a1, io.stem_ch, st); break;
     }
     COUGH_HIP_CHECK(hipGetLastError());
 
-    struct Blk { char *x, *h, *out; int xh, xw, oh, ow, cin, cout, s1, s2; };
-    const Blk blk[2] = {{w.a1, w.h0, w.a2, s.P1h, s.P1w, s.B0h, s.B0w, 32, 64, 0, 1},
-                        {w.a2, w.h1, w.a3, s.B0h, s.B0w, s.B1h, s.B1w, 64, 128, 2, 3}};
-    bool head_done = false;   // the fused block-1 kernel also runs the head
-    bool rule_done = false;   // ... and applied the NaN rule from the per-clip flag
-    for (int i = 0; i < 2; ++i) {
-        const Blk& k = blk[i];
-        if constexpr (sizeof(T) == 4) {
-            // bf16x3: fused split-bf16 block kernels, compiled for the block-input geometries of the feature images the
-            // reference's own flags produce at 101 frames -- 90 rows (shipped: 22x25 -> 11x13), 103 rows (constructor
-            // defaults, delta-delta on: 26x25 -> 13x13) and 110 rows (+ contrast / centroid rows: 27x25 -> 14x13)
-            if (m->dtype == COUGH_DTYPE_BF16X3 && rbx_compiled(i, k.xh, k.xw)) {
+    for (int i = 0; i < p.n_blocks; ++i) {
+        const BlockPlan& b = p.block[i];
+        const BlockIO& k = io.blk[i];
+        switch (b.kernel) {
+            case BLOCK_X3: {
                 RbxArgs ra{};
-                ra.x = reinterpret_cast<const float*>(k.x);
+                ra.x = static_cast<const float*>(k.x);
                 ra.n_clips = n;
-                ra.wf = rbx_t16(k.cin, k.cout, k.xh) ? m->d_wx3t16[i] : m->d_wx3[i];
-                ra.b1 = m->d_b[k.s1];
-                ra.b2 = m->d_b[k.s2];
-                ra.out = reinterpret_cast<float*>(k.out);
-                if (i == 1) {
-                    ra.fcw = m->d_fcw; ra.fcb = m->d_fcb; ra.logits = d_logits; ra.probs = d_probs; ra.preds = d_preds;
-                    if (stem_done) ra.out = nullptr;   // pipeline: nobody reads a3
-                    head_done = true;
-                    if (nanflag) { ra.nanflag = nanflag; rule_done = true; }
+                ra.wf = b.body == BODY_16X16X32 ? m->d_wx3t16[i] : m->d_wx3[i];
+                ra.b1 = k.b1;
+                ra.b2 = k.b2;
+                ra.out = static_cast<float*>(k.out);
+                if (i == 1) {   // block 1 also runs the head
+                    ra.fcw = io.fcw; ra.fcb = io.fcb; ra.logits = d_logits; ra.probs = d_probs; ra.preds = d_preds;
+                    if (!p.store_a3) ra.out = nullptr;
+                    if (p.nan_in_block1) ra.nanflag = nanflag;
                 }
-#define RBX_GO0(R) if (i == 0 && k.xh == R) rbx_launch<32, 64, 1, R, 25>(n, st, ra);
-#define RBX_GO1(R) if (i == 1 && k.xh == R) rbx_launch<64, 128, rbx_block1_clips(R), R, 13>(n, st, ra);
-                RBX_BLOCK0_ROWS(RBX_GO0)
-                RBX_BLOCK1_ROWS(RBX_GO1)
-#undef RBX_GO0
-#undef RBX_GO1
+                const RbxEntry& e = RBX_TABLE[i][b.row];
+                hipLaunchKernelGGL(e.kernel, dim3((n + b.clips - 1) / b.clips), dim3(e.threads), e.lds, st, ra);
                 COUGH_HIP_CHECK(hipGetLastError());
-                continue;
+                break;
             }
-        }
-        if constexpr (sizeof(T) == 2) {   // bf16: fused block kernel when the clip group fits one workgroup's LDS
-            using Cfg0 = RbCfg<32, 64, 1, 3, 4>;     // block 0: 1 clip (66 KB LDS: two workgroups per CU), 4 waves = 2 tile groups x 2 channel tiles
-            using Cfg1 = RbCfg<64, 128, 3, 2, 8>;    // block 1: 3 clips, 8 waves = 2 pixel-tile pairs x 4 channel tiles (2 waves per SIMD)
-            RbArgs ra{};
-            ra.x = reinterpret_cast<const bf16_t*>(k.x); ra.XH = k.xh; ra.XW = k.xw; ra.OH = k.oh; ra.OW = k.ow;
-            ra.n_clips = n;
-            ra.wf1 = m->d_wfrag[k.s1]; ra.b1 = m->d_b[k.s1];
-            ra.wf2 = m->d_wfrag[k.s2]; ra.b2 = m->d_b[k.s2];
-            ra.out = reinterpret_cast<bf16_t*>(k.out);
-            if (i == 1) { ra.fcw = m->d_fcw; ra.fcb = m->d_fcb; ra.logits = d_logits; ra.probs = d_probs; ra.preds = d_preds; }
-            if (i == 1 && stem_done) ra.out = nullptr;   // pipeline: nobody reads a3 (the activation tap,
-                                                         // cough_resnet_read_activation, belongs to cough_resnet_forward)
-            const size_t lds = i == 0 ? Cfg0::lds_bytes(k.xh, k.xw, k.oh, k.ow) : Cfg1::lds_bytes(k.xh, k.xw, k.oh, k.ow);
-            const int g = i == 0 ? 1 : 3, mtmax = i == 0 ? Cfg0::MTMAX : Cfg1::MTMAX;
-            const int threads = i == 0 ? Cfg0::THREADS : Cfg1::THREADS;
-            if (m->dtype == COUGH_DTYPE_BF16 && lds <= 160 * 1024 && g * k.oh * k.ow <= mtmax * 32 &&
-                g * k.xh * k.xw * (k.cin / 8) <= 16 * threads) {
-                const dim3 grid((unsigned)((n + g - 1) / g));
-                // the shipped 90x101 feature image: block inputs 22x25 and 11x13, compiled-in geometry
-                if (i == 0 && k.xh == 22 && k.xw == 25)
-                    hipLaunchKernelGGL((resblock_bf16_kernel<32, 64, 1, 3, 4, 22, 25>), grid, dim3(Cfg0::THREADS), lds, st, ra);
-                else if (i == 0)
-                    hipLaunchKernelGGL((resblock_bf16_kernel<32, 64, 1, 3, 4>), grid, dim3(Cfg0::THREADS), lds, st, ra);
-                else if (k.xh == 11 && k.xw == 13)
-                    hipLaunchKernelGGL((resblock_bf16_kernel<64, 128, 3, 2, 8, 11, 13>), grid, dim3(Cfg1::THREADS), lds, st, ra);
-                else
-                    hipLaunchKernelGGL((resblock_bf16_kernel<64, 128, 3, 2, 8>), grid, dim3(Cfg1::THREADS), lds, st, ra);
+            case BLOCK_BF16_FIXED:
+            case BLOCK_BF16_RUNTIME: {
+                RbArgs ra{};
+                ra.x = static_cast<const bf16_t*>(k.x); ra.XH = b.in.h; ra.XW = b.in.w; ra.OH = b.out.h; ra.OW = b.out.w;
+                ra.n_clips = n;
+                ra.wf1 = m->d_wfrag[2 * i]; ra.b1 = k.b1;
+                ra.wf2 = m->d_wfrag[2 * i + 1]; ra.b2 = k.b2;
+                ra.out = static_cast<bf16_t*>(k.out);
+                if (i == 1) {
+                    ra.fcw = io.fcw; ra.fcb = io.fcb; ra.logits = d_logits; ra.probs = d_probs; ra.preds = d_preds;
+                    if (!p.store_a3) ra.out = nullptr;
+                }
+                hipLaunchKernelGGL(RB_KERNEL[i][b.kernel == BLOCK_BF16_FIXED], dim3((n + b.clips - 1) / b.clips),
+                                   dim3(rb_threads(RB_CFG[i])), b.lds, st, ra);
                 COUGH_HIP_CHECK(hipGetLastError());
-                if (i == 1) head_done = true;
-                continue;
+                break;
             }
+            case BLOCK_CONV_MFMA:
+                if (int e = launch_conv_pair<float>(k, b.in, b.out, 2, n, b.nt, st)) return e;
+                break;
+            case BLOCK_CONV_GEMM_BF16:
+                if (int e = launch_conv_pair<bf16_t>(k, b.in, b.out, 2, n, b.nt, st)) return e;
+                break;
         }
-        ConvArgs<T> c1{};
-        c1.in = reinterpret_cast<const T*>(k.x); c1.H = k.xh; c1.W = k.xw; c1.C = k.cin;
-        c1.KH = 3; c1.KW = 3; c1.stride = 2; c1.pad = 1;
-        c1.in2 = nullptr; c1.C2 = 0; c1.H2 = c1.W2 = 0; c1.stride2 = 1;
-        c1.wp = reinterpret_cast<const T*>(m->d_w[k.s1]); c1.bias = m->d_b[k.s1];
-        c1.out = reinterpret_cast<T*>(k.h); c1.OH = k.oh; c1.OW = k.ow; c1.N = k.cout; c1.Ktot = m->ktot[k.s1];
-        c1.M = (long long)n * k.oh * k.ow;
-        if (int e = launch_conv<T>(m, c1, st)) return e;
-        ConvArgs<T> c2{};
-        c2.in = reinterpret_cast<const T*>(k.h); c2.H = k.oh; c2.W = k.ow; c2.C = k.cout;
-        c2.KH = 3; c2.KW = 3; c2.stride = 1; c2.pad = 1;
-        c2.in2 = reinterpret_cast<const T*>(k.x); c2.H2 = k.xh; c2.W2 = k.xw; c2.C2 = k.cin; c2.stride2 = 2;
-        c2.wp = reinterpret_cast<const T*>(m->d_w[k.s2]); c2.bias = m->d_b[k.s2];
-        c2.out = reinterpret_cast<T*>(k.out); c2.OH = k.oh; c2.OW = k.ow; c2.N = k.cout; c2.Ktot = m->ktot[k.s2];
-        c2.M = (long long)n * k.oh * k.ow;
-        if (int e = launch_conv<T>(m, c2, st)) return e;
     }
-    if (!head_done) {
-        hipLaunchKernelGGL(tail_kernel<T>, dim3(n), dim3(128), 0, st, reinterpret_cast<const T*>(w.a3), s.B1h * s.B1w,
-                           m->d_fcw, m->d_fcb, d_logits, d_probs, d_preds);
-        COUGH_HIP_CHECK(hipGetLastError());
+
+    const BlockIO& last = io.blk[p.n_blocks - 1];
+    const int HWl = p.block[p.n_blocks - 1].out.h * p.block[p.n_blocks - 1].out.w;
+    switch (p.head) {
+        case HEAD_FUSED: break;
+        case HEAD_TAIL_F32:
+            hipLaunchKernelGGL(tail_kernel<float>, dim3(n), dim3(128), 0, st, static_cast<const float*>(last.out), HWl, io.fcw,
+                               io.fcb, d_logits, d_probs, d_preds);
+            break;
+        case HEAD_TAIL_BF16:
+            hipLaunchKernelGGL(tail_kernel<bf16_t>, dim3(n), dim3(128), 0, st, static_cast<const bf16_t*>(last.out), HWl, io.fcw,
+                               io.fcb, d_logits, d_probs, d_preds);
+            break;
+        case HEAD_TAIL_GENERIC:
+            hipLaunchKernelGGL(tail_generic_kernel, dim3(n), dim3(128), 0, st, static_cast<const float*>(last.out), HWl, io.c_last,
+                               last.cout, io.fcw, io.fcb, d_logits, d_probs, d_preds);
+            break;
     }
-    if (!rule_done) {   // a NaN pixel (pipeline: a non-finite sample) -> NaN logits, as torch's ReLU / max-pool propagate it
-        hipLaunchKernelGGL(nan_rule_kernel, dim3(n), dim3(256), 0, st, d_feat, (long long)s.H * s.W, nanflag, d_logits, d_probs,
+    if (p.head != HEAD_FUSED) COUGH_HIP_CHECK(hipGetLastError());
+    if (!p.nan_in_block1) {   // a NaN pixel (pipeline: a non-finite sample) -> NaN logits, as torch's ReLU / max-pool propagate it
+        hipLaunchKernelGGL(nan_rule_kernel, dim3(n), dim3(256), 0, st, d_feat, (long long)H * W, nanflag, d_logits, d_probs,
                            d_preds);
         COUGH_HIP_CHECK(hipGetLastError());
     }
     return COUGH_OK;
+}
+
+// Carve, then run the plan: the shipped net of every dtype and the generic net.  stem_done: the featurise kernel ran the stem.
+int run_net(const cough_resnet* m, const float* d_feat, int n, int H, int W, float* d_logits, float* d_probs, int* d_preds,
+            char* ws, hipStream_t st, bool stem_done = false) {
+    const NetPlan p = plan_resnet(m->dtype, !m->gen, m->gen ? m->gen->n_blocks : 2, H, W, stem_done);
+    return run_plan(m, p, net_io(m, ws, n, H, W), d_feat, n, H, W, d_logits, d_probs, d_preds, st);
 }
 
 }  // namespace
@@ -1223,28 +1209,17 @@ extern "C" int cough_resnet_create(cough_resnet** out, const cough_resnet_weight
         err = upload(reinterpret_cast<void**>(&m->d_fcw), fw);
         if (!err) err = upload(reinterpret_cast<void**>(&m->d_fcb), fb);
     }
-    if (!err && dtype == COUGH_DTYPE_BF16) {   // the fused block kernels use more than 64 KB of dynamic LDS
-        const void* fused[4] = {reinterpret_cast<const void*>(resblock_bf16_kernel<32, 64, 1, 3, 4>),
-                                reinterpret_cast<const void*>(resblock_bf16_kernel<32, 64, 1, 3, 4, 22, 25>),
-                                reinterpret_cast<const void*>(resblock_bf16_kernel<64, 128, 3, 2, 8>),
-                                reinterpret_cast<const void*>(resblock_bf16_kernel<64, 128, 3, 2, 8, 11, 13>)};
+    if (!err) {   // the fused block kernels of the mode use more than 64 KB of dynamic LDS
+        std::vector<const void*> fused;
+        if (dtype == COUGH_DTYPE_BF16)
+            for (const auto& blk : RB_KERNEL)
+                for (const auto kernel : blk) fused.push_back(reinterpret_cast<const void*>(kernel));
+        if (dtype == COUGH_DTYPE_BF16X3)
+            for (int i = 0; i < 2; ++i)
+                for (int r = 0; r < RBX_NROWS[i]; ++r) fused.push_back(reinterpret_cast<const void*>(RBX_TABLE[i][r].kernel));
         hipError_t e = hipSuccess;
         for (const void* fn : fused)
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            set_error("cough_resnet_create: %s", hipGetErrorString(e));
-            err = COUGH_EHIP;
-        }
-    }
-    if (!err && dtype == COUGH_DTYPE_BF16X3) {   // more than 64 KB of dynamic LDS
-#define RBX_FN0(R) reinterpret_cast<const void*>(resblock_x3_kernel<32, 64, 1, R, 25>),
-#define RBX_FN1(R) reinterpret_cast<const void*>(resblock_x3_kernel<64, 128, rbx_block1_clips(R), R, 13>),
-        const void* fused[] = {RBX_BLOCK0_ROWS(RBX_FN0) RBX_BLOCK1_ROWS(RBX_FN1)};
-#undef RBX_FN0
-#undef RBX_FN1
-        hipError_t e = hipSuccess;
-        for (const void* fn : fused)
-            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(RB_LDS_LIMIT));
         if (e != hipSuccess) {
             set_error("cough_resnet_create: %s", hipGetErrorString(e));
             err = COUGH_EHIP;
@@ -1359,7 +1334,7 @@ extern "C" int cough_resnet_forward(const cough_resnet* m, const float* d_feat, 
     COUGH_REQUIRE(n_clips >= 0 && height >= 1 && width >= 1, COUGH_EINVAL, "cough_resnet_forward: bad shape");
     const Shapes s = make_shapes(height, width);
     if (m->gen) {
-        const std::vector<GenShape> sh = gen_shapes(m->gen, height, width);
+        const std::vector<HW> sh = gen_shapes(m->gen, height, width);
         COUGH_REQUIRE(sh.back().h >= 1 && sh.back().w >= 1 && sh[0].h >= 1 && sh[0].w >= 1, COUGH_EINVAL,
                       "cough_resnet_forward: input %dx%d too small for the network", height, width);
     } else
@@ -1372,9 +1347,7 @@ extern "C" int cough_resnet_forward(const cough_resnet* m, const float* d_feat, 
     if (n_clips == 0) return COUGH_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(d_workspace);
-    if (m->gen) return gen_forward(m->gen, d_feat, n_clips, height, width, d_logits, d_probs, d_preds, ws, st);
-    if (m->esize == 4) return forward_impl<float>(m, d_feat, n_clips, s, d_logits, d_probs, d_preds, ws, st);
-    return forward_impl<bf16_t>(m, d_feat, n_clips, s, d_logits, d_probs, d_preds, ws, st);
+    return run_net(m, d_feat, n_clips, height, width, d_logits, d_probs, d_preds, ws, st);
 }
 
 extern "C" int cough_resnet_read_activation(const cough_resnet* m, const void* d_workspace, int n_clips, int height,
@@ -1385,7 +1358,7 @@ extern "C" int cough_resnet_read_activation(const cough_resnet* m, const void* d
         const cough_resnet_generic* g = m->gen;
         COUGH_REQUIRE(which >= 1 && which <= g->n_blocks + 1, COUGH_EINVAL, "cough_resnet_read_activation: which must be 1..%d",
                       g->n_blocks + 1);
-        const std::vector<GenShape> sh = gen_shapes(g, height, width);
+        const std::vector<HW> sh = gen_shapes(g, height, width);
         const GenWorkspace gw = gen_carve(g, const_cast<char*>(static_cast<const char*>(d_workspace)), n_clips, sh);
         const int C = g->ch[which - 1], Cp = g->chp[which - 1], HW = sh[which - 1].h * sh[which - 1].w;
         const long long total = (long long)n_clips * C * HW;
@@ -1456,8 +1429,7 @@ extern "C" int cough_pipeline_forward(const cough_featurizer* f, const cough_res
         const StemFuse stem{m->d_stem_wfrag, m->d_stem_b, w.a1, m->dtype == COUGH_DTYPE_BF16X3 ? 1 : 0, w.nanflag};
         if (int e = launch_featurize(f, d_wav, wav_stride, d_feat, n_clips, flags, &stem, st)) return e;
         if (ev_featurize_end) COUGH_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev_featurize_end), st));
-        if (m->esize == 4) return forward_impl<float>(m, nullptr, n_clips, s, d_logits, d_probs, d_preds, ws, st, true);
-        return forward_impl<bf16_t>(m, nullptr, n_clips, s, d_logits, d_probs, d_preds, ws, st, true);
+        return run_net(m, nullptr, n_clips, H, W, d_logits, d_probs, d_preds, ws, st, true);
     }
     const size_t net_bytes = cough_resnet_workspace_bytes(m, n_clips, H, W);
     const size_t feat_bytes = align256(size_t(n_clips) * H * W * sizeof(float));
@@ -1466,9 +1438,7 @@ extern "C" int cough_pipeline_forward(const cough_featurizer* f, const cough_res
                                  plan_featurize(f, 0, n_clips).workspace))
         return e;
     if (ev_featurize_end) COUGH_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev_featurize_end), st));
-    if (m->gen) return gen_forward(m->gen, feat, n_clips, H, W, d_logits, d_probs, d_preds, ws, st);
-    if (m->esize == 4) return forward_impl<float>(m, feat, n_clips, s, d_logits, d_probs, d_preds, ws, st);
-    return forward_impl<bf16_t>(m, feat, n_clips, s, d_logits, d_probs, d_preds, ws, st);
+    return run_net(m, feat, n_clips, H, W, d_logits, d_probs, d_preds, ws, st);
 }
 
 // ------------------------------------------------------------------------------ one ResidualBlock on its own
@@ -1578,19 +1548,8 @@ extern "C" int cough_resblock_forward(const cough_resblock* m, const float* d_x,
         hipLaunchKernelGGL(nchw_to_nhwc_padded_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_x, x, m->cin,
                            m->cinp, height * width, total);
     }
-    const long long M = (long long)n * s.oh * s.ow;
-    ConvArgs<float> c1{};
-    c1.in = x; c1.H = height; c1.W = width; c1.C = m->cinp; c1.KH = 3; c1.KW = 3; c1.stride = m->stride; c1.pad = 1;
-    c1.in2 = nullptr; c1.C2 = 0; c1.H2 = c1.W2 = 0; c1.stride2 = 1;
-    c1.wp = m->d_w1; c1.bias = m->d_b1; c1.out = h; c1.OH = s.oh; c1.OW = s.ow; c1.N = m->coutp; c1.Ktot = m->k1; c1.M = M;
-    ConvArgs<float> c2{};
-    c2.in = h; c2.H = s.oh; c2.W = s.ow; c2.C = m->coutp; c2.KH = 3; c2.KW = 3; c2.stride = 1; c2.pad = 1;
-    c2.in2 = x; c2.H2 = height; c2.W2 = width; c2.C2 = m->cinp; c2.stride2 = m->stride;
-    c2.wp = m->d_w2; c2.bias = m->d_b2; c2.out = y; c2.OH = s.oh; c2.OW = s.ow; c2.N = m->coutp; c2.Ktot = m->k2; c2.M = M;
-    const long long tiles = (M + 31) / 32;
-    const dim3 grid((unsigned)((tiles + 3) / 4), m->coutp / 32);
-    hipLaunchKernelGGL((conv_mfma_kernel<float, 1>), grid, dim3(256), 0, st, c1);
-    hipLaunchKernelGGL((conv_mfma_kernel<float, 1>), grid, dim3(256), 0, st, c2);
+    const BlockIO io{x, h, y, m->cinp, m->coutp, m->d_w1, m->d_w2, m->d_b1, m->d_b2, m->k1, m->k2};
+    if (int e = launch_conv_pair<float>(io, {height, width}, {s.oh, s.ow}, m->stride, n, 1, st)) return e;
     {
         const long long total = (long long)n * m->cout * s.oh * s.ow;
         hipLaunchKernelGGL(nhwc_padded_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, y, d_y, m->cout,

@@ -155,7 +155,7 @@ class CoughDetectorResidual(NativeModule):
         rows on the shipped set) and 63..70 rows (use_mfcc=False, 64 rows + contrast rows).
 
         ``"fp32"`` for a ``bf16x3`` model with the shipped channels is NOT "every kernel in exact f32": the kernels are
-        picked per stage (``csrc/resnet.hip: forward_impl``; restated as ``plan()`` in ``tests/resnet_layer_ref.py``).
+        picked per stage (``csrc/resnet_plan.h: plan_resnet``; restated as ``plan()`` in ``tests/resnet_layer_ref.py``).
         The stem is the split-bf16 kernel whenever the image has at most 11 264 pixels and fits its LDS image, and
         block 1 is the fused split-bf16 kernel (with its head) whenever ITS input is one of the compiled 8..14 x 13
         shapes, whatever ran block 0 -- e.g. 71..74, 83..86 and 99..102 rows at 99..102 frames, or 103..106 frames at a
@@ -166,7 +166,8 @@ class CoughDetectorResidual(NativeModule):
         if self.channels != (32, 64, 128):
             return "fp32"
         if self.compute_dtype == "bf16x3":
-            # the kernels are selected by the block-0 input (stem + pool output), csrc/resnet.hip rbx_compiled():
+            # the kernels are selected by the block-0 input (stem + pool output), csrc/resnet_plan.h: rbx_compiled() over
+            # RBX_BLOCK0_ROWS x RBX_COLS[0], which X3_BLOCK_INPUTS below restates (tests/test_resnet_layer_ref_host.py):
             # 16x25 <- 63..66 rows, 17x25 <- 67..70, 22x25 <- 87..90, 23x25 <- 91..94, 24x25 <- 95..98, 26x25 <- 103..106,
             # 27x25 <- 107..110, each x 99..102 frames: every image the reference's flags produce at 1 s
             p1 = (((height - 1) // 2 + 1) // 2, ((width - 1) // 2 + 1) // 2)

@@ -1,5 +1,5 @@
 """Float64 restatement of ``CoughDetectorResidual`` stage by stage, a Python restatement of the kernel dispatch of
-``csrc/resnet.hip`` (``plan``), the per-pixel error budget of each kernel family (``stage_bound``), a CPU emulation of the
+``csrc/resnet_plan.h`` (``plan``), the per-pixel error budget of each kernel family (``stage_bound``), a CPU emulation of the
 three operand schemes with plantable defects (``emulate_stage``) and the shape matrix the host and GPU tests share
 (``CASES`` with the hand-written ``EXPECT``).  The conv-stack counterpart is ``cnn_layer_ref.py``; the constants U, C_F32,
 E_BF16, E_SPLIT and the three bound families are the ones defined there.
@@ -13,11 +13,11 @@ writes them, in float64, for any channel tuple; ``tests/test_resnet_layer_ref_ho
 
 Dispatch (``plan``)
 -------------------
-Transcribed from ``make_shapes``, ``stem_lds``, ``rbx_compiled``, ``rbx_t16``, ``rbx_block1_clips``,
-``RbCfg::lds_bytes`` / ``MTMAX``, ``launch_conv`` and the conditions of ``forward_impl`` / ``gen_forward``.  The constants
-below mirror ``STEM_SB_MAXL``, ``RBX_BLOCK0_ROWS``, ``RBX_BLOCK1_ROWS``, ``RBX_G_TALL``, the two ``RbCfg<...>`` parameter
-lists and the 64 KB / 160 KB limits; ``test_plan_constants_are_the_ones_in_resnet_hip`` reads them, and the launch
-conditions, out of the source, so a retune fails there.
+Transcribed from ``csrc/resnet_plan.h``: ``make_shapes``, ``stem_lds``, ``rbx_compiled``, ``rbx_t16``,
+``rbx_block1_clips``, ``rb_lds_bytes`` / ``rb_mtmax`` / ``rb_fits`` and ``plan_resnet``, which ``resnet.hip`` executes.  The
+constants below mirror ``STEM_SB_MAXL``, ``RBX_BLOCK0_ROWS``, ``RBX_BLOCK1_ROWS``, ``RBX_G_TALL``, ``RB_CFG``, ``RB_FIXED`` and
+the 64 KB / 160 KB limits.  ``tests/test_resnet_layer_ref_host.py`` builds ``tests/resnet_plan_dump.cpp`` over that header
+and holds its constants and its plans of some 227 000 images equal to the ones here, so a retune fails there.
 
 Error budget (``stage_bound``)
 ------------------------------

@@ -1,14 +1,19 @@
 """Host tests of tests/resnet_layer_ref.py: the float64 stages against oracle/resnet.py, the dispatch restatement against
-the source it transcribes and against the hand-written table, the derived per-pixel bounds against a CPU emulation of each
+the plans csrc/resnet_plan.h itself computes (tests/resnet_plan_dump.cpp) and against the hand-written table, the derived per-pixel bounds against a CPU emulation of each
 operand scheme over the whole GPU matrix, and planted defects that the per-pixel check must flag."""
+import atexit
 import functools
 import os
 import re
+import shutil
+import subprocess
+import tempfile
 
 import pytest
 import torch
 
 import resnet_layer_ref as R
+from cough_detector_amd import build as cbuild
 from cough_detector_amd import synth
 from oracle import resnet as ores
 
@@ -40,64 +45,132 @@ def test_stages_are_the_oracle(channels, shape):
     assert float((z - acts[1]).abs().max()) <= 1e-12 * max(1.0, float(acts[1].abs().max()))
 
 
-def _src(*parts):
-    return open(os.path.join(ROOT, "cough_detector_amd", "csrc", *parts)).read()
+# ------------------------------------------------------------------------------------------ the C++ plan against plan()
+CSRC = os.path.join(ROOT, "cough_detector_amd", "csrc")
 
 
-def test_plan_constants_are_the_ones_in_resnet_hip():
-    """plan() restates the dispatch with constants of its own; this ties them to the source the library is built from, so a
-    retune of STEM_SB_MAXL, the RBX row lists, RBX_G_TALL or the RbCfg parameter lists (or of the launch rules quoted below)
-    fails here until plan(), EXPECT and the matrix have been revisited."""
-    src, rbx = _src("resnet.hip"), _src("resblock_x3.h")
-    maxl = re.findall(r"constexpr int STEM_SB_MAXL = (\d+);", src)
-    assert [int(v) for v in maxl] == [R.STEM_SB_MAXL]
-    for name, want in (("RBX_BLOCK0_ROWS", R.RBX_BLOCK0_ROWS), ("RBX_BLOCK1_ROWS", R.RBX_BLOCK1_ROWS)):
-        defs = re.findall(rf"#define {name}\(X\)((?: X\(\d+\))+)\s*$", src, flags=re.M)
-        assert len(defs) == 1, (name, defs)                      # one definition: no second list to drift to
-        assert tuple(int(v) for v in re.findall(r"X\((\d+)\)", defs[0])) == want, (name, defs[0])
-    assert [int(v) for v in re.findall(r"constexpr int RBX_G_TALL = (\d+);", src)] == [R.RBX_G_TALL]
-    cfgs = re.findall(r"using Cfg([01]) = RbCfg<(\d+), (\d+), (\d+), (\d+), (\d+)>;", src)
-    assert [(int(c[0]),) + tuple(int(v) for v in c[1:]) for c in cfgs] == [(0,) + R.RB_CFG[0], (1,) + R.RB_CFG[1]], cfgs
-    # the launch rules plan() transcribes, as they stand in the source
-    for rule in ("const int c1h = (H + 6 - 7) / 2 + 1, c1w = (W + 6 - 7) / 2 + 1;",
-                 "s.P1h = c1h / 2; s.P1w = c1w / 2;",
-                 "s.B0h = (s.P1h + 2 - 3) / 2 + 1; s.B0w = (s.P1w + 2 - 3) / 2 + 1;",
-                 "s.B1h = (s.B0h + 2 - 3) / 2 + 1; s.B1w = (s.B0w + 2 - 3) / 2 + 1;",
-                 "l.nrows = std::max(4 * s.P1h + 6, s.H + 3);",
-                 "l.pitch = (std::max(4 * s.P1w + 6, s.W + 3) + 1) & ~1;",
-                 "l.bytes = size_t(l.nrows) * l.pitch * 2;",
-                 "m->dtype == COUGH_DTYPE_BF16 && stem_lds(s).bytes <= 64 * 1024 && s.H * s.W <= 2 * 256 * STEM_SB_MAXL",
-                 "m->dtype == COUGH_DTYPE_BF16X3 && 2 * stem_lds(s).bytes <= 64 * 1024 && s.H * s.W <= 2 * 256 * STEM_SB_MAXL",
-                 "constexpr int rbx_block1_clips(int xh) { return xh <= 12 ? 2 : RBX_G_TALL; }",
-                 "return blk == 0 ? (xw == 25 && (false RBX_BLOCK0_ROWS(RBX_HAS))) : (xw == 13 && (false RBX_BLOCK1_ROWS(RBX_HAS)));",
-                 "if (m->dtype == COUGH_DTYPE_BF16X3 && rbx_compiled(i, k.xh, k.xw)) {",
-                 "ra.wf = rbx_t16(k.cin, k.cout, k.xh) ? m->d_wx3t16[i] : m->d_wx3[i];",
-                 "if (nanflag) { ra.nanflag = nanflag; rule_done = true; }",
-                 "rbx_launch<32, 64, 1, R, 25>(n, st, ra);",
-                 "rbx_launch<64, 128, rbx_block1_clips(R), R, 13>(n, st, ra);",
-                 "static constexpr int NT = COUT / 32, MG = WAVES / NT, MTMAX = MG * MW;",
-                 "const size_t images = (size_t(G) * (XH + 2) * (XW + 2) * CIN + size_t(G) * (OH + 2) * (OW + 2) * COUT) * 2;",
-                 "const size_t tile = size_t(MTMAX) * 32 * (COUT + 8) * 2 + size_t(WAVES) * 2 * sizeof(float);",
-                 "const int g = i == 0 ? 1 : 3, mtmax = i == 0 ? Cfg0::MTMAX : Cfg1::MTMAX;",
-                 "if (m->dtype == COUGH_DTYPE_BF16 && lds <= 160 * 1024 && g * k.oh * k.ow <= mtmax * 32 &&",
-                 "g * k.xh * k.xw * (k.cin / 8) <= 16 * threads) {",
-                 "if (i == 0 && k.xh == 22 && k.xw == 25)",
-                 "else if (k.xh == 11 && k.xw == 13)",
-                 "if (a.N == 64) hipLaunchKernelGGL((conv_gemm_bf16_kernel<2>), grid, dim3(256), 0, st, a);",
-                 "else hipLaunchKernelGGL((conv_gemm_bf16_kernel<4>), grid, dim3(256), 0, st, a);",
-                 "if (a.N == 64) hipLaunchKernelGGL((conv_mfma_kernel<T, 2>), grid, dim3(256), 0, st, a);",
-                 "else hipLaunchKernelGGL((conv_mfma_kernel<T, 4>), grid, dim3(256), 0, st, a);",
-                 "if (!head_done) {", "if (!rule_done) {",
-                 "hipLaunchKernelGGL(tail_kernel<T>, dim3(n), dim3(128), 0, st,",
-                 "hipLaunchKernelGGL((conv_mfma_kernel<float, 1>), grid, dim3(256), 0, st, c1);",
-                 "hipLaunchKernelGGL(tail_generic_kernel, dim3(n), dim3(128), 0, st,",
-                 "hipLaunchKernelGGL(nan_rule_kernel, dim3(n), dim3(256), 0, st, d_feat, (long long)H * W, nullptr,",
-                 "m->dtype = COUGH_DTYPE_FP32;   // every dtype runs a non-shipped channel tuple"):
-        assert rule in src, rule
-    for rule in ("constexpr bool rbx_t16_shape(int cin, int cout) { return (cin == 32 && cout == 64) || (cin == 64 && cout == 128); }",
-                 "return rbx_t16_shape(cin, cout) && (cin == 64 || xh <= 26);"):
-        assert rule in rbx, rule
+@functools.lru_cache(maxsize=None)
+def _dump_exe():
+    """tests/resnet_plan_dump.cpp built once per session by a host compiler: csrc/resnet_plan.h includes no HIP header."""
+    out = tempfile.mkdtemp(prefix="resnet_plan_dump_")
+    atexit.register(shutil.rmtree, out, ignore_errors=True)
+    exe = os.path.join(out, "resnet_plan_dump")
+    cxx = [shutil.which("c++")] if shutil.which("c++") else [cbuild._hipcc(), "-x", "c++"]
+    subprocess.run([*cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "resnet_plan_dump.cpp"),
+                    "-o", exe], check=True)
+    return exe
+
+
+def _dump(queries):
+    """(constants of the header, one plan line per (dtype, H, W, channels) query)."""
+    text = "".join(f"{d} {'shipped' if tuple(ch) == R.SHIPPED else 'generic'} {len(ch) - 1} {h} {w}\n" for d, h, w, ch in queries)
+    out = subprocess.run([_dump_exe()], input=text, capture_output=True, text=True, check=True).stdout
+    head, _, body = out.partition("---\n")
+    consts = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in head.splitlines()}
+    lines = body.splitlines()
+    assert len(lines) == len(queries)
+    return consts, lines
+
+
+def _tail(p, pipeline):
+    """The NaN rule and the a3 store as resnet.hip applies them: block 1's fused split-bf16 head takes the per-clip flag, every
+    other plan ends with nan_rule_kernel; behind the featuriser's stem a fused block 1 does not store its output."""
+    nan = "flag" if pipeline else p.nan
+    by = "block1" if nan == "flag" and len(p.blocks) == 2 and p.blocks[1].kernel == "resblock_x3" else "nan_rule_kernel"
+    return f"{nan} by={by} a3={'skip' if pipeline and p.head == 'fused' else 'store'}"
+
+
+def _line(dtype, H, W, channels=R.SHIPPED):
+    """The line resnet_plan_dump prints for a query, from plan() and the launch arithmetic of resnet_layer_ref."""
+    p = R.plan(dtype, H, W, channels)
+    if p is None:
+        return "none"
+    stem_lds = {"stem_bf16<bf16>": 1, "stem_bf16<x3>": 2}.get(p.stem.kernel, 0) * R.stem_lds(H, W)
+    parts = [f"{p.stem.kernel} lds={stem_lds}"]
+    for i, b in enumerate(p.blocks):
+        lds = R.rb_lds_bytes(R.RB_CFG[i], *b.in_hw, *b.out_hw) if b.kernel.startswith("resblock_bf16") else 0
+        parts.append(f"{b.kernel} {b.body} {b.clips} {R.stage_path(b)} {b.in_hw[0]}x{b.in_hw[1]}->{b.out_hw[0]}x{b.out_hw[1]} lds={lds}")
+    parts += [p.head, _tail(p, False)]
+    if tuple(channels) == R.SHIPPED and dtype != "fp32":
+        parts.append(f"pipeline: featurize_kernel {p.head} " + _tail(p, True))
+    return " | ".join(parts)
+
+
+def _row(line):
+    """plan_row of a dumped line."""
+    f = line.split(" | ")
+    if f[-1].startswith("pipeline: "):
+        f.pop()
+    blocks = [(k, body, int(clips)) for k, body, clips in (b.split()[:3] for b in f[1:-2])]
+    return (f[0].split()[0], blocks, f[-2], f[-1].split()[0])
+
+
+def test_cxx_plan_gives_the_hand_written_row_of_every_case():
+    _, lines = _dump([(c.dtype, c.H, c.W, c.channels) for c in R.CASES])
+    for c, line in zip(R.CASES, lines):
+        assert _row(line) == R.EXPECT[R.case_id(c)], (R.case_id(c), line)
+        assert line == _line(c.dtype, c.H, c.W, c.channels)
+
+
+def test_cxx_plan_is_plan_over_the_sweep():
+    """plan_resnet (csrc/resnet_plan.h, what resnet.hip executes) against plan(), field by field: stem and its LDS, each block's
+    kernel, body, clips, instantiation name, shapes and LDS, the head, the NaN rule and who applies it, the a3 store, and the
+    same for the forward behind the featuriser's stem.  Every dtype over H, W = 1..130 and the low, wide strips up to 1600
+    columns, which hold the deciding cases of every limit (named below), plus the generic tuples of the matrix."""
+    hw = [(h, w) for h in range(1, 131) for w in range(1, 131)] + [(h, w) for h in range(1, 41) for w in range(131, 1601)]
+    queries = [(d, h, w, R.SHIPPED) for d in R.DTYPES for h, w in hw]
+    assert len(queries) == 227100
+    for d in R.DTYPES:
+        queries += [(d, 40, 33, (5, 7, 9)), (d, 17, 30, (64, 32))]
+    _, lines = _dump(queries)
+    at = {q[:3]: ln for q, ln in zip(queries, lines) if q[3] == R.SHIPPED}
+    bad = [(q, ln) for q, ln in zip(queries, lines) if ln != _line(*q)]
+    assert not bad, (len(bad), bad[0], _line(*bad[0][0]))
+    # the sweep reaches every kernel path of the matrix ...
+    seen = set()
+    for ln in lines:
+        if ln != "none":
+            f = ln.split(" | ")
+            seen.add(f[0].split()[0])
+            seen.update(b.split()[3] for b in f[1:] if "->" in b)
+            seen.add(f[-3] if f[-1].startswith("pipeline: ") else f[-2])
+    assert {"stem_mfma<float>", "stem_mfma<bf16>", "stem_bf16<x3>", "stem_bf16<bf16>",
+            "conv_mfma<float,1>", "conv_mfma<float,2>", "conv_mfma<float,4>", "conv_gemm_bf16<2>", "conv_gemm_bf16<4>",
+            "resblock_x3<25,16x16x32,G1>", "resblock_x3<25,32x32,G1>", "resblock_x3<13,16x16x32,G1>", "resblock_x3<13,16x16x32,G2>",
+            "resblock_bf16:fixed<G1>", "resblock_bf16:fixed<G3>", "resblock_bf16:runtime<G1>", "resblock_bf16:runtime<G3>",
+            "fused", "tail_kernel<float>", "tail_kernel<bf16>", "tail_generic_kernel"} <= seen
+    # ... and the two sides of every limit: the stem's pixel count, its two-plane LDS, block 1's pixel tiles, 160 KB alone
+    assert at["bf16x3", 110, 102].startswith("stem_bf16<x3> ") and at["bf16x3", 110, 103].startswith("stem_mfma<float> ")
+    assert at["bf16x3", 8, 1400].startswith("stem_mfma<float> ") and at["bf16_approx", 8, 1400].startswith("stem_bf16<bf16> lds=39368 ")
+    assert "resblock_bf16:runtime<G3> 12x13->6x7" in at["bf16_approx", 96, 101] and "conv_gemm_bf16<4> 13x13->7x7" in at["bf16_approx", 99, 101]
+    assert "resblock_bf16:runtime<G1> 8x84->4x42" in at["bf16_approx", 32, 336] and "conv_gemm_bf16<4> 4x42->2x21" in at["bf16_approx", 32, 336]
+    assert "conv_gemm_bf16<2> 2x384->1x192" in at["bf16_approx", 8, 1536]      # 192 pixels fit the tiles; 173 312 B do not (2 x 362: 163 456 B do)
+    assert "resblock_bf16:runtime<G1> 2x362->1x181 lds=163456" in at["bf16_approx", 8, 1448] and "conv_gemm_bf16<2> 2x363->1x182" in at["bf16_approx", 8, 1452]
+
+
+def test_plan_constants_are_the_header_s_and_defined_once():
+    """plan() restates the dispatch with constants of its own; this ties them to the header the library is built from, so a
+    retune of STEM_SB_MAXL, the RBX row lists, RBX_G_TALL, the RbCfg parameter lists, the fixed geometries or the two LDS
+    limits fails here until plan(), EXPECT and the matrix have been revisited."""
+    consts, _ = _dump([])
+    assert consts == {"STEM_SB_MAXL": (R.STEM_SB_MAXL,), "RBX_BLOCK0_ROWS": R.RBX_BLOCK0_ROWS, "RBX_BLOCK1_ROWS": R.RBX_BLOCK1_ROWS,
+                      "RBX_COLS": (25, 13), "RBX_G_TALL": (R.RBX_G_TALL,), "NET_CH": R.SHIPPED, "RB_CFG": R.RB_CFG[0] + R.RB_CFG[1],
+                      "RB_FIXED": R.RB_FIXED[0] + R.RB_FIXED[1], "RB_MTMAX": tuple(R.rb_mtmax(c) for c in R.RB_CFG),
+                      "RB_THREADS": tuple(c[4] * 64 for c in R.RB_CFG), "STEM_LDS_LIMIT": (R.STEM_LDS_LIMIT,),
+                      "RB_LDS_LIMIT": (R.RB_LDS_LIMIT,), "PLAN_MAX_BLOCKS": (16,)}
     assert R.RB_FIXED == ((22, 25), (11, 13)) and R.STEM_LDS_LIMIT == 64 * 1024 and R.RB_LDS_LIMIT == 160 * 1024
+    # one definition in csrc/: no second list or constant to drift to
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC))}
+    for name in ("STEM_SB_MAXL", "RBX_BLOCK0_ROWS", "RBX_BLOCK1_ROWS", "RBX_COLS", "RBX_G_TALL", "RB_CFG", "RB_FIXED", "STEM_LDS_LIMIT",
+                 "RB_LDS_LIMIT", "NET_CH"):
+        defs = [f for f, text in src.items() for _ in re.findall(rf"(?:#define\s+{name}\b|\b{name}(?:\[\d*\])*\s*=[^=])", text)]
+        assert defs == ["resnet_plan.h"], (name, defs)
+    for rows in (R.RBX_BLOCK0_ROWS, R.RBX_BLOCK1_ROWS):          # ... under any name or as an X-macro
+        lists = [f for f, text in src.items() for _ in re.findall(r"\D{1,6}".join(rf"\b{r}\b" for r in rows), text)]
+        assert lists == ["resnet_plan.h"], (rows, lists)
+    for fn in ("make_shapes", "stem_lds", "rbx_compiled", "rbx_t16", "rbx_block1_clips", "rb_lds_bytes", "rb_mtmax", "plan_resnet"):
+        defs = [f for f, text in src.items() for _ in re.findall(rf"^(?:constexpr|inline|static)[\w \*&:<>]*\b{fn}\(", text, flags=re.M)]
+        assert defs == ["resnet_plan.h"], (fn, defs)
     # no build of the library overrides the tables from the command line
     build_py = open(os.path.join(ROOT, "cough_detector_amd", "build.py")).read()
     assert "RBX_BLOCK" not in build_py and "STEM_SB_MAXL" not in build_py and "RBX_G_TALL" not in build_py
