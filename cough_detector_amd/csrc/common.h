@@ -51,9 +51,19 @@ inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(
 // ---- wave64 / block reductions -------------------------------------------------------------
 // DPP reductions (no LDS crossbar round trips): quad swaps, half-row / row mirrors give every lane its
 // 16-lane row total; two xor-shuffles then combine the four rows.
-template <int CTRL, int ROW_MASK = 0xf>
+// dpp_mov is only valid for controls that are full permutations of the 16-lane row, with every row and bank enabled: then
+// each lane is written from a lane of its own row and the destination's previous content (`old`) is never read, so it is left
+// undefined -- an `old` of 0 costs a v_mov_b32 v, 0 in front of every v_mov_b32_dpp, and chains through one temporary wait out
+// the DPP hazard with s_nop.  bound_ctrl = true keeps what a disabled source lane supplied before: 0.
+constexpr bool dpp_full_row_permutation(int ctrl) {
+    return ctrl == 0xB1 || ctrl == 0x4E       // quad_perm [1,0,3,2], [2,3,0,1]
+        || ctrl == 0x141 || ctrl == 0x140     // row_half_mirror, row_mirror
+        || ctrl == 0x121;                     // row_ror:1
+}
+template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+    static_assert(dpp_full_row_permutation(CTRL), "dpp_mov: the control must permute the whole row (old is undefined)");
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_mov<0xB1>(v));    // quad_perm [1,0,3,2]

@@ -123,6 +123,20 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define K1_MARK(text) do { } while (0)
 #endif
 
+// max(m, |a|, |b|) as ONE v_max3_f32 with |.| modifiers.  fmaxf nesting costs three instructions per pair: a loaded sample may
+// be a signalling NaN, so each operand is canonicalised first.  A quiet NaN is ignored as fmaxf ignores it; a signalling one in
+// a lane's last pair makes that lane's peak NaN, which wave_max drops (the clip's image is NaN either way).
+__device__ __forceinline__ float max3_abs(float m, float a, float b) {
+    float r;
+    asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
+    return r;
+}
+// First sample pair of a lane that a frame scans for the clip's peak.  A frame loads its samples 32 .. 479; in frame t's count
+// frame t - 1 has scanned up to 479 - HOP = 319, so the pairs from 10 on would do.  9 is the pair of the first window tap that
+// is new to the frame (sample 296 of 56 | 400 | 56): the scanned ranges overlap by one pair row.
+constexpr int PEAK_N1 = 9;
+static_assert(32 * PEAK_N1 <= 32 * 15 - HOP, "the pairs from PEAK_N1 on join the previous frame's");
+
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 __device__ __forceinline__ uint16_t f2bf(float f) {
@@ -284,8 +298,8 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
     float peak = 0.f;            // max |sample| seen by this lane
     float chk = 0.f;             // stays 0 while every mel power of this lane is finite, NaN otherwise (acc * 0)
     // Frame samples are fetched one group AHEAD of their use (28 VGPRs): the HBM/L2 latency of a
-    // group's 14 eight-byte loads hides behind the ~600 VALU instructions of the previous group, and every
-    // byte of the clip is requested from HBM once.
+    // group's 14 eight-byte loads hides behind the ~480 VALU instructions that follow the previous group's
+    // first radix-16, and every byte of the clip is requested from HBM once.
     // GEO: the four frames of group g lie inside the clip with their whole 512-sample spans (wave-uniform)
     auto geo_plain = [&](int g) {
         return HP * (FPW * g) - PADL >= 0 && FPW * g + FPW - 1 < NF && HP * (FPW * g + FPW - 1) - PADL + NFFT <= NSMP;
@@ -342,10 +356,20 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
             w_im[n1] = tb->win[32 * n1 + jw + 1] * ws1 * ws2;
         }
         load_group(wave, raw);
+        // Peak of the clip, from each sample once.  Frame t loads clip samples [160 t - 224, 160 t + 224) (reflected at the clip's
+        // ends); its pairs PEAK_N1..14 are [160 t + 32, 160 t + 224), which joins the previous frame's and leaves only the pairs
+        // below PEAK_N1 of frame 0 -- taken here from all four frames of group 0.  Frames 99 and 100 reach 15999 and reflect back,
+        // so the union is the whole clip.  GEO keeps the scan of every pair in the loop.
+        if constexpr (!GEO) {
+            if (wave == 0) {
+#pragma unroll
+                for (int n1 = N1A; n1 < PEAK_N1; ++n1) peak = max3_abs(peak, raw[n1].x, raw[n1].y);
+            }
+        }
 
         K1_MARK("LOOP 6.5 P1 four-frame groups per wave");
         for (int g = wave; g < NGR; g += WAVES) {
-            K1_MARK("PHASE P1 peak + window multiply + next group's loads");
+            K1_MARK("PHASE P1 peak + window multiply");
             const int t_raw = FPW * g + fsub;
             const int t = t_raw < NF ? t_raw : NF - 1;             // idle sub-frames redo the last frame
             const int s0 = HP * t - PADL + 2 * j;                  // clip index of padded sample 2j of frame t
@@ -354,12 +378,16 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
                 a[0] = make_float2(0.f, 0.f);    // window is zero on samples [0,56) and [456,512)
                 a[15] = make_float2(0.f, 0.f);
             }
+            if constexpr (GEO) {   // run-time hop and window: every loaded pair of every frame
+#pragma unroll
+                for (int n1 = N1A; n1 < N1B; ++n1) peak = fmaxf(peak, fmaxf(fabsf(raw[n1].x), fabsf(raw[n1].y)));
+            } else {               // the pairs new to this frame (group 0 took the others in front of the loop)
+#pragma unroll
+                for (int n1 = PEAK_N1; n1 < N1B; ++n1) peak = max3_abs(peak, raw[n1].x, raw[n1].y);
+            }
             if constexpr (!PRE_EMPH) {
 #pragma unroll
-                for (int n1 = N1A; n1 < N1B; ++n1) {
-                    peak = fmaxf(peak, fmaxf(fabsf(raw[n1].x), fabsf(raw[n1].y)));   // one v_max3_f32 with |.| modifiers
-                    a[n1] = make_float2(raw[n1].x * w_re[n1], raw[n1].y * w_im[n1]);
-                }
+                for (int n1 = N1A; n1 < N1B; ++n1) a[n1] = make_float2(raw[n1].x * w_re[n1], raw[n1].y * w_im[n1]);
             }
             if constexpr (PRE_EMPH) {
                 // y[n] = x[n] - coef*x[n-1], y[0] = x[0] (preprocessing.py:235-238), applied before the reflect padding as the
@@ -375,7 +403,6 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
                         const float left = j == 0 ? carry : rot;
                         carry = rot;
                         const float x0 = raw[n1].x, x1 = raw[n1].y;
-                        peak = fmaxf(peak, fmaxf(fabsf(x0), fabsf(x1)));
                         a[n1] = make_float2(__fsub_rn(x0, mul_rn(pre_coef, left)) * w_re[n1],
                                             __fsub_rn(x1, mul_rn(pre_coef, x0)) * w_im[n1]);
                     }
@@ -388,16 +415,22 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
                         const float p0 = i0 > 0 ? mul_rn(pre_coef, x[i0 - 1]) : 0.f;
                         const float p1 = i1 > 0 ? mul_rn(pre_coef, x[i1 - 1]) : 0.f;
                         const float x0 = raw[n1].x, x1 = raw[n1].y;
-                        peak = fmaxf(peak, fmaxf(fabsf(x0), fabsf(x1)));
                         a[n1] = make_float2(__fsub_rn(x0, p0) * w_re[n1], __fsub_rn(x1, p1) * w_im[n1]);
                     }
                 }
             }
-            // the raw registers are free again: the next group's samples start moving now and land while
-            // this group's FFT / mel / log run
-            if (g + WAVES < NGR) load_group(g + WAVES, raw);
-            K1_MARK("PHASE P1 radix-16 #1");
+            K1_MARK("PHASE P1 radix-16 #1 + next group's loads");
             dft16(a);
+            // The raw registers are free again: the next group's samples start moving now and land while the rest of this group's
+            // FFT / mel / log run.  The empty statements keep the peak and the first radix-16 in front of the loads: left alone the
+            // compiler sinks everything that reads the samples below the load branch (the peak as far as the loop's latch), which
+            // keeps the old samples alive beside the new ones and costs 56 register copies per group.  They stand behind the
+            // radix-16, not behind the window multiply: its products are contracted into the first butterflies' FMAs, and a
+            // statement between the two would round them on their own.
+            asm volatile("" : "+v"(peak));
+#pragma unroll
+            for (int k1 = 0; k1 < 16; ++k1) asm volatile("" : "+v"(a[k1].x), "+v"(a[k1].y));
+            if (g + WAVES < NGR) load_group(g + WAVES, raw);
             K1_MARK("PHASE P1 twiddle (LDS table) complex multiply");
 #pragma unroll
             for (int k1 = 1; k1 < 16; ++k1) a[k1] = cmul(a[k1], tw_row[k1]);
@@ -558,7 +591,9 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
             run_max = -INFINITY;
             chk = 0.f;
             __syncthreads();   // every wave is through its mel reads before the scratch / dB buffer are written again
+            K1_MARK("SKIP rescaled second P1 pass (a peak outside 2^-50 .. 2^50: never audio)");
             p1_pass(ws1, ws2);
+            K1_MARK("ENDSKIP");
         }
     }
     if (chk != chk) run_max = INFINITY;   // finite powers give a finite or -inf dB: +inf marks the clip
@@ -967,51 +1002,116 @@ __global__ __launch_bounds__(THREADS, GEO ? COUGH_GEO_WG_PER_CU : 3) void featur
         }
         return;
     }
-    if constexpr (STEM != 0) {
-        // the floored dB values move to registers, then the dB buffer becomes the zero-bordered bf16 image
-        float2 dv[(NMEL * NFRAMES / 2 + THREADS - 1) / THREADS];
-#pragma unroll
-        for (int it = 0; it < (NMEL * NFRAMES / 2 + THREADS - 1) / THREADS; ++it) {
-            const int i2 = tid + it * THREADS;
-            dv[it] = i2 < NMEL * NFRAMES / 2 ? reinterpret_cast<const float2*>(melbuf)[i2] : make_float2(0.f, 0.f);
-        }
+    if constexpr (STEM != 0 && PCS) {
+        // mel rows = the PCEN values this thread formed for (band tid / 4, quarter tid % 4 of the frames): pixel by pixel into the
+        // zero-filled images
         __syncthreads();
         constexpr int NIMG = STEM == 2 ? 2 : 1;     // x3: hi and lo images are adjacent
         for (int i = tid; i < NIMG * ST_ROWS * ST_PITCH / 8; i += THREADS) reinterpret_cast<uint4*>(img)[i] = make_uint4(0, 0, 0, 0);
         for (int i = (NIMG * ST_ROWS * ST_PITCH / 8) * 8 + tid; i < NIMG * ST_ROWS * ST_PITCH; i += THREADS) img[i] = 0;
         __syncthreads();
-        if constexpr (PCS) {   // mel rows = the PCEN values this thread formed for (band tid / 4, quarter tid % 4 of the frames)
-            const int m = tid >> 2, t0 = (tid & 3) * 26;
+        const int m = tid >> 2, t0 = (tid & 3) * 26;
 #pragma unroll
-            for (int k = 0; k < 26; ++k)
-                if (t0 + k < NFRAMES) put((m + 3) * ST_PITCH + t0 + k + 3, pcv[k]);
-        } else {
+        for (int k = 0; k < 26; ++k)
+            if (t0 + k < NFRAMES) put((m + 3) * ST_PITCH + t0 + k + 3, pcv[k]);
+    }
+    // The image is built by pixel PAIRS: image column t + 3 is odd for t = 0, so pair p of a row is the columns 2 p + 2, 2 p + 3 =
+    // frames 2 p - 1, 2 p -- pair 0 carries the border column 2 in its first half, pair 51 (columns 104, 105: the last ones a
+    // fragment reads) is all border.  A pair is one v_cvt_pk_bf16_f32 for hi, two subtractions and one for lo, and one 4-byte
+    // store per plane; the rows' left border (columns 0, 1) and what lies behind column 105 are zeroed by the threads at the rows'
+    // ends, the border rows by the first threads: nothing is written twice, so no barrier separates the zeros from the pixels.
+    constexpr int ST_P2 = ST_PITCH / 2, ST_PLANE2 = ST_ROWS * ST_P2, ST_NPAIR = (NFRAMES + 3) / 2;   // dwords per row / plane; 52
+    static_assert(ST_PITCH % 2 == 0 && 2 * ST_NPAIR + 2 <= ST_PITCH && NFRAMES % 2 == 1, "pixel pairs: frame 100 ends pair 50");
+    uint32_t* img2 = reinterpret_cast<uint32_t*>(img);
+    [[maybe_unused]] auto put2 = [&](int d /* dword of the pair in a plane */, float v0, float v1) {
+        using f32x2 = __attribute__((ext_vector_type(2))) float;
+        using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+        const f32x2 v = {v0, v1};
+        const uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+        img2[d] = hi;
+        if constexpr (STEM == 2) {
+            const f32x2 lo = {v0 - __uint_as_float(hi << 16), v1 - __uint_as_float(hi & 0xffff0000u)};
+            img2[ST_PLANE2 + d] = __builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2));
+        }
+    };
+    [[maybe_unused]] auto zero2 = [&](int d) {
+        img2[d] = 0;
+        if constexpr (STEM == 2) img2[ST_PLANE2 + d] = 0;
+    };
+    if constexpr (STEM != 0 && !PCS) {
+        // mel rows: thread = (band, quarter of the row) takes 13 pairs = frames 26 q - 1 .. 26 q + 24.  The floored dB values move
+        // to registers first, then the dB buffer becomes image space.
+        static_assert(NMEL * 4 == THREADS && 4 * 13 == ST_NPAIR && 4 * ST_P2 <= THREADS, "mel rows of the image: 13 pairs per thread");
+        const int m = tid >> 2, q = tid & 3;
+        const float* src = melbuf + m * NFRAMES + 26 * q - 1;
+        float dv[26];
 #pragma unroll
-            for (int it = 0; it < (NMEL * NFRAMES / 2 + THREADS - 1) / THREADS; ++it) {
-                const int e = 2 * (tid + it * THREADS);
-                if (e < NMEL * NFRAMES) {
-                    const int m0 = e / NFRAMES, t0 = e - m0 * NFRAMES;
-                    const int m1 = t0 + 1 < NFRAMES ? m0 : m0 + 1, t1 = t0 + 1 < NFRAMES ? t0 + 1 : 0;
-                    put((m0 + 3) * ST_PITCH + t0 + 3, fminf(fmaxf((dv[it].x + 80.0f) * 0.0125f, 0.f), 1.f));
-                    put((m1 + 3) * ST_PITCH + t1 + 3, fminf(fmaxf((dv[it].y + 80.0f) * 0.0125f, 0.f), 1.f));
+        for (int i = 0; i < 26; ++i) {
+            // frame -1 (q = 0) and frames 101, 102 (q = 3) are border: read a neighbour inside the row instead
+            const bool border = (i == 0 && q == 0) || (i >= 24 && q == 3);
+            dv[i] = src[(i == 0 || i >= 24) && border ? 1 : i];
+        }
+        __syncthreads();
+        if (tid < 3 * ST_P2) zero2(tid);                                         // image rows 0..2
+        else if (tid < 4 * ST_P2) zero2((ST_ROWS - 1) * ST_P2 + tid - 3 * ST_P2);   // image row 93
+        const int row2 = (m + 3) * ST_P2;
+        if (q == 0) zero2(row2);
+        if (q == 3)
+            for (int c = ST_NPAIR + 1; c < ST_P2; ++c) zero2(row2 + c);
+#pragma unroll
+        for (int k = 0; k < 13; ++k) {
+            float v0 = fminf(fmaxf((dv[2 * k] + 80.0f) * 0.0125f, 0.f), 1.f);       // (dB + 80) / 80, as the mel rows above
+            float v1 = fminf(fmaxf((dv[2 * k + 1] + 80.0f) * 0.0125f, 0.f), 1.f);
+            if (k == 0) v0 = q == 0 ? 0.f : v0;
+            if (k == 12) {
+                v0 = q == 3 ? 0.f : v0;
+                v1 = q == 3 ? 0.f : v1;
+            }
+            put2(row2 + 1 + 13 * q + k, v0, v1);
+        }
+    }
+    if constexpr (STEM != 0) {
+        // MFCC and delta rows: thread = (coefficient, sixteenth of the row) takes 4 pairs = frames 8 s - 1 .. 8 s + 6 of both rows
+        // out of ten z-scored values (clamped to the row: the delta's own edge rule, preprocessing.py:353-355)
+        static_assert(16 * 4 >= ST_P2 - 1 && NMFCC * 16 <= THREADS, "MFCC / delta rows of the image: 4 pairs per thread");
+        const int c = tid >> 4, s = tid & 15;
+        if (c < NMFCC) {
+            const float* row = mf + c * NFRAMES;
+            float xv[10];
+#pragma unroll
+            for (int i = 0; i < 10; ++i) {
+                const int t = 8 * s - 2 + i;
+                xv[i] = row[t < 0 ? 0 : t > NFRAMES - 1 ? NFRAMES - 1 : t];
+            }
+            const int r_mfcc = (NMEL + c + 3) * ST_P2, r_delta = (NMEL + NMFCC + c + 3) * ST_P2;
+            if (s == 0) {
+                zero2(r_mfcc);
+                zero2(r_delta);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int p = 4 * s + k, t0 = 2 * p - 1;   // frames t0, t0 + 1 = xv[2 k + 1], xv[2 k + 2]
+                if (p < ST_P2 - 1) {
+                    const bool live0 = t0 >= 0 && t0 < NFRAMES, live1 = t0 + 1 < NFRAMES;
+                    put2(r_mfcc + 1 + p, live0 ? xv[2 * k + 1] : 0.f, live1 ? xv[2 * k + 2] : 0.f);
+                    put2(r_delta + 1 + p, live0 ? (xv[2 * k + 2] - xv[2 * k]) / 2.0f : 0.f,
+                         live1 ? (xv[2 * k + 3] - xv[2 * k + 1]) / 2.0f : 0.f);
                 }
             }
         }
     }
     float* o_mfcc = o + nmel * NF;
     float* o_delta = o_mfcc + nmf;
-    for (int item = tid; item < nmf; item += THREADS) {
-        const int c = item / NF, t = item - c * NF;
-        const float* row = mf + c * NF;
-        const float d = (row[t < NF - 1 ? t + 1 : t] - row[t > 0 ? t - 1 : 0]) / 2.0f;   // :353-355
-        if (wr) {
-            o_mfcc[item] = row[t];
-            o_delta[item] = d;
-        }
-        if (delta_delta == 1) dl[item] = d;
-        if constexpr (STEM != 0) {
-            put((NMEL + c + 3) * ST_PITCH + t + 3, row[t]);
-            put((NMEL + NMFCC + c + 3) * ST_PITCH + t + 3, d);
+    if (wr || delta_delta == 1) {   // workgroup-uniform: the fused pipeline materialises no features
+        for (int item = tid; item < nmf; item += THREADS) {
+            const int c = item / NF, t = item - c * NF;
+            const float* row = mf + c * NF;
+            const float d = (row[t < NF - 1 ? t + 1 : t] - row[t > 0 ? t - 1 : 0]) / 2.0f;   // :353-355
+            if (wr) {
+                o_mfcc[item] = row[t];
+                o_delta[item] = d;
+            }
+            if (delta_delta == 1) dl[item] = d;
         }
     }
     K1_STAMP(6);
