@@ -1,6 +1,6 @@
 // Sequential conv-block classifiers for gfx950 (eval mode): CoughDetector ("standard") and CoughDetectorSmall.
 //
-// Replaces /root/reference/src/model.py:11-40 (ConvBlock), :43-141 (CoughDetector.forward / predict) and
+// Replaces the reference's src/model.py:11-40 (ConvBlock), :43-141 (CoughDetector.forward / predict) and
 // :144-207 (CoughDetectorSmall.forward / predict).  Both networks are a stack of
 //     y = maxpool2?( ReLU( BN( conv(x) ) ) )        conv = 3x3 pad 1, or depthwise 3x3 pad 1 -> pointwise 1x1
 // followed by a global mean and Linear -> ReLU -> Linear.  At create time BatchNorm (running stats) is folded into
@@ -19,6 +19,10 @@
 //                          and the un-pooled conv output never exists (floor mode: the odd last row / column is
 //                          never computed)
 //   head                   cnn_tail_kernel: mean over H x W -> Linear -> ReLU -> Linear -> softmax / argmax
+//
+// Which of these a layer runs, with what band, grid and LDS, is decided in cnn_plan.h alone: cough_cnn_create packs the
+// weight forms layer_forms names, cnn_run calls plan_cnn once and run_plan launches what the plan says through the
+// instantiation tables below.
 #include <cmath>
 #include <utility>
 #include <vector>
@@ -27,6 +31,7 @@
 #include "internal.h"
 #include "nn_common.h"
 #include "conv_gemm.h"
+#include "cnn_plan.h"   // what a forward runs: plan_cnn decides, run_plan (below) launches
 
 namespace cough {
 namespace {
@@ -97,16 +102,7 @@ __global__ __launch_bounds__(256) void cnn_first_kernel(const float* __restrict_
 // ds_read_b32 + two v_alignbyte per row.  GEMM rows are ordered (pool window, dy, dx): the 2x2 max is a max over 4
 // accumulator registers.  Three MFMAs per tile (hi*hi + lo*hi + hi*lo), f32 NHWC output.  r03's f32 VALU kernel
 // (cnn_first_kernel) spent 0.27-0.54 ms per 4096 clips here; it stays for the other dtypes / shapes.
-constexpr int CNN_FIRST_MAXL = 22;   // float2 loads per thread: H * W <= 2 * 256 * 22 = 11 264 (the 110 x 101 image fits)
-struct FirstLds { int nrows, pitch; size_t bytes; };
-inline FirstLds first_lds(int H, int W) {
-    FirstLds l;
-    l.nrows = H + 3;                       // rows -1 .. H + 1 (the row below the last conv row is read with zero weights)
-    l.pitch = (W + 7) & ~1;                // cols -1 .. W + 4, even (dword-aligned pairs)
-    l.bytes = size_t(l.nrows) * l.pitch * 2;
-    return l;
-}
-
+// (CNN_FIRST_MAXL float2 loads per thread, nrows and pitch of the image: cnn_plan.h)
 __global__ __launch_bounds__(256) void cnn_first_x3_kernel(const float* __restrict__ feat, int H, int W, int OH, int OW,
                                                            int nrows, int pitch, const bf16_t* __restrict__ wfrag /* [2][64][8] */,
                                                            const float* __restrict__ bias, int N, float* __restrict__ out) {
@@ -309,7 +305,7 @@ __global__ __launch_bounds__(256) void cnn_conv_kernel(CnnConvArgs<T> a) {
 // the MFMAs, sets its speed); all 9 * CIN / 16 k-steps then run out of LDS.  Weights arrive as MFMA fragments
 // [k-step][n-tile][64 lanes][8] straight from L2 (every wave of every workgroup walks the same 36-74 KB stream).
 // GEMM rows are ordered (pool window, dy, dx) as in cnn_conv_kernel; wave w owns tiles w*MW .. w*MW + MW - 1.
-constexpr int CNN_LDS_UNP = 12;   // 16-byte pieces of the LDS image per thread (image <= 48 KB)
+// (CNN_LDS_UNP 16-byte pieces of the LDS image per thread: cnn_plan.h)
 struct CnnLdsArgs {
     const bf16_t* in;     // NHWC [B][H][W][CIN]
     const bf16_t* wf;     // [9 * CIN / 16][NT][64][8]
@@ -732,44 +728,57 @@ __global__ void cnn_nhwc_to_nchw_kernel(const T* __restrict__ in, float* __restr
     out[idx] = to_f32<T>(in[(b * HW + p) * C + c]);
 }
 
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// ------------------------------------------------------------------------------------------ the instantiation tables
+// The kernels this file instantiates, [row][pool == 2]: the LDS-image kernels by the row of their configuration table in
+// cnn_plan.h (CnnLayerPlan::row), the direct and the LDS-staged GEMM kernels by their 32-channel tiles (nt_row).
+static_assert(CNN_X3_ROWS == 4 && CNN_LDS_ROWS == 3, "one row below per row of the configuration tables");
+using X3Kernel = void (*)(CnnX3Args);
+template <int R, bool POOL>
+constexpr X3Kernel x3_kernel() {
+    constexpr X3Cfg c = CNN_X3_TABLE[R];
+    return cnn_conv_lds_x3_kernel<c.cin, c.nt, c.mw, POOL, c.wm, c.wn, (c.lean ? -c.pieces : c.pieces)>;
+}
+constexpr X3Kernel X3_KERNEL[CNN_X3_ROWS][2] = {{x3_kernel<0, false>(), x3_kernel<0, true>()},
+                                                {x3_kernel<1, false>(), x3_kernel<1, true>()},
+                                                {x3_kernel<2, false>(), x3_kernel<2, true>()},
+                                                {x3_kernel<3, false>(), x3_kernel<3, true>()}};
+using LdsKernel = void (*)(CnnLdsArgs);
+template <int R, bool POOL>
+constexpr LdsKernel lds_kernel() {
+    constexpr LdsCfg c = CNN_LDS_CFG[R];
+    return cnn_conv_lds_kernel<c.cin, c.nt, c.mw, POOL>;
+}
+constexpr LdsKernel LDS_KERNEL[CNN_LDS_ROWS][2] = {{lds_kernel<0, false>(), lds_kernel<0, true>()},
+                                                   {lds_kernel<1, false>(), lds_kernel<1, true>()},
+                                                   {lds_kernel<2, false>(), lds_kernel<2, true>()}};
+constexpr int nt_row(int nt) { return nt == 4 ? 2 : nt - 1; }   // nt 1, 2, 4
+template <typename T>
+constexpr void (*CONV_KERNEL[3][2])(CnnConvArgs<T>) = {{cnn_conv_kernel<T, 1, false>, cnn_conv_kernel<T, 1, true>},
+                                                       {cnn_conv_kernel<T, 2, false>, cnn_conv_kernel<T, 2, true>},
+                                                       {cnn_conv_kernel<T, 4, false>, cnn_conv_kernel<T, 4, true>}};
+constexpr void (*GEMM_KERNEL[2][2])(ConvArgs<bf16_t>) = {{conv_gemm_bf16_kernel<2, false>, conv_gemm_bf16_kernel<2, true>},   // nt 2, 4
+                                                         {conv_gemm_bf16_kernel<4, false>, conv_gemm_bf16_kernel<4, true>}};
 
 }  // namespace
 }  // namespace cough
 
 struct cough_cnn {
     struct Layer {
-        int cin, cout, ks, pool;
-        void* d_w;      // first layer: float [9][N]; others: T [N][ktot]
+        cough::LayerForms forms;   // what the layer owns (cnn_plan.h: layer_forms)
+        void* d_w;                 // the plain rows: first layer float [9][N]; others f32 or bf16 [N][forms.ktot]
         float* d_b;
-        int ktot;       // row pitch of d_w: ks*ks*cin, padded to a multiple of 64 for the LDS-staged bf16 GEMM
-        bool gemm;      // bf16, cin % 32 == 0, cout % 64 == 0: conv_gemm_bf16_kernel
-        cough::bf16_t* d_wfrag;   // bf16 (16->32), (32->64), (64->128) blocks: MFMA fragments for cnn_conv_lds_kernel;
-                                  // bf16x3: (hi, lo) fragments of every block after the first for cnn_conv_lds_x3_kernel
+        cough::bf16_t* d_wfrag;    // the one fragment form `forms` names (frag_bf16, frag_x3 or first_x3), or nullptr
     };
     int dtype;
-    size_t esize;
-    std::vector<Layer> layers;
+    int n_layers;
+    cough::CnnDims dims[cough::PLAN_MAX_LAYERS];
+    Layer layers[cough::PLAN_MAX_LAYERS];
     int feat_c, hidden;
     float *d_w1, *d_b1, *d_w2, *d_b2;
 };
 
 namespace cough {
 namespace {
-
-struct CnnShape { int h, w, c; };
-
-// output shape of every block for an (H, W) input; false if the image vanishes
-bool cnn_shapes(const cough_cnn* m, int H, int W, std::vector<CnnShape>& out) {
-    int h = H, w = W;
-    out.clear();
-    for (const auto& l : m->layers) {
-        if (l.pool == 2) { h /= 2; w /= 2; }
-        if (h < 1 || w < 1) return false;
-        out.push_back({h, w, l.cout});
-    }
-    return true;
-}
 
 template <typename T>
 int cnn_upload(void** dst, const std::vector<T>& v) {
@@ -778,195 +787,116 @@ int cnn_upload(void** dst, const std::vector<T>& v) {
     return COUGH_OK;
 }
 
-// Tile configuration of the split-bf16 LDS-image convolution per input width (cin): NT 32-channel tiles per workgroup,
-// WM x WN waves, MW 32-row tiles per wave, PIECES = LDS capacity of the band's two images in 16-byte units.
-struct X3Cfg { int nt, mw, wm, wn, pieces; };
-#ifndef CNN_X3_CFG32
-// measured (profiles/r04_cnn_x3_experiments.txt): 4-wave workgroups of 2 x 2 waves with bands small enough for TWO per CU
-// (one's staging overlaps the other's MFMA phase) for the 64-channel input and THREE (lean fragment pipeline) for the
-// 32-channel one; the 128-channel input (one clip =
-// 120 GEMM rows, 86 KB of images: one workgroup per CU) as 2 x 4 waves so that all eight waves have rows
-#define CNN_X3_CFG32 2, 5, 2, 2, -3328   /* negative: LEAN fragment pipeline, <= 168 registers, bands <= 52 KB: THREE workgroups per CU */
-#define CNN_X3_CFG64 4, 3, 2, 2, 5056
-#define CNN_X3_CFG128 4, 2, 2, 4, 6144
-#endif
-#define CNN_X3_CFG16 1, 4, 4, 1, 6144
-constexpr X3Cfg X3_C16{CNN_X3_CFG16}, X3_C32{CNN_X3_CFG32}, X3_C64{CNN_X3_CFG64}, X3_C128{CNN_X3_CFG128};
-inline const X3Cfg* x3_cfg(const cough_cnn::Layer& l) {
-    const int nt = l.cout >= 128 ? 4 : l.cout / 32;
-    if (l.cin == 16 && nt == X3_C16.nt) return &X3_C16;
-    if (l.cin == 32 && nt == X3_C32.nt) return &X3_C32;
-    if (l.cin == 64 && nt == X3_C64.nt) return &X3_C64;
-    if (l.cin == 128 && nt == X3_C128.nt) return &X3_C128;
-    return nullptr;
-}
-// output rows per workgroup (0: the layer does not fit, use the f32 kernel): the kernel's tile shape must exist, the
-// band's GEMM rows must fit WM waves x MW tiles and its two bf16 images the configuration's LDS capacity
-inline int x3_band(const cough_cnn::Layer& l, const CnnShape& s, int in_w) {
-    const X3Cfg* c = x3_cfg(l);
-    if (!c) return 0;
-    const int per_out = l.pool == 2 ? 4 : 1;
-    int band = (c->wm * c->mw * 32) / (per_out * s.w);
-    if (band > s.h) band = s.h;
-    while (band >= 1 && size_t((l.pool == 2 ? 2 : 1) * band + 2) * (in_w + 2) * (l.cin / 4) > size_t(c->pieces < 0 ? -c->pieces : c->pieces)) --band;
-    return band;
-}
-template <int CIN, int NT, int MW, int WM, int WN, int PIECES>
-void x3_launch(bool pool, dim3 grid, size_t lds, hipStream_t st, const CnnX3Args& a) {
-    if (pool) hipLaunchKernelGGL((cnn_conv_lds_x3_kernel<CIN, NT, MW, true, WM, WN, PIECES>), grid, dim3(64 * WM * WN), lds, st, a);
-    else hipLaunchKernelGGL((cnn_conv_lds_x3_kernel<CIN, NT, MW, false, WM, WN, PIECES>), grid, dim3(64 * WM * WN), lds, st, a);
-}
-template <int CIN, int NT, int MW, int WM, int WN, int PIECES>
-hipError_t x3_set_lds() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cnn_conv_lds_x3_kernel<CIN, NT, MW, true, WM, WN, PIECES>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (PIECES < 0 ? -PIECES : PIECES) * 16 + 64);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(cnn_conv_lds_x3_kernel<CIN, NT, MW, false, WM, WN, PIECES>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (PIECES < 0 ? -PIECES : PIECES) * 16 + 64);
-    return e;
-}
-
-// single-bf16 LDS-image convolution: band of output rows per workgroup, 4 waves x MW tiles x 32 GEMM rows (x4 rows per
-// output when pooled); 0 if not even one row fits the tiles or the CNN_LDS_UNP * 256 staged pieces
-inline int lds_band(const cough_cnn::Layer& l, const CnnShape& s, int in_w, size_t* lds_bytes) {
-    const int mw = l.cin == 64 ? 2 : 4, per_out = l.pool == 2 ? 4 : 1;
-    int band = (4 * mw * 32) / (per_out * s.w);
-    if (band > s.h) band = s.h;
-    const size_t lds = size_t((l.pool == 2 ? 2 : 1) * band + 2) * (in_w + 2) * l.cin * 2;
-    if (lds_bytes) *lds_bytes = lds;
-    return (band >= 1 && lds <= size_t(CNN_LDS_UNP) * 256 * 16) ? band : 0;
+// MFMA B fragments of the LDS-image kernels, [k-step][n-tile][planes][64 lanes][8]: lane (r, h) of (k-step s, n-tile t)
+// holds W[32t + r][16s + 8h ..+7].  planes = 1: bf16 (cnn_conv_lds_kernel); 2: hi, lo (cnn_conv_lds_x3_kernel)
+std::vector<bf16_t> pack_frags(const std::vector<double>& wd, int N, int K, int planes) {
+    const int ks = K / 16, nt = N / 32;
+    std::vector<bf16_t> wfr(size_t(ks) * nt * planes * 512);
+    for (int st = 0; st < ks; ++st)
+        for (int t = 0; t < nt; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int jj = 0; jj < 8; ++jj) {
+                    const float v = float(wd[size_t(32 * t + (lane & 31)) * K + 16 * st + 8 * (lane >> 5) + jj]);
+                    const size_t base = ((size_t(st) * nt + t) * planes) * 512 + size_t(lane) * 8 + jj;
+                    if (planes == 1) wfr[base] = f2bf_host(v);
+                    else split_bf16_host(v, wfr[base], wfr[base + 512]);
+                }
+    return wfr;
 }
 
 template <typename T>
-int cnn_forward_impl(const cough_cnn* m, const float* d_feat, int n, int H, int W, float* d_logits, float* d_probs,
-                     int* d_preds, char* ws, hipStream_t st, int tap_layer, float* d_tap) {
-    std::vector<CnnShape> shp;
-    cnn_shapes(m, H, W, shp);
-    if (sizeof(T) == 2) {   // refuse an image the single-bf16 kernels cannot take before the first launch
-        int iw = W;
-        for (size_t i = 0; i < m->layers.size(); ++i) {
-            if (i > 0 && m->layers[i].d_wfrag && lds_band(m->layers[i], shp[i], iw, nullptr) < 1) {
-                set_error("cough_cnn_forward: image %dx%d too wide for the LDS-image convolution", i ? shp[i - 1].h : H, iw);
-                return COUGH_EUNSUPPORTED;
+void launch_first(bool pool, long long n_out, hipStream_t st, const float* d_feat, const CnnLayerPlan& s,
+                  const cough_cnn::Layer& l, int N, void* dst) {
+    const auto kernel = pool ? cnn_first_kernel<T, true> : cnn_first_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, d_feat, s.in.h, s.in.w, s.out.h, s.out.w,
+                       n_out, static_cast<const float*>(l.d_w), l.d_b, N, static_cast<T*>(dst));
+}
+
+template <typename T>
+void launch_conv(bool pool, long long M, hipStream_t st, const void* cur, const CnnLayerPlan& s, const cough_cnn::Layer& l,
+                 CnnDims d, void* dst) {
+    CnnConvArgs<T> a{};
+    a.in = static_cast<const T*>(cur); a.H = s.in.h; a.W = s.in.w; a.C = d.cin; a.KS = 3;
+    a.wp = static_cast<const T*>(l.d_w); a.bias = l.d_b;
+    a.out = static_cast<T*>(dst); a.OH = s.out.h; a.OW = s.out.w; a.N = d.cout;
+    a.M = M;
+    const dim3 grid((unsigned)(((M + 31) / 32 + 3) / 4), (unsigned)s.gy);
+    hipLaunchKernelGGL(CONV_KERNEL<T>[nt_row(s.nt)][pool], grid, dim3(256), 0, st, a);
+}
+
+// the layers -> the tapped layer's NCHW copy -> tail (if logits are wanted)
+int run_plan(const cough_cnn* m, const CnnPlan& p, const float* d_feat, int n, float* d_logits, float* d_probs, int* d_preds,
+             char* ws, hipStream_t st, int tap_layer, float* d_tap) {
+    const bool bf16 = m->dtype == COUGH_DTYPE_BF16;
+    char* const ping[2] = {ws, ws + p.buf_bytes(n)};
+    const void* cur = nullptr;
+    for (int i = 0; i < p.n_layers; ++i) {
+        const CnnLayerPlan& s = p.layer[i];
+        const cough_cnn::Layer& l = m->layers[i];
+        const CnnDims d = m->dims[i];
+        const bool pool = d.pool == 2;
+        const long long M = (long long)n * s.gx;
+        void* dst = ping[i & 1];
+        switch (s.kernel) {
+            case CNN_FIRST:
+                if (bf16) launch_first<bf16_t>(pool, M, st, d_feat, s, l, d.cout, dst);
+                else launch_first<float>(pool, M, st, d_feat, s, l, d.cout, dst);
+                break;
+            case CNN_FIRST_X3:
+                hipLaunchKernelGGL(cnn_first_x3_kernel, dim3(n), dim3(256), s.lds, st, d_feat, s.in.h, s.in.w, s.out.h, s.out.w,
+                                   p.first.nrows, p.first.pitch, l.d_wfrag, l.d_b, d.cout, static_cast<float*>(dst));
+                break;
+            case CNN_LDS_BF16: {
+                CnnLdsArgs a{static_cast<const bf16_t*>(cur), l.d_wfrag, l.d_b, static_cast<bf16_t*>(dst), s.in.h, s.in.w,
+                             s.out.h, s.out.w, s.band, s.n_bands};
+                hipLaunchKernelGGL(LDS_KERNEL[s.row][pool], dim3((unsigned)M), dim3(256), s.lds, st, a);
+                break;
             }
-            iw = shp[i].w;
-        }
-    }
-    size_t buf = 0;
-    for (const auto& s : shp) buf = std::max(buf, align256(size_t(n) * s.h * s.w * s.c * m->esize));
-    T* ping[2] = {reinterpret_cast<T*>(ws), reinterpret_cast<T*>(ws + buf)};
-    const T* cur = nullptr;
-    int ch = H, cw = W;
-    bool means_in_dst = false;
-    for (size_t i = 0; i < m->layers.size(); ++i) {
-        const auto& l = m->layers[i];
-        const CnnShape& s = shp[i];
-        T* dst = ping[i & 1];
-        if (i == 0) {
-            const long long n_out = (long long)n * s.h * s.w;
-            const dim3 grid((unsigned)((n_out + 255) / 256));
-            const FirstLds fl = first_lds(ch, cw);
-            if (sizeof(T) == 4 && m->dtype == COUGH_DTYPE_BF16X3 && l.d_wfrag && l.pool == 2 && ch * cw <= 2 * 256 * CNN_FIRST_MAXL &&
-                2 * fl.bytes <= 64 * 1024) {
-                if constexpr (sizeof(T) == 4)
-                    hipLaunchKernelGGL(cnn_first_x3_kernel, dim3(n), dim3(256), 2 * fl.bytes, st, d_feat, ch, cw, s.h, s.w, fl.nrows,
-                                       fl.pitch, l.d_wfrag, l.d_b, l.cout, dst);
-            } else if (l.pool == 2)
-                hipLaunchKernelGGL((cnn_first_kernel<T, true>), grid, dim3(256), 0, st, d_feat, ch, cw, s.h, s.w, n_out,
-                                   static_cast<const float*>(l.d_w), l.d_b, l.cout, dst);
-            else
-                hipLaunchKernelGGL((cnn_first_kernel<T, false>), grid, dim3(256), 0, st, d_feat, ch, cw, s.h, s.w, n_out,
-                                   static_cast<const float*>(l.d_w), l.d_b, l.cout, dst);
-        } else if (l.d_wfrag && sizeof(T) == 2) {
-            if constexpr (sizeof(T) == 2) {
-                size_t lds = 0;
-                const int band = lds_band(l, s, cw, &lds);
-                if (band >= 1) {
-                    const int n_bands = (s.h + band - 1) / band;
-                    CnnLdsArgs a{cur, l.d_wfrag, l.d_b, dst, ch, cw, s.h, s.w, band, n_bands};
-                    const dim3 grid((unsigned)(n * n_bands));
-#define COUGH_LDS_LAUNCH(CIN, NT, MW)                                                                            \
-    do {                                                                                                         \
-        if (l.pool == 2) hipLaunchKernelGGL((cnn_conv_lds_kernel<CIN, NT, MW, true>), grid, dim3(256), lds, st, a);  \
-        else hipLaunchKernelGGL((cnn_conv_lds_kernel<CIN, NT, MW, false>), grid, dim3(256), lds, st, a);             \
-    } while (0)
-                    if (l.cin == 16) COUGH_LDS_LAUNCH(16, 1, 4);
-                    else if (l.cin == 32) COUGH_LDS_LAUNCH(32, 2, 4);
-                    else COUGH_LDS_LAUNCH(64, 4, 2);
-#undef COUGH_LDS_LAUNCH
-                } else {   // not reached: the check ahead of the first launch has refused this image
-                    set_error("cough_cnn_forward: image %dx%d too wide for the LDS-image convolution", ch, cw);
-                    return COUGH_EUNSUPPORTED;
-                }
+            case CNN_LDS_X3: {
+                CnnX3Args a{static_cast<const float*>(cur), l.d_wfrag, l.d_b, static_cast<float*>(dst), s.in.h, s.in.w, s.out.h,
+                            s.out.w, s.band, s.n_bands, d.cout / 32, nullptr};
+                // fused mean: [n][cout] floats in `dst`, and the activation never crosses HBM
+                if (s.fused_mean) a.mean_out = static_cast<float*>(dst);
+                hipLaunchKernelGGL(X3_KERNEL[s.row][pool], dim3((unsigned)M, (unsigned)s.gy),
+                                   dim3(x3_threads(CNN_X3_TABLE[s.row])), s.lds, st, a);
+                break;
             }
-        } else if (l.gemm) {
-            if constexpr (sizeof(T) == 2) {
+            case CNN_GEMM_BF16: {
                 ConvArgs<bf16_t> a{};
-                a.in = cur; a.H = ch; a.W = cw; a.C = l.cin; a.KH = a.KW = 3; a.stride = 1; a.pad = 1;
+                a.in = static_cast<const bf16_t*>(cur); a.H = s.in.h; a.W = s.in.w; a.C = d.cin; a.KH = a.KW = 3; a.stride = 1; a.pad = 1;
                 a.in2 = nullptr; a.H2 = a.W2 = 0; a.C2 = 0; a.stride2 = 1;
                 a.wp = static_cast<const bf16_t*>(l.d_w); a.bias = l.d_b;
-                a.out = dst; a.OH = s.h; a.OW = s.w; a.N = l.cout; a.Ktot = l.ktot;
-                a.M = (long long)n * s.h * s.w * (l.pool == 2 ? 4 : 1);
-                const int nt = l.cout % 128 == 0 ? 4 : 2;
-                const dim3 grid((unsigned)((a.M + CG_BM - 1) / CG_BM), (unsigned)(l.cout / (32 * nt)));
-                if (nt == 4 && l.pool == 2) hipLaunchKernelGGL((conv_gemm_bf16_kernel<4, true>), grid, dim3(256), 0, st, a);
-                else if (nt == 4) hipLaunchKernelGGL((conv_gemm_bf16_kernel<4, false>), grid, dim3(256), 0, st, a);
-                else if (l.pool == 2) hipLaunchKernelGGL((conv_gemm_bf16_kernel<2, true>), grid, dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((conv_gemm_bf16_kernel<2, false>), grid, dim3(256), 0, st, a);
+                a.out = static_cast<bf16_t*>(dst); a.OH = s.out.h; a.OW = s.out.w; a.N = d.cout; a.Ktot = l.forms.ktot;
+                a.M = M;
+                const dim3 grid((unsigned)((M + CG_BM - 1) / CG_BM), (unsigned)s.gy);
+                hipLaunchKernelGGL(GEMM_KERNEL[s.nt == 4][pool], grid, dim3(256), 0, st, a);
+                break;
             }
-        } else if (sizeof(T) == 4 && m->dtype == COUGH_DTYPE_BF16X3 && l.d_wfrag && x3_band(l, s, cw) >= 1) {
-            if constexpr (sizeof(T) == 4) {
-                // split-bf16 LDS-image convolution: band of output rows per workgroup, as many as 4 waves x MW tiles cover
-                // and as two band images of <= 96 KB hold
-                const int band = x3_band(l, s, cw), n_bands = (s.h + band - 1) / band;
-                const size_t lds = (size_t((l.pool == 2 ? 2 : 1) * band + 2) * (cw + 2) * l.cin * 2 + 15) / 16 * 16 * 2;
-                CnnX3Args a{cur, l.d_wfrag, l.d_b, dst, ch, cw, s.h, s.w, band, n_bands, l.cout / 32, nullptr};
-                // last block, whole image in one band, logits wanted, nobody taps the activation: its epilogue forms the
-                // head's channel means ([n][cout] floats in `dst`) and the activation never crosses HBM
-                if (i + 1 == m->layers.size() && n_bands == 1 && d_logits && !(d_tap && tap_layer == int(i))) {
-                    a.mean_out = reinterpret_cast<float*>(dst);
-                    means_in_dst = true;
-                }
-                const int nt = l.cout >= 128 ? 4 : l.cout / 32;
-                const dim3 grid((unsigned)(n * n_bands), (unsigned)(l.cout / (32 * nt)));
-                if (l.cin == 16) x3_launch<16, CNN_X3_CFG16>(l.pool == 2, grid, lds, st, a);
-                else if (l.cin == 32) x3_launch<32, CNN_X3_CFG32>(l.pool == 2, grid, lds, st, a);
-                else if (l.cin == 64) x3_launch<64, CNN_X3_CFG64>(l.pool == 2, grid, lds, st, a);
-                else x3_launch<128, CNN_X3_CFG128>(l.pool == 2, grid, lds, st, a);
-            }
-        } else {
-            CnnConvArgs<T> a{};
-            a.in = cur; a.H = ch; a.W = cw; a.C = l.cin; a.KS = l.ks;
-            a.wp = static_cast<const T*>(l.d_w); a.bias = l.d_b;
-            a.out = dst; a.OH = s.h; a.OW = s.w; a.N = l.cout;
-            a.M = (long long)n * s.h * s.w * (l.pool == 2 ? 4 : 1);
-            const int nt = l.cout >= 128 ? 4 : l.cout / 32;
-            const dim3 grid((unsigned)(((a.M + 31) / 32 + 3) / 4), (unsigned)(l.cout / (32 * nt)));
-#define COUGH_CNN_LAUNCH(NT)                                                                              \
-    do {                                                                                                 \
-        if (l.pool == 2) hipLaunchKernelGGL((cnn_conv_kernel<T, NT, true>), grid, dim3(256), 0, st, a);   \
-        else hipLaunchKernelGGL((cnn_conv_kernel<T, NT, false>), grid, dim3(256), 0, st, a);              \
-    } while (0)
-            if (nt == 1) COUGH_CNN_LAUNCH(1);
-            else if (nt == 2) COUGH_CNN_LAUNCH(2);
-            else COUGH_CNN_LAUNCH(4);
-#undef COUGH_CNN_LAUNCH
+            case CNN_CONV_F32: launch_conv<float>(pool, M, st, cur, s, l, d, dst); break;
+            case CNN_CONV_BF16: launch_conv<bf16_t>(pool, M, st, cur, s, l, d, dst); break;
         }
         COUGH_HIP_CHECK(hipGetLastError());
-        if (d_tap && tap_layer == int(i)) {
-            const long long total = (long long)n * s.c * s.h * s.w;
-            hipLaunchKernelGGL(cnn_nhwc_to_nchw_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dst,
-                               d_tap, s.c, s.h * s.w, total);
+        if (d_tap && tap_layer == i) {
+            const int hw = s.out.h * s.out.w;
+            const long long total = (long long)n * d.cout * hw;
+            const dim3 grid((unsigned)((total + 255) / 256));
+            if (bf16)
+                hipLaunchKernelGGL(cnn_nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, st, static_cast<const bf16_t*>(dst), d_tap,
+                                   d.cout, hw, total);
+            else
+                hipLaunchKernelGGL(cnn_nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(dst), d_tap,
+                                   d.cout, hw, total);
             COUGH_HIP_CHECK(hipGetLastError());
         }
         cur = dst;
-        ch = s.h;
-        cw = s.w;
     }
-    if (d_logits) {
-        // (means_in_dst: `cur` holds the channel means, i.e. a 1 x 1 "image" per clip)
-        hipLaunchKernelGGL(cnn_tail_kernel<T>, dim3(n), dim3(256), 0, st, cur, means_in_dst ? 1 : ch * cw, m->feat_c, m->hidden,
-                           m->d_w1, m->d_b1, m->d_w2, m->d_b2, d_logits, d_probs, d_preds);
+    if (d_logits) {   // (head_hw == 1: `cur` holds the channel means, a 1 x 1 "image" per clip)
+        if (bf16)
+            hipLaunchKernelGGL(cnn_tail_kernel<bf16_t>, dim3(n), dim3(256), 0, st, static_cast<const bf16_t*>(cur), p.head_hw,
+                               m->feat_c, m->hidden, m->d_w1, m->d_b1, m->d_w2, m->d_b2, d_logits, d_probs, d_preds);
+        else
+            hipLaunchKernelGGL(cnn_tail_kernel<float>, dim3(n), dim3(256), 0, st, static_cast<const float*>(cur), p.head_hw,
+                               m->feat_c, m->hidden, m->d_w1, m->d_b1, m->d_w2, m->d_b2, d_logits, d_probs, d_preds);
         COUGH_HIP_CHECK(hipGetLastError());
     }
     return COUGH_OK;
@@ -977,10 +907,10 @@ int cnn_forward_impl(const cough_cnn* m, const float* d_feat, int n, int H, int 
 
 extern "C" void cough_cnn_destroy(cough_cnn* m) {
     if (!m) return;
-    for (auto& l : m->layers) {
-        (void)hipFree(l.d_w);
-        (void)hipFree(l.d_b);
-        (void)hipFree(l.d_wfrag);
+    for (int i = 0; i < m->n_layers; ++i) {
+        (void)hipFree(m->layers[i].d_w);
+        (void)hipFree(m->layers[i].d_b);
+        (void)hipFree(m->layers[i].d_wfrag);
     }
     (void)hipFree(m->d_w1);
     (void)hipFree(m->d_b1);
@@ -995,7 +925,7 @@ extern "C" int cough_cnn_create(cough_cnn** out, const cough_cnn_weights* w, int
                   "cough_cnn_create: NULL argument");
     COUGH_REQUIRE(dtype == COUGH_DTYPE_FP32 || dtype == COUGH_DTYPE_BF16 || dtype == COUGH_DTYPE_BF16X3, COUGH_EINVAL,
                   "cough_cnn_create: unknown dtype %d", dtype);
-    COUGH_REQUIRE(w->n_blocks >= 2 && w->n_blocks <= 16, COUGH_EUNSUPPORTED, "cough_cnn_create: %d blocks (need 2..16)", w->n_blocks);
+    COUGH_REQUIRE(w->n_blocks >= 2 && w->n_blocks <= PLAN_MAX_LAYERS, COUGH_EUNSUPPORTED, "cough_cnn_create: %d blocks (need 2..16)", w->n_blocks);
     COUGH_REQUIRE(w->hidden >= 1 && w->hidden <= 256, COUGH_EUNSUPPORTED, "cough_cnn_create: hidden = %d (need 1..256)", w->hidden);
     // bf16x3 keeps f32 activations: a layer without a split-bf16 instantiation (x3_band) runs the exact-f32 kernel, so only
     // that kernel's 8-channel chunk is required; the single-bf16 mode needs 16
@@ -1023,8 +953,6 @@ extern "C" int cough_cnn_create(cough_cnn** out, const cough_cnn_weights* w, int
 
     cough_cnn* m = new cough_cnn();
     m->dtype = dtype;
-    m->esize = dtype == COUGH_DTYPE_BF16 ? 2 : 4;
-    m->d_w1 = m->d_b1 = m->d_w2 = m->d_b2 = nullptr;
     int err = COUGH_OK;
     for (int i = 0; i < w->n_blocks && !err; ++i) {
         const cough_cnn_block& bk = w->blocks[i];
@@ -1046,9 +974,10 @@ extern "C" int cough_cnn_create(cough_cnn** out, const cough_cnn_weights* w, int
             for (int k = 0; k < K; ++k) wd[size_t(n) * K + k] *= scale;
             bd[n] = (bacc - double(p.bn_mean[n])) * scale + double(p.bn_b[n]);
         }
-        cough_cnn::Layer l{Cc, N, 3, bk.pool, nullptr, nullptr, K, false, nullptr};
-        l.gemm = i > 0 && m->esize == 2 && Cc % 32 == 0 && N % 64 == 0;
-        if (l.gemm) l.ktot = ((K + 63) / 64) * 64;
+        m->dims[i] = {Cc, N, bk.pool};
+        cough_cnn::Layer& l = m->layers[i];
+        const LayerForms f = l.forms = layer_forms(dtype, i, Cc, N, bk.pool);
+        m->n_layers = i + 1;   // cough_cnn_destroy frees what this layer has uploaded when a later upload fails
         std::vector<float> bf(N);
         for (int n = 0; n < N; ++n) bf[n] = float(bd[n]);
         if (i == 0) {
@@ -1056,75 +985,39 @@ extern "C" int cough_cnn_create(cough_cnn** out, const cough_cnn_weights* w, int
             for (int n = 0; n < N; ++n)
                 for (int t = 0; t < 9; ++t) wk[size_t(t) * N + n] = float(wd[size_t(n) * 9 + t]);
             err = cnn_upload(&l.d_w, wk);
-        } else if (m->esize == 4) {
+        } else if (!f.bf16_rows) {
             std::vector<float> wf(wd.size());
             for (size_t k = 0; k < wd.size(); ++k) wf[k] = float(wd[k]);
             err = cnn_upload(&l.d_w, wf);
         } else {
-            std::vector<bf16_t> wb(size_t(N) * l.ktot, 0);
+            std::vector<bf16_t> wb(size_t(N) * f.ktot, 0);
             for (int n = 0; n < N; ++n)
-                for (int k = 0; k < K; ++k) wb[size_t(n) * l.ktot + k] = f2bf_host(float(wd[size_t(n) * K + k]));
+                for (int k = 0; k < K; ++k) wb[size_t(n) * f.ktot + k] = f2bf_host(float(wd[size_t(n) * K + k]));
             err = cnn_upload(&l.d_w, wb);
         }
-        if (!err && i > 0 && m->esize == 2 && ((Cc == 16 && N == 32) || (Cc == 32 && N == 64) || (Cc == 64 && N == 128))) {
-            // fragment order of cnn_conv_lds_kernel: lane (r, h) of (k-step s, n-tile t) holds W[32t + r][16s + 8h ..+7]
-            const int ks = K / 16, nt = N / 32;
-            std::vector<bf16_t> wfr(size_t(ks) * nt * 512);
-            for (int st = 0; st < ks; ++st)
-                for (int t = 0; t < nt; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int jj = 0; jj < 8; ++jj)
-                            wfr[((size_t(st) * nt + t) * 64 + lane) * 8 + jj] =
-                                f2bf_host(float(wd[size_t(32 * t + (lane & 31)) * K + 16 * st + 8 * (lane >> 5) + jj]));
-            err = cnn_upload(reinterpret_cast<void**>(&l.d_wfrag), wfr);
-        }
-        if (!err && i > 0 && dtype == COUGH_DTYPE_BF16X3 && (Cc == 16 || Cc == 32 || Cc == 64 || Cc == 128) &&
-            (N == 32 || N == 64 || N % 128 == 0)) {
-            // fragment order of cnn_conv_lds_x3_kernel: [k-step][n-tile][hi, lo][64 lanes][8], lo = bf16(w - hi)
-            const int ks = K / 16, nt = N / 32;
-            std::vector<bf16_t> wfr(size_t(ks) * nt * 2 * 512);
-            for (int st = 0; st < ks; ++st)
-                for (int t = 0; t < nt; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int jj = 0; jj < 8; ++jj) {
-                            const float v = float(wd[size_t(32 * t + (lane & 31)) * K + 16 * st + 8 * (lane >> 5) + jj]);
-                            const bf16_t hi = f2bf_host(v);
-                            const uint32_t hb = uint32_t(hi) << 16;
-                            float hf;
-                            std::memcpy(&hf, &hb, 4);
-                            const size_t base = ((size_t(st) * nt + t) * 2) * 512 + size_t(lane) * 8 + jj;
-                            wfr[base] = hi;
-                            wfr[base + 512] = f2bf_host(v - hf);
-                        }
-            err = cnn_upload(reinterpret_cast<void**>(&l.d_wfrag), wfr);
-        }
-        if (!err && i == 0 && dtype == COUGH_DTYPE_BF16X3 && bk.pool == 2 && N <= 32) {
+        if (!err && (f.frag_bf16 || f.frag_x3))
+            err = cnn_upload(reinterpret_cast<void**>(&l.d_wfrag), pack_frags(wd, N, K, f.frag_x3 ? 2 : 1));
+        if (!err && f.first_x3) {
             // B fragments of cnn_first_x3_kernel: lane (n, h), element jj <-> k = 8h + jj = 4 kh + kw' (kw' = 3 and kh = 3: zero)
             std::vector<bf16_t> wfr(2 * 512, 0);
             for (int lane = 0; lane < 64; ++lane)
                 for (int jj = 0; jj < 8; ++jj) {
                     const int n = lane & 31, k = 8 * (lane >> 5) + jj, kh = k >> 2, kw = k & 3;
                     if (n >= N || kh >= 3 || kw >= 3) continue;
-                    const float v = float(wd[size_t(n) * 9 + kh * 3 + kw]);
-                    const bf16_t hi = f2bf_host(v);
-                    const uint32_t hb = uint32_t(hi) << 16;
-                    float hf;
-                    std::memcpy(&hf, &hb, 4);
-                    wfr[size_t(lane) * 8 + jj] = hi;
-                    wfr[512 + size_t(lane) * 8 + jj] = f2bf_host(v - hf);
+                    split_bf16_host(float(wd[size_t(n) * 9 + kh * 3 + kw]), wfr[size_t(lane) * 8 + jj], wfr[512 + size_t(lane) * 8 + jj]);
                 }
             err = cnn_upload(reinterpret_cast<void**>(&l.d_wfrag), wfr);
         }
         if (!err) err = cnn_upload(reinterpret_cast<void**>(&l.d_b), bf);
-        m->layers.push_back(l);
     }
     m->feat_c = w->blocks[w->n_blocks - 1].cout;
     m->hidden = w->hidden;
     if (!err && dtype == COUGH_DTYPE_BF16X3) {   // the two LDS images of a band can exceed 64 KB
-        hipError_t e = x3_set_lds<16, CNN_X3_CFG16>();
-        if (e == hipSuccess) e = x3_set_lds<32, CNN_X3_CFG32>();
-        if (e == hipSuccess) e = x3_set_lds<64, CNN_X3_CFG64>();
-        if (e == hipSuccess) e = x3_set_lds<128, CNN_X3_CFG128>();
+        hipError_t e = hipSuccess;
+        for (int r = 0; r < CNN_X3_ROWS && e == hipSuccess; ++r)
+            for (int pool = 0; pool < 2 && e == hipSuccess; ++pool)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(X3_KERNEL[r][pool]),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, x3_max_lds(CNN_X3_TABLE[r]));
         if (e != hipSuccess) {
             set_error("cough_cnn_create: %s", hipGetErrorString(e));
             err = COUGH_EHIP;
@@ -1148,32 +1041,30 @@ extern "C" int cough_cnn_create(cough_cnn** out, const cough_cnn_weights* w, int
 }
 
 extern "C" size_t cough_cnn_workspace_bytes(const cough_cnn* m, int n_clips, int height, int width) {
-    using namespace cough;
-    std::vector<CnnShape> shp;
-    if (!m || n_clips < 0 || height < 1 || width < 1 || !cnn_shapes(m, height, width, shp)) return 0;
-    size_t buf = 0;
-    for (const auto& s : shp) buf = std::max(buf, align256(size_t(n_clips) * s.h * s.w * s.c * m->esize));
-    return 2 * buf;
+    if (!m || n_clips < 0 || height < 1 || width < 1) return 0;
+    const cough::CnnPlan p = cough::plan_cnn(m->dtype, m->dims, m->n_layers, height, width, true, -1);
+    return p.ok ? 2 * p.buf_bytes(n_clips) : 0;
 }
 
 namespace {
+// validate, plan once, refuse or carve from the plan, run it
 int cnn_run(const cough_cnn* m, const float* d_feat, int n_clips, int height, int width, float* d_logits, float* d_probs,
             int* d_preds, void* d_workspace, size_t workspace_bytes, void* stream, int tap_layer, float* d_tap) {
     using namespace cough;
     COUGH_REQUIRE(m && d_feat && d_workspace, COUGH_EINVAL, "cough_cnn_forward: NULL argument");
     COUGH_REQUIRE(n_clips >= 0 && height >= 1 && width >= 1, COUGH_EINVAL, "cough_cnn_forward: bad shape");
-    std::vector<CnnShape> shp;
-    COUGH_REQUIRE(cnn_shapes(m, height, width, shp), COUGH_EINVAL, "cough_cnn_forward: input %dx%d too small for the network",
-                  height, width);
+    const CnnPlan p = plan_cnn(m->dtype, m->dims, m->n_layers, height, width, d_logits != nullptr, d_tap ? tap_layer : -1);
+    COUGH_REQUIRE(p.ok, COUGH_EINVAL, "cough_cnn_forward: input %dx%d too small for the network", height, width);
     COUGH_REQUIRE((reinterpret_cast<size_t>(d_workspace) & 255) == 0, COUGH_EINVAL, "cough_cnn_forward: workspace must be 256-byte aligned");
-    COUGH_REQUIRE(workspace_bytes >= cough_cnn_workspace_bytes(m, n_clips, height, width), COUGH_EWORKSPACE,
-                  "cough_cnn_forward: workspace too small");
+    COUGH_REQUIRE(workspace_bytes >= 2 * p.buf_bytes(n_clips), COUGH_EWORKSPACE, "cough_cnn_forward: workspace too small");
     if (n_clips == 0) return COUGH_OK;
+    if (p.unsupported_layer >= 0) {   // refused before the first launch
+        const HW in = p.layer[p.unsupported_layer].in;
+        set_error("cough_cnn_forward: image %dx%d too wide for the LDS-image convolution", in.h, in.w);
+        return COUGH_EUNSUPPORTED;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(d_workspace);
-    const int e = m->esize == 4
-        ? cnn_forward_impl<float>(m, d_feat, n_clips, height, width, d_logits, d_probs, d_preds, ws, st, tap_layer, d_tap)
-        : cnn_forward_impl<bf16_t>(m, d_feat, n_clips, height, width, d_logits, d_probs, d_preds, ws, st, tap_layer, d_tap);
+    const int e = run_plan(m, p, d_feat, n_clips, d_logits, d_probs, d_preds, static_cast<char*>(d_workspace), st, tap_layer, d_tap);
     if (e == COUGH_OK && d_logits) {   // a NaN pixel -> NaN logits (nn_common.h: torch's ReLU / max-pool propagate it)
         hipLaunchKernelGGL(nan_rule_kernel, dim3(n_clips), dim3(256), 0, st, d_feat, (long long)height * width, nullptr, d_logits,
                            d_probs, d_preds);
@@ -1194,5 +1085,6 @@ extern "C" int cough_cnn_conv_output(const cough_cnn* m, const float* d_feat, in
                                      float* d_out, void* d_workspace, size_t workspace_bytes, void* stream) {
     COUGH_REQUIRE(m && d_out, COUGH_EINVAL, "cough_cnn_conv_output: NULL argument");
     return cnn_run(m, d_feat, n_clips, height, width, nullptr, nullptr, nullptr, d_workspace, workspace_bytes, stream,
-                   int(m->layers.size()) - 1, d_out);
+                   m->n_layers - 1, d_out);
 }
+

@@ -25,6 +25,14 @@ inline bf16_t f2bf_host(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return bf16_t(u >> 16);
 }
+// the split-bf16 operand pair of a weight: hi = bf16(v), lo = bf16(v - hi)
+inline void split_bf16_host(float v, bf16_t& hi, bf16_t& lo) {
+    hi = f2bf_host(v);
+    const uint32_t hb = uint32_t(hi) << 16;
+    float hf;
+    std::memcpy(&hf, &hb, 4);
+    lo = f2bf_host(v - hf);
+}
 
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }

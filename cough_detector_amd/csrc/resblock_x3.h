@@ -669,13 +669,8 @@ inline void pack_x3_fragments(std::vector<bf16_t>& wf, const std::vector<float>&
             for (int lane = 0; lane < 64; ++lane)
                 for (int jj = 0; jj < 8; ++jj) {
                     const float v = w[size_t(32 * t + (lane & 31)) * K + 16 * sl + 8 * (lane >> 5) + jj];
-                    const bf16_t hi = f2bf_host(v);
-                    uint32_t hb = uint32_t(hi) << 16;
-                    float hf;
-                    std::memcpy(&hf, &hb, 4);
                     const size_t base = ((size_t(s) * nt + t) * 2) * 512 + size_t(lane) * 8 + jj;
-                    wf[base] = hi;
-                    wf[base + 512] = f2bf_host(v - hf);
+                    split_bf16_host(v, wf[base], wf[base + 512]);
                 }
     }
 }
@@ -693,13 +688,8 @@ inline void pack_x3_t16_fragments(std::vector<bf16_t>& wt, const std::vector<flo
             for (int lane = 0; lane < 64; ++lane)
                 for (int jj = 0; jj < 8; ++jj) {
                     const float v = w[size_t(16 * t + (lane & 15)) * K + 32 * ql + 8 * (lane >> 4) + jj];
-                    const bf16_t hi = f2bf_host(v);
-                    const uint32_t hb = uint32_t(hi) << 16;
-                    float hf;
-                    std::memcpy(&hf, &hb, 4);
                     const size_t base = ((size_t(q) * nt + t) * 2) * 512 + size_t(lane) * 8 + jj;
-                    wt[base] = hi;
-                    wt[base + 512] = f2bf_host(v - hf);
+                    split_bf16_host(v, wt[base], wt[base + 512]);
                 }
     }
 }

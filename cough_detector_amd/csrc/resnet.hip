@@ -1184,13 +1184,8 @@ extern "C" int cough_resnet_create(cough_resnet** out, const cough_resnet_weight
                             const int kh = 2 * st + hh;
                             if (kh >= 7) continue;
                             const float v = f.w[size_t(n) * 49 + kh * 7 + jj];
-                            const bf16_t hi = f2bf_host(v);
-                            const uint32_t hb = uint32_t(hi) << 16;
-                            float hf;
-                            std::memcpy(&hf, &hb, 4);
                             const size_t idx = ((size_t(st) * 2 + hh) * 32 + n) * 8 + jj;
-                            wf[idx] = hi;
-                            wf[2048 + idx] = f2bf_host(v - hf);
+                            split_bf16_host(v, wf[idx], wf[2048 + idx]);
                         }
             err = upload(reinterpret_cast<void**>(&m->d_stem_wfrag), wf);
         }

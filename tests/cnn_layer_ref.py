@@ -1,5 +1,5 @@
 """Float64 restatement of the conv-stack classifiers layer by layer, a Python restatement of the kernel dispatch of
-``csrc/cnn.hip`` (``plan``), the per-pixel error budget of each kernel family (``layer_bound``), a CPU emulation of the
+``csrc/cnn_plan.h`` (``plan``), the per-pixel error budget of each kernel family (``layer_bound``), a CPU emulation of the
 three operand schemes with plantable defects (``emulate_layer``) and the shape matrix the host and GPU tests share.
 
 Blocks
@@ -11,11 +11,13 @@ float64 and returns every block's output; ``tests/test_cnn_layer_ref_host.py`` p
 
 Dispatch (``plan``)
 -------------------
-Transcribed from ``cnn_shapes``, ``first_lds``, ``x3_cfg``, ``x3_band`` and the launch conditions of
-``cnn_forward_impl``.  The constants below (``X3_CFG``, ``FIRST_MAXL``, ``LDS_UNP``) mirror ``CNN_X3_CFG*``,
-``CNN_FIRST_MAXL`` and ``CNN_LDS_UNP``; ``test_plan_constants_are_the_ones_in_cnn_hip`` reads them, and the launch rules, out
-of the source, so a retune fails there; the GPU tests then assert that every shape of the matrix lands on the path it was
-chosen for according to ``plan``, instead of the coverage moving silently.
+A restatement, written independently, of ``plan_cnn`` in ``csrc/cnn_plan.h``, the one place the library decides what a
+forward launches (``csrc/cnn.hip`` executes that plan).  The constants below (``X3_CFG``, ``FIRST_MAXL``, ``LDS_UNP``)
+mirror ``CNN_X3_TABLE``, ``CNN_FIRST_MAXL`` and ``CNN_LDS_UNP``.  ``tests/test_cnn_layer_ref_host.py`` compiles the header
+into ``tests/cnn_plan_dump.cpp`` and holds its constants, its capability record and its plans equal to this module's,
+field by field (``plan_line``) over the matrix and a sweep of shapes, so a retune fails there; the GPU tests then assert
+that every shape of the matrix lands on the path it was chosen for according to ``plan`` and the hand-written ``EXPECT``
+rows, instead of the coverage moving silently.
 
 Error budget (``layer_bound``)
 ------------------------------
@@ -161,7 +163,8 @@ FIRST_MAXL = 22
 LDS_UNP = 12
 DTYPES = ("fp32", "bf16x3", "bf16_approx")
 
-Step = namedtuple("Step", "kernel cin cout pool nt band_rows n_bands fused_mean odd_hw in_hw out_hw")
+Step = namedtuple("Step", "kernel cin cout pool nt band_rows n_bands fused_mean odd_hw in_hw out_hw lds")
+MODES = ("forward", "conv_output")
 
 
 def shapes(dims, H, W):
@@ -187,10 +190,12 @@ def x3_band(cin, cout, pool, out_h, out_w, in_w) -> int:
     return band
 
 
-def plan(blocks_or_dims, dtype: str, H: int, W: int) -> Optional[List[Step]]:
-    """The kernel every layer of ``cough_cnn_forward`` launches for an (H, W) image, or None if the image vanishes.
-    kernel: first | first_x3 | conv_f32 | lds_x3 | lds_bf16 | gemm_bf16 | conv_bf16 | unsupported (the launch is refused)."""
-    assert dtype in DTYPES
+def plan(blocks_or_dims, dtype: str, H: int, W: int, mode: str = "forward") -> Optional[List[Step]]:
+    """The kernel every layer of ``cough_cnn_forward`` (``mode`` "conv_output": of ``cough_cnn_conv_output``, which taps the
+    last layer and wants no logits) launches for an (H, W) image, or None if the image vanishes.
+    kernel: first | first_x3 | conv_f32 | lds_x3 | lds_bf16 | gemm_bf16 | conv_bf16 | unsupported (the launch is refused).
+    lds: the dynamic LDS bytes of the launch."""
+    assert dtype in DTYPES and mode in MODES
     dims = blocks_or_dims if isinstance(blocks_or_dims[0][0], int) else layer_dims(blocks_or_dims)
     shp = shapes(dims, H, W)
     if shp is None:
@@ -198,11 +203,11 @@ def plan(blocks_or_dims, dtype: str, H: int, W: int) -> Optional[List[Step]]:
     out, ch, cw = [], H, W
     for i, ((cin, cout, pool), (sh, sw, _)) in enumerate(zip(dims, shp)):
         nt = 4 if cout >= 128 else cout // 32
-        kernel, band, n_bands, fused, odd = None, 0, 0, False, False
+        kernel, band, n_bands, fused, odd, lds = None, 0, 0, False, False, 0
         if i == 0:
             lds2 = 2 * (ch + 3) * ((cw + 7) & ~1) * 2
             if dtype == "bf16x3" and cout <= 32 and pool == 2 and ch * cw <= 2 * 256 * FIRST_MAXL and lds2 <= 64 * 1024:
-                kernel, odd = "first_x3", (ch * cw) % 2 == 1
+                kernel, odd, lds = "first_x3", (ch * cw) % 2 == 1, lds2
             else:
                 kernel = "first"
         elif dtype == "bf16_approx" and (cin, cout) in ((16, 32), (32, 64), (64, 128)):
@@ -212,7 +217,7 @@ def plan(blocks_or_dims, dtype: str, H: int, W: int) -> Optional[List[Step]]:
             if band >= 1 and lds <= LDS_UNP * 256 * 16:
                 kernel, n_bands = "lds_bf16", -(-sh // band)
             else:
-                kernel, band = "unsupported", 0
+                kernel, band, lds = "unsupported", 0, 0
         elif dtype == "bf16_approx":
             kernel = "gemm_bf16" if cin % 32 == 0 and cout % 64 == 0 else "conv_bf16"
         else:
@@ -220,12 +225,45 @@ def plan(blocks_or_dims, dtype: str, H: int, W: int) -> Optional[List[Step]]:
             band = x3_band(cin, cout, pool, sh, sw, cw) if has_frag else 0
             if band >= 1:
                 kernel, n_bands = "lds_x3", -(-sh // band)
-                fused = i + 1 == len(dims) and n_bands == 1
+                # two images (hi, lo), each rounded up to 16 bytes
+                lds = -(-(((2 if pool == 2 else 1) * band + 2) * (cw + 2) * cin * 2) // 16) * 16 * 2
+                fused = i + 1 == len(dims) and n_bands == 1 and mode == "forward"
             else:
                 kernel = "conv_f32"
-        out.append(Step(kernel, cin, cout, pool, nt, band, n_bands, fused, odd, (ch, cw), (sh, sw)))
+        out.append(Step(kernel, cin, cout, pool, nt, band, n_bands, fused, odd, (ch, cw), (sh, sw), lds))
         ch, cw = sh, sw
     return out
+
+
+def plan_line(dims, dtype: str, H: int, W: int, mode: str = "forward") -> str:
+    """The line tests/cnn_plan_dump.cpp prints for a query, built from ``plan`` and the launch arithmetic of csrc/cnn.hip:
+    the grid (x per clip: workgroups of the one-workgroup-per-clip / per-band kernels, threads of the first block, GEMM
+    rows of the rest; y: channel groups), one ping-pong buffer for 1 and for 3 clips, the tail kernel's HW."""
+    steps = plan(dims, dtype, H, W, mode)
+    if steps is None:
+        return "none"
+    parts = []
+    for i, s in enumerate(steps):
+        oh, ow = s.out_hw
+        if s.kernel == "first":
+            gx, gy = oh * ow, 1
+        elif s.kernel == "first_x3":
+            gx, gy = 1, 1
+        elif s.kernel in ("lds_bf16", "unsupported"):
+            gx, gy = s.n_bands, 1
+        elif s.kernel == "lds_x3":
+            gx, gy = s.n_bands, s.cout // (32 * s.nt)
+        else:
+            gx, gy = oh * ow * (4 if s.pool == 2 else 1), s.cout // (32 * s.nt)
+        parts.append(f"{s.kernel} {s.nt if i else 0} {s.band_rows} {s.n_bands} lds={s.lds} grid={gx},{gy} {int(s.fused_mean)} "
+                     f"{int(s.odd_hw)} {s.in_hw[0]}x{s.in_hw[1]}->{oh}x{ow}")
+    act = max(s.out_hw[0] * s.out_hw[1] * s.cout for s in steps) * (2 if dtype == "bf16_approx" else 4)
+    hw = 1 if steps[-1].fused_mean else steps[-1].out_hw[0] * steps[-1].out_hw[1]
+    parts.append(f"buf={-(-act // 256) * 256},{-(-3 * act // 256) * 256} head_hw={hw}")
+    bad = [i for i, s in enumerate(steps) if s.kernel == "unsupported"]
+    if bad:
+        parts.append(f"unsupported={bad[0]} {steps[bad[0]].in_hw[0]}x{steps[bad[0]].in_hw[1]}")
+    return " | ".join(parts)
 
 
 SCHEME = {"first": "f32", "conv_f32": "f32", "first_x3": "bf16x3", "lds_x3": "bf16x3", "lds_bf16": "bf16", "gemm_bf16": "bf16",
@@ -388,6 +426,34 @@ CASES = [
     Case("first24_31x37", "first24", 31, 37, 3, False), Case("first64_20x28", "first64", 20, 28, 3, False),
     Case("approx_48x56", "approx", 48, 56, 3, True),
 ]
+
+
+# hand-checked (kernel, band_rows, n_bands, fused mean) of the cases that exist for one path of the dispatch
+T_, F_ = True, False
+EXPECT = {
+    ("std_90x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 8, F_), ("lds_x3", 4, 3, F_), ("lds_x3", 5, 1, T_)],
+    ("small_90x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 5, 5, F_), ("lds_x3", 6, 2, F_), ("lds_x3", 11, 1, T_)],
+    ("std_110x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 9, F_), ("lds_x3", 4, 4, F_), ("lds_x3", 5, 2, F_)],
+    ("std_111x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 9, F_), ("lds_x3", 4, 4, F_), ("lds_x3", 5, 2, F_)],
+    ("std_16x16", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 4, 1, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, T_)],
+    ("small_8x8", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, F_), ("lds_x3", 1, 1, T_)],
+    ("std_128x128", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 2, 16, F_), ("lds_x3", 3, 6, F_), ("lds_x3", 4, 2, F_)],
+    ("small_128x128", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 4, 8, F_), ("lds_x3", 5, 4, F_), ("lds_x3", 12, 2, F_)],
+    ("std_40x300", "bf16x3"): [("first", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 1, 5, F_), ("lds_x3", 1, 2, F_)],
+    ("std_64x400", "bf16x3"): [("first", 0, 0, F_)] + [("conv_f32", 0, 0, F_)] * 3,
+    ("small_64x400", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 1, 16, F_), ("lds_x3", 1, 8, F_), ("lds_x3", 3, 3, F_)],
+    ("std_300x40", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 8, 10, F_), ("lds_x3", 9, 5, F_), ("lds_x3", 12, 2, F_)],
+    ("small_9x200", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, F_), ("lds_x3", 1, 1, T_)],
+    ("nopool_26x22", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 13, 1, F_), ("lds_x3", 13, 1, F_), ("lds_x3", 13, 1, F_),
+                                 ("lds_x3", 11, 2, F_)],
+    ("mixed_72x88", "bf16x3"): [("first_x3", 0, 0, F_), ("conv_f32", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 7, 2, F_),
+                                ("conv_f32", 0, 0, F_), ("lds_x3", 4, 1, F_), ("lds_x3", 4, 1, T_)],
+    ("first24_31x37", "bf16x3"): [("first_x3", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 7, 1, T_)],
+    ("first64_20x28", "bf16x3"): [("first", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 5, 1, T_)],
+    ("std_90x101", "bf16_approx"): [("first", 0, 0, F_), ("lds_bf16", 5, 5, F_), ("lds_bf16", 5, 3, F_), ("gemm_bf16", 0, 0, F_)],
+    ("approx_48x56", "bf16_approx"): [("first", 0, 0, F_), ("lds_bf16", 9, 2, F_), ("conv_bf16", 0, 0, F_), ("lds_bf16", 6, 1, F_),
+                                      ("lds_bf16", 6, 1, F_), ("gemm_bf16", 0, 0, F_)],
+}
 
 
 def case_dtypes(case: Case):

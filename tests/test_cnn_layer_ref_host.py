@@ -1,12 +1,20 @@
 """Host tests of tests/cnn_layer_ref.py: the float64 block list against oracle/cnn.py, the dispatch restatement against a
-hand-checked table, the derived per-pixel bounds against a CPU emulation of each operand scheme over the whole GPU matrix
-(within HALF of the bound), and planted defects that the per-pixel check flags while the logits stay within LOGIT_TOL."""
+hand-checked table and against the plans csrc/cnn_plan.h itself computes (tests/cnn_plan_dump.cpp), the derived per-pixel
+bounds against a CPU emulation of each operand scheme over the whole GPU matrix (within HALF of the bound), and planted
+defects that the per-pixel check flags while the logits stay within LOGIT_TOL."""
+import atexit
 import functools
+import os
+import re
+import shutil
+import subprocess
+import tempfile
 
 import pytest
 import torch
 
 import cnn_layer_ref as R
+from cough_detector_amd import build as cbuild
 from oracle import cnn as ocnn
 from parity import LOGIT_TOL
 
@@ -67,40 +75,121 @@ def test_plan_table():
     assert R.plan(R.STD_DIMS, "bf16_approx", 64, 400)[1].kernel == "unsupported"
 
 
-def test_plan_constants_are_the_ones_in_cnn_hip():
-    """plan() restates the dispatch with constants of its own; this ties them to the source the library is built from, so a
-    retune of CNN_X3_CFG*, CNN_FIRST_MAXL or CNN_LDS_UNP (or of the launch rules quoted below) fails here until plan(), the
-    hand-checked tables and the matrix have been revisited."""
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cough_detector_amd", "csrc",
-                            "cnn.hip")).read()
-    for cin, want in R.X3_CFG.items():
-        defs = re.findall(rf"#define CNN_X3_CFG{cin}\s+(-?\d+),\s*(-?\d+),\s*(-?\d+),\s*(-?\d+),\s*(-?\d+)", src)
-        assert len(defs) == 1, (cin, defs)                       # one definition: no second default to drift to
-        nt, mw, wm, wn, pieces = (int(v) for v in defs[0])
-        assert (nt, mw, wm, wn, abs(pieces)) == want, (cin, defs[0])
-    assert int(re.search(r"constexpr int CNN_FIRST_MAXL = (\d+);", src).group(1)) == R.FIRST_MAXL
-    assert int(re.search(r"constexpr int CNN_LDS_UNP = (\d+);", src).group(1)) == R.LDS_UNP
-    # the launch rules plan() transcribes, as they stand in the source
-    for rule in ("l.nrows = H + 3;", "l.pitch = (W + 7) & ~1;",
-                 "ch * cw <= 2 * 256 * CNN_FIRST_MAXL", "2 * fl.bytes <= 64 * 1024", "bk.pool == 2 && N <= 32",
-                 "const int mw = l.cin == 64 ? 2 : 4, per_out = l.pool == 2 ? 4 : 1;",
-                 "int band = (4 * mw * 32) / (per_out * s.w);",
-                 "lds <= size_t(CNN_LDS_UNP) * 256 * 16",
-                 "(Cc == 16 && N == 32) || (Cc == 32 && N == 64) || (Cc == 64 && N == 128)",
-                 "l.gemm = i > 0 && m->esize == 2 && Cc % 32 == 0 && N % 64 == 0;",
-                 "(Cc == 16 || Cc == 32 || Cc == 64 || Cc == 128) &&",
-                 "(N == 32 || N == 64 || N % 128 == 0)",
-                 "const int nt = l.cout >= 128 ? 4 : l.cout / 32;",
-                 "int band = (c->wm * c->mw * 32) / (per_out * s.w);",
-                 "* (in_w + 2) * (l.cin / 4) > size_t(c->pieces < 0 ? -c->pieces : c->pieces)) --band;",
-                 "i + 1 == m->layers.size() && n_bands == 1 && d_logits"):
-        assert rule in src, rule
-    # no build of the library overrides the tile configurations from the command line
-    build_py = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cough_detector_amd",
-                                 "build.py")).read()
-    assert "CNN_X3_CFG" not in build_py
+# ------------------------------------------------------------------------------------------ the C++ plan against plan()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "cough_detector_amd", "csrc")
+ALL_DIMS = {"standard": R.STD_DIMS, "small": R.SMALL_DIMS, **{k: [(a, b, p) for a, b, p, _ in v] for k, v in R.GENERIC.items()}}
+
+
+@functools.lru_cache(maxsize=None)
+def _dump_exe():
+    """tests/cnn_plan_dump.cpp built once per session by a host compiler: csrc/cnn_plan.h includes no HIP header."""
+    out = tempfile.mkdtemp(prefix="cnn_plan_dump_")
+    atexit.register(shutil.rmtree, out, ignore_errors=True)
+    exe = os.path.join(out, "cnn_plan_dump")
+    cxx = [shutil.which("c++")] if shutil.which("c++") else [cbuild._hipcc(), "-x", "c++"]
+    subprocess.run([*cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cnn_plan_dump.cpp"),
+                    "-o", exe], check=True)
+    return exe
+
+
+def _dump(queries):
+    """(constants of the header, one line per query).  A query is a ready "forms ..." string or (dims, dtype, H, W, mode)."""
+    text = "".join(q + "\n" if isinstance(q, str) else
+                   f"{q[1]} {len(q[0])} {' '.join(f'{a} {b} {p}' for a, b, p in q[0])} {q[2]} {q[3]} {q[4]}\n" for q in queries)
+    out = subprocess.run([_dump_exe()], input=text, capture_output=True, text=True, check=True).stdout
+    head, _, body = out.partition("---\n")
+    consts = {ln.split()[0]: tuple(int(v) for v in ln.split()[1:]) for ln in head.splitlines()}
+    lines = body.splitlines()
+    assert len(lines) == len(queries)
+    return consts, lines
+
+
+def _row(line):
+    """(kernel, band_rows, n_bands, fused mean) per layer of a dumped line: the columns of R.EXPECT."""
+    layers = [f.split() for f in line.split(" | ") if "->" in f]
+    return [(f[0], int(f[2]), int(f[3]), f[6] == "1") for f in layers]
+
+
+def test_cxx_plan_gives_the_hand_written_row_of_every_case():
+    queries = [(R.case_dims(c), dt, c.H, c.W, "forward") for c in R.CASES for dt in R.case_dtypes(c)]
+    names = [(c.name, dt) for c in R.CASES for dt in R.case_dtypes(c)]
+    _, lines = _dump(queries)
+    assert set(R.EXPECT) <= set(names)
+    for name, q, line in zip(names, queries, lines):
+        if name in R.EXPECT:
+            assert _row(line) == R.EXPECT[name], (name, line)
+        assert line == R.plan_line(*q), (name, line, R.plan_line(*q))
+
+
+def test_cxx_plan_is_plan_over_the_sweep():
+    """plan_cnn (csrc/cnn_plan.h, what cnn.hip executes) against plan(), field by field: each layer's kernel, tiles, band,
+    bands per clip, dynamic LDS, grid, fused mean, odd pixel count and shapes, the ping-pong buffer, the head's HW and the
+    single-bf16 refusal.  Both shipped nets and every generic net of the matrix, the three dtypes, both entry points, over
+    H, W = 1..40 densely, the values around 90 / 101 / 110 / 128 and the wide and tall 300 and 400."""
+    grid = list(range(1, 41)) + [47, 64, 72, 88, 89, 90, 91, 99, 100, 101, 102, 109, 110, 111, 112, 127, 128, 129, 300, 400]
+    queries = [(dims, dt, h, w, mode) for dims in ALL_DIMS.values() for dt in R.DTYPES for mode in R.MODES for h in grid for w in grid]
+    assert len(queries) == 7 * 3 * 2 * 60 * 60
+    # low, wide strips through a two-block net: under 11 264 pixels, the two planes of the first block's image reach 64 KB
+    strip = [(1, 16, 2), (16, 32, 2)]
+    queries += [(strip, dt, h, w, mode) for dt in R.DTYPES for mode in R.MODES for h in (4, 8) for w in (1400, 2334, 2336)]
+    _, lines = _dump(queries)
+    bad = [(q, ln) for q, ln in zip(queries, lines) if ln != R.plan_line(*q)]
+    assert not bad, (len(bad), bad[0], R.plan_line(*bad[0][0]))
+    # the sweep reaches every kernel, the refusal, the vanishing image and both answers of the fused mean in each mode
+    seen = {f.split()[0] for ln in lines for f in ln.split(" | ")[:-1]} | {ln for ln in lines if ln == "none"}
+    assert {"first", "first_x3", "conv_f32", "lds_x3", "lds_bf16", "gemm_bf16", "conv_bf16", "unsupported", "none"} <= seen
+    at = {(tuple(q[0]), *q[1:]): ln for q, ln in zip(queries, lines)}
+    std = tuple(R.STD_DIMS)
+    assert at[std, "bf16x3", 90, 101, "forward"].endswith("head_hw=1") and at[std, "bf16x3", 90, 101, "conv_output"].endswith("head_hw=30")
+    assert at[std, "bf16x3", 110, 101, "forward"].endswith("head_hw=36")                # two bands: no fused mean
+    assert at[std, "bf16_approx", 64, 400, "forward"].endswith("unsupported=1 32x200")
+    # the two sides of the first block's limits: 110 x 102 = 11 220 pixels inside, 110 x 103 outside; 2 planes of 64 KB
+    assert at[std, "bf16x3", 110, 102, "forward"].startswith("first_x3 ") and at[std, "bf16x3", 111, 102, "forward"].startswith("first ")
+    assert at[std, "bf16x3", 27, 400, "forward"].startswith("first_x3 0 0 0 lds=48720 ") and at[std, "bf16x3", 1, 400, "forward"] == "none"
+    assert at[tuple(strip), "bf16x3", 8, 1400, "forward"].startswith("first_x3 0 0 0 lds=61864 ")       # over 60 KB
+    assert at[tuple(strip), "bf16x3", 4, 2334, "forward"].startswith("first_x3 0 0 0 lds=65520 ") and \
+        at[tuple(strip), "bf16x3", 4, 2336, "forward"].startswith("first ")                               # 65 576 B do not fit
+
+
+def test_capability_record_is_what_plan_assumes():
+    """layer_forms (what cough_cnn_create packs and the forward reads) against the conditions plan() uses, over
+    cin 8..256 step 8 x cout {32, 64, 96, 128, 256} x pool {1, 2}, every dtype, first and later layers."""
+    combos = [(dt, i, cin, cout, pool) for dt in R.DTYPES for i in (0, 1) for cin in range(8, 257, 8) for cout in (32, 64, 96, 128, 256)
+              for pool in (1, 2)]
+    _, lines = _dump([f"forms {dt} {i} {cin} {cout} {pool}" for dt, i, cin, cout, pool in combos])
+    for (dt, i, cin, cout, pool), line in zip(combos, lines):
+        later, approx, x3 = i > 0, dt == "bf16_approx", dt == "bf16x3"
+        gemm = later and approx and cin % 32 == 0 and cout % 64 == 0
+        want = (later and approx, -(-9 * cin // 64) * 64 if gemm else 9 * cin, gemm,
+                later and approx and (cin, cout) in ((16, 32), (32, 64), (64, 128)),
+                later and x3 and cin in R.X3_CFG and (cout in (32, 64) or cout % 128 == 0),
+                not later and x3 and pool == 2 and cout <= 32)
+        assert tuple(int(v) for v in line.split()) == tuple(int(v) for v in want), (dt, i, cin, cout, pool, line)
+
+
+def test_plan_constants_are_the_header_s_and_defined_once():
+    """plan() restates the dispatch with constants of its own; this ties them to the header the library is built from, so a
+    retune of CNN_X3_TABLE, CNN_FIRST_MAXL, CNN_LDS_UNP, the single-bf16 tile list or the first block's LDS limit fails
+    here until plan(), the hand-checked tables and the matrix have been revisited."""
+    consts, _ = _dump([])
+    x3 = tuple(v for cin, (nt, mw, wm, wn, pieces) in R.X3_CFG.items() for v in (cin, nt, mw, wm, wn, pieces, int(cin == 32)))
+    assert consts == {"CNN_FIRST_MAXL": (R.FIRST_MAXL,), "CNN_FIRST_LDS_LIMIT": (64 * 1024,), "CNN_LDS_UNP": (R.LDS_UNP,),
+                      "CNN_LDS_CFG": (16, 1, 4, 32, 2, 4, 64, 4, 2), "CNN_X3_TABLE": x3,
+                      "CNN_X3_THREADS": tuple(64 * c[2] * c[3] for c in R.X3_CFG.values()),
+                      "CNN_X3_MAX_LDS": tuple(16 * c[4] + 64 for c in R.X3_CFG.values()), "PLAN_MAX_LAYERS": (16,)}
+    assert (R.FIRST_MAXL, R.LDS_UNP) == (22, 12)
+    # one definition in csrc/: no second list or constant to drift to
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC))}
+    for name in ("CNN_FIRST_MAXL", "CNN_FIRST_LDS_LIMIT", "CNN_LDS_UNP", "CNN_LDS_CFG", "CNN_X3_TABLE", "PLAN_MAX_LAYERS"):
+        defs = [f for f, text in src.items() for _ in re.findall(rf"(?:#define\s+{name}\b|\b{name}(?:\[\d*\])*\s*=[^=])", text)]
+        assert defs == ["cnn_plan.h"], (name, defs)
+    for fn in ("first_lds", "layer_forms", "x3_band", "x3_lds_bytes", "lds_band", "lds_bytes", "conv_nt", "plan_cnn"):
+        defs = [f for f, text in src.items() for _ in re.findall(rf"^(?:constexpr|inline|static)[\w \*&:<>]*\b{fn}\(", text, flags=re.M)]
+        assert defs == ["cnn_plan.h"], (fn, defs)
+    # the comma-list macros are gone, and no build of the library overrides the tile configurations from the command line
+    build_py = open(os.path.join(ROOT, "cough_detector_amd", "build.py")).read()
+    assert not [f for f, text in src.items() if "CNN_X3_CFG" in text] and "CNN_X3" not in build_py
 
 
 def test_matrix_reaches_every_path_of_the_dispatch():

@@ -67,32 +67,7 @@ def _blocks(case, cnn_golden):
     return R.random_blocks(R.GENERIC[case.net], seed=sum(map(ord, case.net)))
 
 
-# hand-checked (kernel, band_rows, n_bands, fused mean) of the cases that exist for one path of the dispatch
-T_, F_ = True, False
-EXPECT = {
-    ("std_90x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 8, F_), ("lds_x3", 4, 3, F_), ("lds_x3", 5, 1, T_)],
-    ("small_90x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 5, 5, F_), ("lds_x3", 6, 2, F_), ("lds_x3", 11, 1, T_)],
-    ("std_110x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 9, F_), ("lds_x3", 4, 4, F_), ("lds_x3", 5, 2, F_)],
-    ("std_111x101", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 3, 9, F_), ("lds_x3", 4, 4, F_), ("lds_x3", 5, 2, F_)],
-    ("std_16x16", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 4, 1, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, T_)],
-    ("small_8x8", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, F_), ("lds_x3", 1, 1, T_)],
-    ("std_128x128", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 2, 16, F_), ("lds_x3", 3, 6, F_), ("lds_x3", 4, 2, F_)],
-    ("small_128x128", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 4, 8, F_), ("lds_x3", 5, 4, F_), ("lds_x3", 12, 2, F_)],
-    ("std_40x300", "bf16x3"): [("first", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 1, 5, F_), ("lds_x3", 1, 2, F_)],
-    ("std_64x400", "bf16x3"): [("first", 0, 0, F_)] + [("conv_f32", 0, 0, F_)] * 3,
-    ("small_64x400", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 1, 16, F_), ("lds_x3", 1, 8, F_), ("lds_x3", 3, 3, F_)],
-    ("std_300x40", "bf16x3"): [("first", 0, 0, F_), ("lds_x3", 8, 10, F_), ("lds_x3", 9, 5, F_), ("lds_x3", 12, 2, F_)],
-    ("small_9x200", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 2, 1, F_), ("lds_x3", 1, 1, F_), ("lds_x3", 1, 1, T_)],
-    ("nopool_26x22", "bf16x3"): [("first_x3", 0, 0, F_), ("lds_x3", 13, 1, F_), ("lds_x3", 13, 1, F_), ("lds_x3", 13, 1, F_),
-                                 ("lds_x3", 11, 2, F_)],
-    ("mixed_72x88", "bf16x3"): [("first_x3", 0, 0, F_), ("conv_f32", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 7, 2, F_),
-                                ("conv_f32", 0, 0, F_), ("lds_x3", 4, 1, F_), ("lds_x3", 4, 1, T_)],
-    ("first24_31x37", "bf16x3"): [("first_x3", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 7, 1, T_)],
-    ("first64_20x28", "bf16x3"): [("first", 0, 0, F_), ("conv_f32", 0, 0, F_), ("lds_x3", 5, 1, T_)],
-    ("std_90x101", "bf16_approx"): [("first", 0, 0, F_), ("lds_bf16", 5, 5, F_), ("lds_bf16", 5, 3, F_), ("gemm_bf16", 0, 0, F_)],
-    ("approx_48x56", "bf16_approx"): [("first", 0, 0, F_), ("lds_bf16", 9, 2, F_), ("conv_bf16", 0, 0, F_), ("lds_bf16", 6, 1, F_),
-                                      ("lds_bf16", 6, 1, F_), ("gemm_bf16", 0, 0, F_)],
-}
+EXPECT = R.EXPECT       # the hand-checked table, shared with tests/test_cnn_layer_ref_host.py
 ODD_HW = {"std_91x101", "small_91x101", "std_89x99", "small_89x99", "std_33x35", "small_33x35", "std_17x17", "small_17x17"}
 
 WORST = collections.defaultdict(lambda: (0.0, ""))      # path -> (worst GPU / bound, where); printed by the last test
