@@ -23,7 +23,9 @@ The default ``speed=False`` draws nothing for it and changes no result.
 reference calls sox for it and returns its input when sox is missing).  It is a float64 phase vocoder with a magnitude
 floor, ``cough_stretch_rows``, followed by ``cough_warp_rows`` (``cough_detector_amd/pitch.py``): stretch by
 ``2 ** (-n_steps / 12)``, resample from ``int(sample_rate / rate)`` to ``sample_rate``, cut or pad back to the clip's
-length.  The default ``pitch=False`` changes no result and moves no random stream.
+length.  The default ``pitch=False`` changes no result and moves no random stream.  ``phase_lock=True`` (with
+``pitch=True``) stretches with identity phase locking, which keeps a steady tone's level where the plain vocoder returns
+it at 0.6; it draws nothing, and the default ``phase_lock=False`` is the plain vocoder, bit for bit.
 
 Differences a caller can observe: results come back where the input lives, as float32.  With ``pitch=False``
 ``pitch_shift`` draws its coin and semitones as the reference does and returns its input unchanged -- the reference's
@@ -153,7 +155,7 @@ def _repeated_length(entry_len: int, target_len: int) -> int:
 class AudioAugmentor:
     def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
                  speed: bool = False, speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
-                 pitch_range: Tuple[int, int] = (-2, 2)):
+                 pitch_range: Tuple[int, int] = (-2, 2), phase_lock: bool = False):
         self.sample_rate = sample_rate
         self.p_augment = p_augment
         self.speed = bool(speed)
@@ -166,6 +168,9 @@ class AudioAugmentor:
             self.pitch_range = _pitch.check_pitch_range(self.pitch_range, "AudioAugmentor")
             if not 2 <= int(sample_rate) <= _lib.WARP_MAX_RATE // 2:         # int(sample_rate / rate) stays a rate the resampler takes
                 raise ValueError(f"AudioAugmentor: pitch=True needs a sample_rate in 2..2^19, got {sample_rate}")
+        self.phase_lock = bool(phase_lock)               # the pitch step's stretch mode; draws nothing
+        if self.phase_lock and not self.pitch:
+            raise ValueError("AudioAugmentor: phase_lock=True is a mode of the pitch step and needs pitch=True")
         self.noise_samples: List[torch.Tensor] = []      # (1, L) float32 on the host, as the reference keeps them
         self._bank_host = torch.zeros(0, dtype=torch.float32)
         self._bank_offsets: List[int] = []
@@ -341,13 +346,14 @@ class AudioAugmentor:
                    gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
         """``_run`` behind the speed and pitch steps (``cough_detector_amd/chain.py``): ``cough_warp_rows`` when a speed
         coin fired (shift and resampling; a row without a pair is copied), ``cough_stretch_rows`` and ``cough_warp_rows``
-        when a row has semitones (a row without is copied by both), then ``cough_augment_waveforms`` on the result with
+        when a row has semitones (a row without is copied by both; with ``phase_lock`` the stretch locks the phases of
+        the rows with semitones), then ``cough_augment_waveforms`` on the result with
         the records' shifts zeroed and the lengths ``n'``.  ``pairs`` / ``steps`` are None when the step is switched
         off.  Returns (B, max n') with a speed step and (B, N) without.  ``gaussian`` is cut to the width of the rows that
         ``_run`` gets.  When nothing fired the launches are skipped and the path is ``_run``'s."""
         b, n = x.shape
         lens = [int(v) for v in lengths] if lengths is not None else [n] * b
-        plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n)
+        plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n, self.phase_lock)
         width = plans.width if plans.arrays else n
         if gaussian is not None and gaussian.shape[1] != width:
             gaussian = gaussian[:, :width].contiguous()
@@ -434,7 +440,8 @@ class AudioAugmentor:
         """With ``pitch=False``: draws the reference's coin and semitones (:215-247; (-2, 2) by default), then returns
         the input unchanged -- what the reference returns when sox is not available; ``augment`` does not call it.
         With ``pitch=True``: the same draws (the augmentor's range by default), the input itself for 0 semitones, and
-        otherwise the clip shifted by that many semitones, (1, n): ``pitch_shift_rows``."""
+        otherwise the clip shifted by that many semitones, (1, n): ``pitch_shift_rows``, in the augmentor's stretch mode
+        (``phase_lock``)."""
         if not self.pitch:
             if random.random() > self.p_augment:
                 return waveform
@@ -590,10 +597,11 @@ class MixUp:
 def create_augmentation_pipeline(sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
                                  use_spec_augment: bool = True, speed: bool = False,
                                  speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
-                                 pitch_range: Tuple[int, int] = (-2, 2)) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
+                                 pitch_range: Tuple[int, int] = (-2, 2),
+                                 phase_lock: bool = False) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
     """(AudioAugmentor, SpecAugment or None), reference :372-398; ``speed`` / ``speed_range`` / ``pitch`` /
-    ``pitch_range`` go to the augmentor."""
+    ``pitch_range`` / ``phase_lock`` go to the augmentor."""
     audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment, speed=speed,
-                               speed_range=speed_range, pitch=pitch, pitch_range=pitch_range)
+                               speed_range=speed_range, pitch=pitch, pitch_range=pitch_range, phase_lock=phase_lock)
     spec_aug = SpecAugment(p=p_augment) if use_spec_augment else None
     return audio_aug, spec_aug

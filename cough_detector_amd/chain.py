@@ -37,7 +37,8 @@ class HostPlans(NamedTuple):
 
 
 def host_plans(shifts: Sequence[int], pairs: Optional[Sequence[Optional[Tuple[int, int]]]],
-               steps: Optional[Sequence[Optional[int]]], lengths: Sequence[int], sample_rate: int, n: int) -> HostPlans:
+               steps: Optional[Sequence[Optional[int]]], lengths: Sequence[int], sample_rate: int, n: int,
+               phase_lock: bool = False) -> HostPlans:
     """The plans of a batch drawn on the host.  Per row: its time shift, the speed step's ``(orig, new)`` (None when its
     coin did not fire), the pitch step's semitones (None likewise; 0 shifts nothing) and its length; ``pairs`` /
     ``steps`` are None as a whole when the step is switched off.  ``n`` is the width of the input rows.
@@ -45,7 +46,9 @@ def host_plans(shifts: Sequence[int], pairs: Optional[Sequence[Optional[Tuple[in
     The first launch that reads the source rows carries the shift: the warp if any pair fired, else the stretch if any
     row has semitones, else the augmentation record.  A row without a pair is copied by the warp (``(1, 1)``), a row
     without semitones by the stretch and its resampling (rate 1, ``(1, 1)``).  The output is ``max n'`` wide with a
-    speed step and ``n`` wide without."""
+    speed step and ``n`` wide without.  With ``phase_lock`` the stretch plans of the rows with semitones other than 0
+    carry the mode ``pitch.PHASE_LOCK`` and all other rows mode 0 -- the rule of ``cough_draw_pitch``, so the host's and
+    the device's plans of the same draws are the same bytes."""
     lengths = [int(v) for v in lengths]
     warps = pairs is not None and any(p is not None for p in pairs)
     new_lengths = [l if p is None else _warp.warped_length(l, *p) for l, p in zip(lengths, pairs)] if warps else lengths
@@ -56,7 +59,8 @@ def host_plans(shifts: Sequence[int], pairs: Optional[Sequence[Optional[Tuple[in
         arrays["new_lengths"] = np.asarray(new_lengths, dtype=np.int32)
     if steps is not None and any(steps):
         rates = [_pitch.pitch_rate(s) if s else 1.0 for s in steps]
-        arrays["stretch"] = _pitch.plan_array([(0 if warps else shift, r) for shift, r in zip(shifts, rates)])
+        modes = [_pitch.PHASE_LOCK if phase_lock and s else 0 for s in steps]
+        arrays["stretch"] = _pitch.plan_array([(0 if warps else shift, r, m) for shift, r, m in zip(shifts, rates, modes)])
         arrays["back"] = _warp.plan_array([(0,) + (_pitch.pitch_rate_pair(s, sample_rate) if s else (1, 1)) for s in steps])
         stretch_width = max(_pitch.stretched_length(l, r) for l, r in zip(new_lengths, rates))
     return HostPlans(arrays, new_lengths, width, stretch_width)

@@ -6,7 +6,15 @@
 // the CU: a second of audio has 126 x 257 complex doubles (518 KB), so the workgroup keeps only the two input spectra
 // an output frame interpolates between -- as magnitude and unit phasor per bin, transformed once each as the march
 // reaches them -- the accumulated phasor P of bin `tid` in registers (thread 0 also carries bin 256), two FFT buffers
-// and a 512-sample overlap-add ring whose finished 128 samples leave as float32 after every frame.  About 41 KB of LDS.
+// and a 512-sample overlap-add ring whose finished 128 samples leave as float32 after every frame.  About 49 KB of LDS.
+//
+// Identity phase locking (plan.reserved bit 0, uniform over the block).  When an input frame is analysed, every bin
+// decides whether it is a peak, the waves publish the decisions as ballots (four 64-bit words and bin 256), and every
+// bin finds its nearest peak with a count-leading / find-first-set over at most five words: O(1) per bin whatever the
+// number of peaks, once per input frame and at the cost of one barrier.  An output frame costs no barrier of its own:
+// every bin leaves the phasor it carries into the next frame in LDS before the barriers of the inverse transform, and
+// the bins that a peak owns read the peak's there and the two analysis phasors that tie them to it (two buffers, by
+// the parity of t, because a wave may run ahead into the next frame's write).  A plain row skips all of it.
 //
 // The FFT is a 512-point complex radix-2 Stockham transform, one butterfly per thread and stage, nine barriers.  A
 // real frame goes in with a zero imaginary part; the inverse transforms the conjugated Hermitian extension and keeps
@@ -73,6 +81,8 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
     __shared__ double2 buf_a[NFFT], buf_b[NFFT];
     __shared__ double s_mag[2][SPEC], s_ux[2][SPEC], s_uy[2][SPEC];   // the two cached input spectra
     __shared__ double ring[NFFT];              // overlap-add, sample m at m & 511
+    __shared__ double2 s_q[2][SPEC];           // locked rows: R[t] of every bin at [t & 1], for the bins a peak owns
+    __shared__ unsigned long long s_peaks[2][PT / 64 + 1];       // locked rows: per slot, the peaks of bins 0 .. 256 as bits
     __shared__ float red_peak[PT / 64];
     __shared__ int red_bad[PT / 64];
 
@@ -81,6 +91,7 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
     const cough_stretch_plan plan = plans[b];
     const int shift = min(max(plan.shift, -n), n);
     const double rate = plan.rate;
+    const bool lock = (plan.reserved & COUGH_STRETCH_PHASE_LOCK) != 0;       // uniform over the block
     const float* x = src + row_offsets[b];
     float* o = out + (long long)b * n_samples;
 
@@ -146,6 +157,7 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
                 s_ux[s][HALF] = 1.0;
                 s_uy[s][HALF] = 0.0;
             }
+            if (lock && tid <= PT / 64) s_peaks[s][tid] = 0ull;               // no peaks: every bin owns itself
             __syncthreads();
             return;
         }
@@ -166,6 +178,37 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
             s_uy[s][k] = low ? 0.0 : v.y / m;
         }
         __syncthreads();
+        if (!lock) return;
+        // a peak is above the floor and above the bins within two of it (0 .. 256: there is no mirror)
+        auto is_peak = [&](int k) {
+            const double m = s_mag[s][k];
+            bool pk = m > floor_mag;
+            for (int d = -2; d <= 2; ++d) {
+                const int j = k + d;
+                if (d != 0 && j >= 0 && j <= HALF) pk = pk && m > s_mag[s][j];
+            }
+            return pk;
+        };
+        const unsigned long long votes = __ballot(is_peak(tid));
+        if ((tid & 63) == 0) s_peaks[s][tid >> 6] = votes;
+        if (tid == 0) s_peaks[s][PT / 64] = is_peak(HALF) ? 1ull : 0ull;
+        __syncthreads();
+    };
+    // the nearest peak of bin k in slot s, the lower one on a tie; k itself when the frame has no peak.  Five words,
+    // no loop over the peaks and no branch on them: selects only.
+    auto owner = [&](int k, int s) {
+        const int w = k >> 6, bit = k & 63;
+        int below = -1, above = -1;
+#pragma unroll
+        for (int i = 0; i <= PT / 64; ++i) {
+            const unsigned long long word = s_peaks[s][i];
+            const unsigned long long lo = i < w ? word : i == w ? word & (~0ull >> (63 - bit)) : 0ull;      // peaks <= k
+            const unsigned long long hi = i > w ? word : i == w ? word & (~0ull << bit) : 0ull;             // peaks >= k
+            below = lo ? (i << 6) + 63 - __clzll((long long)lo) : below;                                    // the last word wins
+            above = hi && above < 0 ? (i << 6) + __ffsll(hi) - 1 : above;                                   // the first
+        }
+        const int near = above < 0 || (below >= 0 && k - below <= above - k) ? below : above;
+        return near < 0 ? k : near;
     };
 
     // env[m] = sum over the frames t that cover m of w[m - 128 t]^2, ascending t
@@ -186,6 +229,15 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
     };
 
     int slot_frame[2] = {-1, -1};              // which input frame each slot holds (uniform over the block)
+    int own_0 = tid, own_1 = tid, own_nyq_0 = HALF, own_nyq_1 = HALF;        // locked rows: per slot, the owner of bin tid; of bin 256
+    auto adopt = [&](int s) {                  // after analyse(f, s), whose last barrier published the slot's peaks
+        if (!lock) return;
+        const int p = owner(tid, s), p_nyq = tid == 0 ? owner(HALF, s) : HALF;
+        own_0 = s ? own_0 : p;
+        own_1 = s ? p : own_1;
+        own_nyq_0 = s ? own_nyq_0 : p_nyq;
+        own_nyq_1 = s ? p_nyq : own_nyq_1;
+    };
     double2 P = make_double2(1.0, 0.0), P_nyq = make_double2(1.0, 0.0);      // bin tid; bin 256 (thread 0)
     for (int t = 0; t < T_out; ++t) {
         const double ts = double(t) * rate;
@@ -197,18 +249,40 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
         if (s0 < 0) {
             s0 = s1 == 0 ? 1 : 0;
             analyse(i0, s0);
+            adopt(s0);
             slot_frame[s0] = i0;
         }
         if (s1 < 0) {
             s1 = 1 - s0;
             analyse(i0 + 1, s1);
+            adopt(s1);
             slot_frame[s1] = i0 + 1;
         }
         if (t == 0) {
             P = make_double2(s_ux[s0][tid], s_uy[s0][tid]);
             if (tid == 0) P_nyq = make_double2(s_ux[s0][HALF], s_uy[s0][HALF]);
         }
-        // Y[t] = mag * P into the conjugated Hermitian extension; then P advances by u(S[i0+1]) conj(u(S[i0]))
+        if (lock) {
+            // Q[t]: a peak keeps the phasor it carries; a bin it owns takes the peak's, turned by the phase the bin
+            // has against the peak in input frame i0.  P holds R[t] on entry and Q[t] on exit.  Every bin left its
+            // R[t] in s_q[t & 1] before the barriers of frame t - 1's inverse transform, so frame 0 alone needs one.
+            if (t == 0) {
+                s_q[0][tid] = P;
+                if (tid == 0) s_q[0][HALF] = P_nyq;
+                __syncthreads();
+            }
+            auto led = [&](int k, int p) {
+                const double2 r = s_q[t & 1][p];
+                const double ukx = s_ux[s0][k], uky = s_uy[s0][k], upx = s_ux[s0][p], upy = s_uy[s0][p];
+                const double cx = ukx * upx + uky * upy, cy = uky * upx - ukx * upy;  // u(S[k]) * conj(u(S[p]))
+                return make_double2(r.x * cx - r.y * cy, r.x * cy + r.y * cx);
+            };
+            const int p = s0 ? own_1 : own_0, p_nyq = s0 ? own_nyq_1 : own_nyq_0;
+            if (p != tid) P = led(tid, p);
+            if (tid == 0 && p_nyq != HALF) P_nyq = led(HALF, p_nyq);
+        }
+        // Y[t] = mag * P into the conjugated Hermitian extension; then P advances by u(S[i0+1]) conj(u(S[i0])) (locked
+        // rows: R[t+1] = Q[t] times the same step)
         auto synthesise = [&](int k, double2& p) {
             const double mag = a * s_mag[s1][k] + (1.0 - a) * s_mag[s0][k];
             const double yr = mag * p.x, yi = mag * p.y;
@@ -222,6 +296,10 @@ __global__ __launch_bounds__(PT) void stretch_kernel(const float* __restrict__ s
         };
         synthesise(tid, P);
         if (tid == 0) synthesise(HALF, P_nyq);
+        if (lock) {                            // R[t + 1] for the bins that a peak of the next frame's i0 owns
+            s_q[(t + 1) & 1][tid] = P;
+            if (tid == 0) s_q[(t + 1) & 1][HALF] = P_nyq;
+        }
         __syncthreads();
         const double2* y = fft512(buf_a, buf_b, tw, tid);
         for (int j = tid; j < NFFT; j += PT) {
@@ -254,7 +332,7 @@ __global__ __launch_bounds__(DT) void draw_pitch_kernel(unsigned long long seed,
     auto unit = [](unsigned x) { return (double(x) + 0.5) * 0x1p-32; };
     cough_stretch_plan sp;
     sp.shift = 0;
-    sp.reserved = 0;
+    sp.reserved = 0;                           // the mode
     sp.rate = 1.0;
     cough_warp_plan wp;
     wp.shift = 0;
@@ -268,6 +346,7 @@ __global__ __launch_bounds__(DT) void draw_pitch_kernel(unsigned long long seed,
             const int steps = min(lo + int(double(hi - lo + 1) * unit(d.y)), hi);
             if (steps != 0) {
                 sp.rate = table[steps - lo].rate;
+                sp.reserved = table[steps - lo].reserved & COUGH_STRETCH_PHASE_LOCK;
                 wp.orig = table[steps - lo].orig;
             }
         }

@@ -43,7 +43,8 @@ An ``AudioAugmentor(pitch=True)`` adds the pitch step behind it (``cough_detecto
 the clips in place from the bank and applies the time shift.  With ``draws="host"`` the two plans per row travel with
 the pinned upload (a batch in which no pitch coin fired runs the launches it ran before); with ``draws="device"``
 ``cough_draw_pitch`` draws them, and the stretched rows are as wide as the largest number of semitones can make the
-longest row.
+longest row.  The augmentor's ``phase_lock`` is the stretch's mode for the rows with semitones: it rides in the host's
+stretch plans or in the table ``cough_draw_pitch`` reads, and changes neither the draws nor the launches.
 """
 from __future__ import annotations
 
@@ -476,7 +477,7 @@ class DeviceDataLoader:
         plans = None
         if plan.clips is not None and (plan.warps() or plan.pitches()):  # the plans ride behind the other words
             plans = _chain.host_plans([c.shift for c in plan.clips], plan.pairs, plan.steps, host_lens,
-                                      self.audio_augmentor.sample_rate, row_len)
+                                      self.audio_augmentor.sample_rate, row_len, self.audio_augmentor.phase_lock)
             row_len = plans.width
             for name, array in plans.arrays.items():
                 words.add(name, array, align8=name == "stretch")
@@ -536,8 +537,9 @@ class DeviceDataLoader:
             speed = _warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) + (row_len,)
             lens_new = speed[1]
         if aug is not None and aug.pitch:
-            if self._pitch_table is None:
-                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate)).to(bank.device)
+            if self._pitch_table is None:        # the augmentor's stretch mode rides in the table's entries
+                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate,
+                                                                       aug.phase_lock)).to(bank.device)
             pitch = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
                                       self._pitch_table)[:2] + (_pitch.drawn_width(row_len, aug.pitch_range), row_len)
         clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,

@@ -7,13 +7,16 @@ and moves the pitch (``torchaudio.functional.pitch_shift``).
 * ``stretch_rows``: every row of a batch stretched by a rate of its own in one launch of ``cough_stretch_rows`` -- a
   float64 phase vocoder (n_fft 512, hop 128, Hann) with a magnitude floor, one workgroup per row; the spectra stay in
   LDS.  The rows are read in place from a packed buffer and the time shift of the waveform chain is fused into the read.
+  A row whose plan carries the mode ``PHASE_LOCK`` is stretched with identity phase locking, which keeps a steady
+  tone's level (the plain vocoder returns a 440 Hz tone at 0.6 of it); mode 0, the default everywhere, is the plain
+  vocoder.
 * ``pitch_shift_rows``: ``stretch_rows``, then ``warp_rows`` (``cough_detector_amd/warp.py``) on the stretched rows.
 * ``draw_pitch``: the per-row plans of both launches for a ``draws="device"`` batch, one launch of ``cough_draw_pitch``
   -- a seeded Philox4x32-10 stream per batch.
 * ``pitch_rate`` / ``pitch_rate_pair`` / ``stretched_length``: the host's side of the same arithmetic.
 
 The arithmetic and the draw contract are stated in ``include/cough_amd_pitch.h`` and restated in numpy in
-``tests/pitch_ref.py``.
+``tests/pitch_ref.py`` (the locked mode in ``tests/pitch_lock_ref.py``).
 """
 from __future__ import annotations
 
@@ -30,6 +33,7 @@ from ._native import _on_gpu, _stream
 PLAN_BYTES = C.sizeof(_lib.CoughStretchPlan)       # 16: int32 shift, int32 reserved, float64 rate
 MAX_LENGTH = _lib.PITCH_MAX_LENGTH
 MIN_STRETCH_LENGTH = 257                           # the reflect padding of the first and last frame needs 257 samples
+PHASE_LOCK = 1                                     # COUGH_STRETCH_PHASE_LOCK: the mode bit of a plan's `reserved` word
 _PLAN_DTYPE = np.dtype([("shift", np.int32), ("reserved", np.int32), ("rate", np.float64)])
 _STEP_DTYPE = np.dtype([("rate", np.float64), ("orig", np.int32), ("reserved", np.int32)])
 
@@ -64,21 +68,26 @@ def check_pitch_range(pitch_range: Sequence[int], who: str) -> Tuple[int, int]:
     return int(lo), int(hi)
 
 
-def plan_array(plans: Sequence[Tuple[int, float]]) -> np.ndarray:
-    """(B, 16) uint8: ``(shift, rate)`` per row in the layout of ``cough_stretch_plan``."""
+def plan_array(plans: Sequence[Sequence]) -> np.ndarray:
+    """(B, 16) uint8: ``(shift, rate)`` or ``(shift, rate, mode)`` per row in the layout of ``cough_stretch_plan``.  The
+    mode (0 when left out) goes into the field ``reserved``: ``PHASE_LOCK`` stretches the row with identity phase locking,
+    0 with the plain vocoder; the kernel reads bit 0 only."""
     arr = np.zeros(len(plans), dtype=_PLAN_DTYPE)
-    for k, (shift, rate) in enumerate(plans):
-        arr[k] = (max(-2**31, min(2**31 - 1, int(shift))), 0, float(rate))
+    for k, plan in enumerate(plans):
+        shift, rate, mode = plan if len(plan) == 3 else tuple(plan) + (0,)
+        arr[k] = (max(-2**31, min(2**31 - 1, int(shift))), int(mode), float(rate))
     return arr.view(np.uint8).reshape(len(plans), PLAN_BYTES)
 
 
-def step_table(pitch_range: Sequence[int], sample_rate: int) -> np.ndarray:
+def step_table(pitch_range: Sequence[int], sample_rate: int, phase_lock: bool = False) -> np.ndarray:
     """(hi - lo + 1, 16) uint8: per ``n_steps`` in ``lo..hi`` the rate and the resampler's ``orig``, the layout of
-    ``cough_pitch_step`` -- computed here so that no device ``pow`` enters the draw."""
+    ``cough_pitch_step`` -- computed here so that no device ``pow`` enters the draw.  With ``phase_lock`` every entry
+    carries the mode ``PHASE_LOCK`` in its ``reserved`` word, and ``cough_draw_pitch`` hands it to the rows that draw
+    semitones other than 0."""
     lo, hi = check_pitch_range(pitch_range, "step_table")
     arr = np.zeros(hi - lo + 1, dtype=_STEP_DTYPE)
     for k, s in enumerate(range(lo, hi + 1)):
-        arr[k] = (pitch_rate(s), pitch_rate_pair(s, sample_rate)[0], 0)
+        arr[k] = (pitch_rate(s), pitch_rate_pair(s, sample_rate)[0], PHASE_LOCK if phase_lock else 0)
     return arr.view(np.uint8).reshape(hi - lo + 1, PLAN_BYTES)
 
 
@@ -123,19 +132,22 @@ def pitch_shift_rows(src: torch.Tensor, row_offsets_dev: torch.Tensor, lengths_d
 
 
 def draw_pitch(seed: int, lengths_dev: torch.Tensor, p_augment: float, pitch_range: Sequence[int],
-               sample_rate: int, table_dev: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+               sample_rate: int, table_dev: Optional[torch.Tensor] = None,
+               phase_lock: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The pitch draws of one batch, on the device: ``(stretch plans uint8 (B, 16), warp plans int32 (B, 3), stretched
     lengths int32 (B,))``.  Row b's coin fires with probability ``p_augment``; it then draws ``n_steps`` uniformly
     from ``pitch_range`` (inclusive, as ``random.randint``) and gets the rate ``pitch_rate(n_steps)`` and the pair
     ``pitch_rate_pair(n_steps, sample_rate)``; otherwise, and for 0 semitones, rate 1 and ``(sample_rate,
-    sample_rate)``.  ``table_dev``: ``step_table(pitch_range, sample_rate)`` already on the device (uploaded here
-    otherwise).  The same ``seed`` gives the same draws."""
+    sample_rate)``.  ``table_dev``: ``step_table(pitch_range, sample_rate, phase_lock)`` already on the device (uploaded
+    here otherwise; ``phase_lock`` is not looked at when the caller brings a table).  A row that draws semitones other
+    than 0 gets the mode of its table entry (``PHASE_LOCK`` or 0), every other row mode 0.  The same ``seed`` gives the
+    same draws, whatever the mode."""
     lo, hi = check_pitch_range(pitch_range, "draw_pitch")
     if not 1 <= int(sample_rate) <= _lib.WARP_MAX_RATE:
         raise ValueError(f"draw_pitch: sample_rate {sample_rate} must lie in 1..2^20")
     dev = _on_gpu("draw_pitch", lengths_dev=(lengths_dev, torch.int32))
     if table_dev is None:
-        table_dev = torch.from_numpy(step_table((lo, hi), sample_rate)).to(dev)
+        table_dev = torch.from_numpy(step_table((lo, hi), sample_rate, phase_lock)).to(dev)
     _on_gpu("draw_pitch", lengths_dev=(lengths_dev, torch.int32), table_dev=(table_dev, torch.uint8))
     if table_dev.numel() != (hi - lo + 1) * PLAN_BYTES:
         raise ValueError(f"draw_pitch: table_dev must hold {hi - lo + 1} entries of {PLAN_BYTES} bytes")

@@ -57,6 +57,34 @@
  * An implementation meets the contract when every sample satisfies |y - y_ref| <= 2^-24 |y_ref| + E[m] with the
  * first-order bound E of tests/pitch_ref.py, which allows the spectrum an error of 16 * 2^-53 * 256 * peak per bin.
  *
+ * THE LOCKED STRETCH'S ARITHMETIC (a plan whose mode word has bit 0 set: identity phase locking, Laroche & Dolson 1999).
+ * A plain vocoder advances every bin's phase on its own, so the bins of a sinusoid's main lobe drift apart and the
+ * sinusoid loses level (a steady 440 Hz tone shifted up two semitones comes back at 0.6 of its level).  Here only the
+ * spectral peaks carry a phase forward; the bins around a peak keep the phase relation they had to it in the analysis
+ * frame.  Everything not named below is exactly as in the plain stretch: float64 without contraction, the floor, u(),
+ * mag, T, T_out, i0, a, the inverse transform, the overlap-add, the envelope, n_s, the rows that are copied, the NaN /
+ * Inf rows and the silent rows.  Write f = i0(t) and M[k] = |S[f][k]|.
+ *   peaks of input frame f < T: bin k is a peak when M[k] > floor and M[k] > M[j] for every j in {k-2, k-1, k+1, k+2}
+ *            with 0 <= j <= 256 (there is no Hermitian mirror);  the zero frames T and T + 1 have no peaks
+ *   own[f][k] = k when frame f has no peak;  else the peak p that minimises |k - p|, the lower p on a tie (a peak owns
+ *            itself)
+ *   R[0] = u(S[0]);  for t = 0 .. T_out-1, with p = own[f][k]:
+ *            Q[t][k]   = R[t][k] when p == k, else R[t][p] * u(S[f][k]) * conj(u(S[f][p]))
+ *            Y[t][k]   = mag[t][k] * Q[t][k]
+ *            R[t+1][k] = Q[t][k] * u(S[f+1][k]) * conj(u(S[f][k]))
+ *            (the kernel may renormalise any product of unit phasors)
+ * With mode 0, Q = R = P.  In both modes frame 0 is u(S[0]).  While i0(t) == t the two modes coincide, because
+ * R[t] = u(S[t]) telescopes and Q[t][k] = u(S[t][p]) u(S[t][k]) conj(u(S[t][p])): that covers the first frames of any row
+ * and all of a short row at rate 2^(1/12).
+ * The contract is the plain one, |y - y_ref| <= 2^-24 |y_ref| + E_lock[m], with the first-order bound E_lock of
+ * tests/pitch_lock_ref.py: delta and the per-bin phasor uncertainty eu (delta / |S| above the floor, 0 at or below it)
+ * as for E, and  eR[0] = eu[0];  eQ[k] = eR[k] for a bin that owns itself, else eR[p] + eu[f][k] + eu[f][p];
+ * eY = mag * eQ + delta;  eR' = eQ + eu[f+1] + eu[f];  then through the inverse transform, the window, the overlap-add
+ * and the envelope as E is.  Two implementations must also pick the same peaks: for every frame f < T and every bin with
+ * M[k] > floor let m_k = min(M[k] - floor, min over the existing neighbours j of (M[k] - M[j]) / 2); m_k > 0 exactly when
+ * k is a peak, and |m_k| is what a perturbation must overcome to flip the decision.  A row is fit for a comparison only
+ * when its peak margin, min |m_k| / delta, is at least 64, like its floor margin.
+ *
  * THE PITCH DRAW CONTRACT, in the conventions of cough_amd_draws.h: Philox4x32-10, key = seed (low word, high word); a
  * 32-bit word x gives u = (x + 0.5) * 2^-32 in float64; a coin with probability p fires iff u <= p; all arithmetic is
  * float64, one IEEE operation per operator, conversions to int truncate toward zero.
@@ -88,10 +116,15 @@ extern "C" {
 int cough_pitch_abi_version(void);
 const char* cough_pitch_last_error(void);  /* thread-local, never NULL */
 
+/* The mode word of a plan or a table entry (the field `reserved`, which every version 1 caller wrote as 0): bit 0 set
+ * means identity phase locking, THE LOCKED STRETCH'S ARITHMETIC above; mode 0 is the plain stretch, unchanged.  All other
+ * bits are ignored -- the host never sees device plans, so a word the kernel does not know must be harmless. */
+#define COUGH_STRETCH_PHASE_LOCK 1
+
 /* One row's plan.  16 bytes. */
 typedef struct cough_stretch_plan {
     int shift;     /* time_shift samples: > 0 right (zeros on the left), < 0 left */
-    int reserved;  /* not read */
+    int reserved;  /* the mode: COUGH_STRETCH_PHASE_LOCK or 0; only bit 0 is read */
     double rate;   /* the row becomes n_s = rint(n / rate) samples long: > 1 shorter, < 1 longer */
 } cough_stretch_plan;
 
@@ -99,7 +132,7 @@ typedef struct cough_stretch_plan {
 typedef struct cough_pitch_step {
     double rate;   /* 2^(-n_steps / 12) */
     int orig;      /* (int)(sample_rate / rate): the rate the stretched row is taken to have */
-    int reserved;  /* not read */
+    int reserved;  /* the mode a row that draws this entry gets: COUGH_STRETCH_PHASE_LOCK or 0; only bit 0 is read */
 } cough_pitch_step;
 
 /* ------------------------------------------------------------------ per-row time stretch
@@ -122,7 +155,8 @@ int cough_stretch_rows(const float* d_src, const long long* d_row_offsets, const
  * One thread per row draws by the contract above and writes the row's stretch plan (shift 0, the drawn entry's rate) to
  * d_stretch_plans_out[row], the resampler's plan (0, the entry's orig, sample_rate) to d_warp_plans_out[row] and the
  * length n_s the stretch gives the row to d_stretch_lengths_out[row].  A coin that did not fire, or n_steps == 0,
- * writes rate 1 and (0, sample_rate, sample_rate).
+ * writes rate 1 and (0, sample_rate, sample_rate).  The stretch plan's mode word is (table[n_steps - lo].reserved & 1)
+ * when the coin fired and n_steps != 0, and 0 otherwise: a table of zeros draws plain plans, as version 1 callers get.
  *   d_lengths: [n_rows] int32, the rows' lengths n (a length < 1 yields the blank plans and n_s = 0; a length above
  *              2^20 counts as 2^20)
  *   d_table:   [hi - lo + 1] cough_pitch_step, entry n_steps - lo for n_steps = lo .. hi, 8-byte aligned

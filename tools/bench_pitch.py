@@ -1,4 +1,4 @@
-"""Times pitch shift on the MI355X; writes profiles/pitch_shift_bench.txt.
+"""Times pitch shift on the MI355X; writes profiles/pitch_shift_bench.txt (``--steps lock``: profiles/pitch_lock_bench.txt).
 
 Everything runs in one process, the two sides of a comparison alternating run by run so that both see the same box at the
 same time; medians of ``--repeats`` runs after ``--warmup`` warm-up runs each are reported.
@@ -12,6 +12,11 @@ same time; medians of ``--repeats`` runs after ``--warmup`` warm-up runs each ar
   loader  an epoch of a ``DeviceDataLoader`` alone, then the same epoch feeding ``train_epoch_async`` (SmallTrainer),
           each with and without ``pitch`` on the augmentor, in both draw modes, ``--clips`` synthetic 1 s clips at batch
           32, a host clock around the epoch.  The baseline is the same tree with ``pitch=False``.
+  lock    identity phase locking (the mode bit of the stretch plans) against the plain stretch of the same build, same
+          rows and semitones: ``cough_stretch_rows``, ``pitch_shift_rows`` and one 32-row ``launch_batch_drawn`` of a
+          ``DeviceDataLoader`` whose every row draws a pitch coin.  With ``--parent-lib`` (another build of
+          ``libcough_amd_pitch.so``, e.g. the parent commit's) the plain stretch of that library runs as a third side,
+          its outputs are compared bit for bit with this build's plain rows, and its own spread is the yardstick.
 
 Run it under a time limit, e.g. ``timeout -k 10 400 python tools/bench_pitch.py``.
 """
@@ -30,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import cough_detector_amd as cda                                  # noqa: E402
+from cough_detector_amd import _lib                               # noqa: E402
 from cough_detector_amd import synth                              # noqa: E402
 from cough_detector_amd import pitch as cpitch                    # noqa: E402
 from cough_detector_amd import warp as cwarp                      # noqa: E402
@@ -144,6 +150,97 @@ def bench_kernel(args, lines) -> None:
                   "not compared)"]
 
 
+def bench_lock(args, lines) -> None:
+    b, n, sr = args.rows, 16000, 16000
+    x = ((torch.rand((b, n), generator=torch.Generator().manual_seed(1)) - 0.5) * 0.8).cuda()
+    flat = x.reshape(-1)
+    offs = (torch.arange(b, dtype=torch.int64) * n).cuda()
+    lens = torch.full((b,), n, dtype=torch.int32).cuda()
+    plain, back, _ = cpitch.draw_pitch(7, lens, 1.0, RANGE, sr)
+    locked = cpitch.draw_pitch(7, lens, 1.0, RANGE, sr, phase_lock=True)[0]
+    modes = locked.cpu().numpy().view(cpitch._PLAN_DTYPE)["reserved"].reshape(-1)
+    width = cpitch.drawn_width(n, RANGE)
+    lines += [f"  lock: {b} rows of {n} samples, semitones drawn in {RANGE} (p = 1), {int(modes.sum())} rows with semitones "
+              f"(locked on the locked side), width {width}; device events around the launches, sides alternating"]
+    sides = {"plain": lambda: cpitch.stretch_rows(flat, offs, lens, plain, width),
+             "locked": lambda: cpitch.stretch_rows(flat, offs, lens, locked, width)}
+    parent = None
+    if args.parent_lib:
+        parent = _lib.Library("pitch", _lib.LIBRARIES["pitch"].abi, _lib.LIBRARIES["pitch"].prototypes)
+        parent.path = os.path.abspath(args.parent_lib)
+
+        def stretch_parent():                                     # allocates its output, as stretch_rows does
+            out = torch.empty((b, width), dtype=torch.float32, device="cuda")
+            parent.check(parent.load().cough_stretch_rows(flat.data_ptr(), offs.data_ptr(), lens.data_ptr(), b, plain.data_ptr(),
+                                                          out.data_ptr(), width, None, torch.cuda.current_stream().cuda_stream),
+                         "cough_stretch_rows")
+            return out
+        sides = {"parent": stretch_parent, **sides}
+        same = torch.equal(stretch_parent(), sides["plain"]())
+        lines.append(f"  plain rows of this build against {args.parent_lib}: {'bit-identical' if same else 'NOT bit-identical'} on these {b} rows")
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        try:
+            import pitch_lock_ref as L
+            import pitch_ref as P
+            cases = L.lock_cases()
+            packed, offsets = P.pack(cases)
+            t_src, t_offs = torch.from_numpy(packed).cuda(), torch.from_numpy(offsets).cuda()
+            t_lens = torch.tensor([c[1].size for c in cases], dtype=torch.int32).cuda()
+            t_plans = torch.from_numpy(cpitch.plan_array([(c[2], c[3]) for c in cases])).cuda()
+            t_width = max(cpitch.stretched_length(c[1].size, c[3]) for c in cases)
+            ours = cpitch.stretch_rows(t_src, t_offs, t_lens, t_plans, t_width)
+            theirs = torch.empty_like(ours)
+            parent.check(parent.load().cough_stretch_rows(t_src.data_ptr(), t_offs.data_ptr(), t_lens.data_ptr(), len(cases),
+                                                          t_plans.data_ptr(), theirs.data_ptr(), t_width, None,
+                                                          torch.cuda.current_stream().cuda_stream),
+                         "cough_stretch_rows")
+            same = bool((ours.view(torch.int32) == theirs.view(torch.int32)).all())
+            lines.append(f"  the same on the {len(cases)} rows of the test batch (tests/pitch_lock_ref.py, NaN rows included): "
+                         f"{'bit-identical' if same else 'NOT bit-identical'}")
+        except ImportError as e:
+            lines.append(f"  the test batch could not be loaded: {e}")
+    sides["pitch_shift_rows, plain"] = lambda: cpitch.pitch_shift_rows(flat, offs, lens, plain, back, n, width)
+    sides["pitch_shift_rows, locked"] = lambda: cpitch.pitch_shift_rows(flat, offs, lens, locked, back, n, width)
+    for _ in range(args.warmup):
+        for fn in sides.values():
+            fn()
+    times = {name: [] for name in sides}
+    for _ in range(args.repeats):
+        for name, fn in sides.items():
+            times[name].append(device_time(fn))
+    med = {name: statistics.median(t) for name, t in times.items()}
+    spread = lambda t: (max(t) - min(t)) / statistics.median(t)                                        # noqa: E731
+    for name, t in times.items():
+        lines.append(fmt(name if "rows" in name else f"cough_stretch_rows, {name}", t))
+    if parent is not None:
+        lines.append(f"    plain / parent = {med['plain'] / med['parent']:.4f}; the parent's own spread (max - min) / median over "
+                     f"{args.repeats} rounds: {100 * spread(times['parent']):.1f} %")
+    lines.append(f"    cough_stretch_rows: locked / plain = {med['locked'] / med['plain']:.4f}; pitch_shift_rows: locked / plain = "
+                 f"{med['pitch_shift_rows, locked'] / med['pitch_shift_rows, plain']:.4f}; the plain side's spread "
+                 f"{100 * spread(times['plain']):.1f} %")
+    # one 32-row batch of the loader, device draws, every row with a pitch coin
+    pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
+    audio = synth.device_clips(4100, 64).reshape(-1)
+    bank = object.__new__(cda.DeviceClipBank)
+    bank.device = audio.device
+    bank._set(audio, [synth.N] * 64, [k % 2 for k in range(64)])
+    loaders = {lock: cda.DeviceDataLoader(bank, pre, batch_size=32, draws="device", generator=torch.Generator().manual_seed(2),
+                                          audio_augmentor=cda.AudioAugmentor(p_augment=1.0, pitch=True, phase_lock=lock),
+                                          spec_augmentor=cda.SpecAugment(p=0.5)) for lock in (False, True)}
+    indices = list(range(32))
+    for _ in range(args.warmup):
+        for ld in loaders.values():
+            ld.launch_batch_drawn(indices, 5)
+    t_batch = {lock: [] for lock in loaders}
+    for k in range(args.repeats):
+        for lock, ld in loaders.items():
+            t_batch[lock].append(host_time(lambda: ld.launch_batch_drawn(indices, 100 + k)))
+    lines += [fmt("loader batch of 32 (launch_batch_drawn, p = 1), plain", t_batch[False]),
+              fmt("loader batch of 32 (launch_batch_drawn, p = 1), locked", t_batch[True]),
+              f"    loader batch: locked / plain = {statistics.median(t_batch[True]) / statistics.median(t_batch[False]):.4f} "
+              "(host clock, launch to synchronize; 4 of 5 rows draw semitones)"]
+
+
 def bench_loader(args, lines) -> None:
     pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
     audio = synth.device_clips(4100, args.clips).reshape(-1)
@@ -184,19 +281,22 @@ def bench_loader(args, lines) -> None:
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "pitch_shift_bench.txt"))
+    ap.add_argument("--out", default=None, help="profiles/pitch_shift_bench.txt, or profiles/pitch_lock_bench.txt for --steps lock")
+    ap.add_argument("--parent-lib", default=None, help="another build of libcough_amd_pitch.so for the lock step's third side")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--loader-repeats", type=int, default=7)
     ap.add_argument("--rows", type=int, default=4096)
     ap.add_argument("--clips", type=int, default=512)
-    ap.add_argument("--steps", nargs="+", default=["kernel", "loader"], choices=["kernel", "loader"])
+    ap.add_argument("--steps", nargs="+", default=["kernel", "loader"], choices=["kernel", "loader", "lock"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_pitch.py needs the MI355X; there is no CPU fallback")
     bound_torch_threads()
     lines = [f"pitch shift: the per-row float64 phase vocoder and the resampler behind it; {torch.cuda.get_device_name(0)}"]
-    for step, fn in (("kernel", bench_kernel), ("loader", bench_loader)):
+    if args.out is None:
+        args.out = os.path.join("profiles", "pitch_lock_bench.txt" if args.steps == ["lock"] else "pitch_shift_bench.txt")
+    for step, fn in (("kernel", bench_kernel), ("loader", bench_loader), ("lock", bench_lock)):
         if step in args.steps:
             fn(args, lines)
     text = "\n".join(lines) + "\n"
