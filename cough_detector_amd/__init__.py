@@ -10,7 +10,7 @@ from .augmentation import AudioAugmentor, MixUp, SpecAugment, create_augmentatio
 from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, create_trainer, train_epoch
 from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, load_checkpoint, save_checkpoint,
                    train_epoch_async, validate)
-from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders
+from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders, prepare_dataset_split, stratified_split
 from .draws import augment_rows_drawn, draw_batch
 from .warp import draw_speed, speed_rate_pair, warp_rows
 from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
@@ -25,7 +25,7 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "ResidualTrainer", "SmallTrainer", "StandardTrainer", "create_trainer", "HipAdamW", "train_epoch",
            "EpochMeter", "EarlyStopping", "train_epoch_async", "validate", "save_checkpoint", "load_checkpoint",
            "class_weights_from_counts", "fit", "DeviceClipBank", "DeviceDataLoader", "create_data_loaders",
-           "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
+           "prepare_dataset_split", "stratified_split", "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
            "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report",
            "draw_batch", "augment_rows_drawn", "warp_rows", "draw_speed", "speed_rate_pair",
            "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length"]

@@ -11,6 +11,10 @@
   (``include/cough_amd_data.h``).
 * ``create_data_loaders`` (:368-418): the ``WeightedRandomSampler`` / ``drop_last=True`` training loader and the
   sequential validation loader.
+* ``stratified_split`` / ``prepare_dataset_split`` (:421-483): the stratified 80 / 20 split of a directory's clips, the
+  indices scikit-learn's ``train_test_split`` gives, drawn in numpy.  ``DeviceClipBank.from_esc50`` / ``esc50_rows``:
+  ``ESC50Dataset`` (:176-264); ``DeviceClipBank.concat``: ``CombinedDataset`` (:299-330).  Host bookkeeping around the
+  bank; ``cough_detector_amd/train.py`` assembles them.
 
 The random draws are the reference's, in the order a ``num_workers=0`` loader makes them: the sampler's indices for the
 epoch, then item by item in batch order the augmentor's draws for that clip's length, its ``torch.randn`` when the
@@ -48,6 +52,8 @@ stretch plans or in the table ``cough_draw_pitch`` reads, and changes neither th
 """
 from __future__ import annotations
 
+import csv
+import math
 import random
 import warnings
 from pathlib import Path
@@ -67,6 +73,93 @@ from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_b
 
 CLASSES = ["non_cough", "cough"]
 _AUDIO_EXTENSIONS = {".wav", ".mp3", ".flac", ".ogg", ".webm"}      # dataset.py:86
+ESC50_COUGH_CLASS = 24                                              # "coughing" (dataset.py:185)
+ESC50_NEGATIVE_CLASSES = (20, 21, 22, 23, 25, 26, 38)               # the sounds closest to a cough (dataset.py:188-196)
+
+
+def _approximate_mode(counts: np.ndarray, n_draws: int, rng: np.random.RandomState) -> np.ndarray:
+    """How many of ``n_draws`` each class gets: the floor of its proportional share, the remainder handed out by
+    descending fractional part, ties broken by ``rng.choice(..., replace=False)`` (one call per distinct fraction)."""
+    share = counts / counts.sum() * n_draws
+    taken = np.floor(share)
+    left = int(n_draws - taken.sum())
+    if left > 0:
+        frac = share - taken
+        for value in np.unique(frac)[::-1]:
+            inds, = np.where(frac == value)
+            k = min(len(inds), left)
+            taken[rng.choice(inds, size=k, replace=False)] += 1
+            left -= k
+            if left == 0:
+                break
+    return taken.astype(int)
+
+
+def stratified_split(labels: Sequence[int], val_split: float = 0.2, random_state: int = 42) -> Tuple[List[int], List[int]]:
+    """``(train_idx, val_idx)`` of ``sklearn.model_selection.train_test_split(range(n), test_size=val_split,
+    random_state=random_state, stratify=labels)`` (dataset.py:454-459), index for index and in its order, in numpy:
+    ``ceil(val_split * n)`` clips go to validation; each class is allotted its share of both sides (``_approximate_mode``,
+    training first, then validation from what the class has left), permuted, and cut; both lists are permuted once
+    more.  All draws come from one ``np.random.RandomState(random_state)``.  Inputs that scikit-learn refuses raise
+    ``ValueError``: a ``val_split`` outside (0, 1), a class with a single member, a side smaller than the number of
+    classes."""
+    y = np.asarray(labels.tolist() if isinstance(labels, torch.Tensor) else labels)
+    if y.ndim != 1:
+        raise ValueError(f"stratified_split: labels must be one-dimensional, got shape {y.shape}")
+    n = int(y.shape[0])
+    if isinstance(val_split, bool) or not isinstance(val_split, (float, np.floating)) or not 0.0 < val_split < 1.0:
+        raise ValueError(f"stratified_split: val_split={val_split!r} must be a float in the (0, 1) range")
+    n_test = int(math.ceil(val_split * n))
+    n_train = n - n_test
+    if n_train <= 0:
+        raise ValueError(f"stratified_split: with {n} clip(s) and val_split={val_split} the training side is empty")
+    classes, y_idx = np.unique(y, return_inverse=True)
+    counts = np.bincount(y_idx)
+    if counts.min() < 2:
+        raise ValueError(f"stratified_split: class {classes[int(counts.argmin())]!r} has a single member; a stratified "
+                         "split needs at least 2 of every class")
+    for side, size in (("training", n_train), ("validation", n_test)):
+        if size < len(classes):
+            raise ValueError(f"stratified_split: the {side} side would hold {size} clip(s) for {len(classes)} classes; "
+                             "it needs at least one per class")
+    by_class = np.split(np.argsort(y_idx, kind="mergesort"), np.cumsum(counts)[:-1])
+    rng = np.random.RandomState(random_state)
+    n_i = _approximate_mode(counts, n_train, rng)
+    t_i = _approximate_mode(counts - n_i, n_test, rng)
+    train, test = [], []
+    for c, members in enumerate(by_class):
+        members = members[rng.permutation(int(counts[c]))]
+        train.extend(members[:n_i[c]])
+        test.extend(members[n_i[c]:n_i[c] + t_i[c]])
+    train = rng.permutation(np.asarray(train, dtype=np.int64))
+    test = rng.permutation(np.asarray(test, dtype=np.int64))
+    return [int(i) for i in train], [int(i) for i in test]
+
+
+def esc50_rows(csv_path, is_training: bool = True, fold: Optional[int] = None,
+               include_all_negatives: bool = True) -> List[Tuple[str, int]]:
+    """``[(filename, label)]`` of ``ESC50Dataset`` (dataset.py:227-264) from ``meta/esc50.csv``, in csv order: with
+    ``fold`` set, training keeps the rows of the other folds and validation the rows of that fold; rows whose
+    ``audio/<filename>`` (beside ``meta/``) does not exist are skipped; target 24 ("coughing") is labelled 1, any other
+    target 0 when ``include_all_negatives`` is set or the target is one of ``ESC50_NEGATIVE_CLASSES``, else dropped."""
+    csv_path = Path(csv_path)
+    if not csv_path.exists():
+        raise FileNotFoundError(f"ESC-50 metadata not found at {csv_path}; nothing here downloads it: put a checkout of "
+                                "ESC-50 (meta/esc50.csv, audio/*.wav) there or pass its directory as esc50_dir")
+    audio_dir = csv_path.parent.parent / "audio"
+    rows = []
+    with open(csv_path, newline="") as f:
+        for row in csv.DictReader(f):
+            if fold is not None and (int(row["fold"]) != int(fold)) != bool(is_training):
+                continue
+            if not (audio_dir / row["filename"]).exists():
+                continue
+            target = int(row["target"])
+            if target == ESC50_COUGH_CLASS:
+                rows.append((row["filename"], 1))
+            elif include_all_negatives or target in ESC50_NEGATIVE_CLASSES:
+                rows.append((row["filename"], 0))
+    return rows
 
 
 def _upload(dev: torch.device, i64: np.ndarray, i32: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -239,6 +332,55 @@ class DeviceClipBank:
             warnings.warn(f"DeviceClipBank: skipped {skipped} audio file(s) that are not WAVE files; this build decodes "
                           "WAVE only", stacklevel=2)
         return cls(waveforms, labels, device=device)
+
+    @classmethod
+    def concat(cls, banks: Sequence["DeviceClipBank"]) -> "DeviceClipBank":
+        """What ``CombinedDataset`` (dataset.py:299-330) is to its datasets: one bank of the clips of ``banks``, bank
+        after bank in their order, packed with one ``torch.cat`` where the banks live (no host round trip).  The banks
+        share a device; no banks give an empty bank on the default device."""
+        banks = list(banks)
+        if not banks:
+            return cls([], [])
+        devices = {b.data.device for b in banks}
+        if len(devices) != 1:
+            raise ValueError(f"DeviceClipBank.concat: the banks live on {sorted(str(d) for d in devices)}; they must "
+                             "share one device")
+        out = object.__new__(cls)
+        out.device = banks[0].device
+        out._set(torch.cat([b.data for b in banks]), [n for b in banks for n in b.lengths.tolist()],
+                 [v for b in banks for v in b.labels.tolist()])
+        return out
+
+    @classmethod
+    def from_esc50(cls, data_dir: str, preprocessor, is_training: bool = True, fold: Optional[int] = None,
+                   include_all_negatives: bool = True, device=None) -> "DeviceClipBank":
+        """The clips ``ESC50Dataset`` collects (dataset.py:176-264) from an ESC-50 checkout at ``data_dir``: the rows
+        ``esc50_rows(data_dir/meta/esc50.csv, is_training, fold, include_all_negatives)`` in csv order, each
+        ``audio/<filename>`` read with ``preprocessor.load_audio``, ``resample`` (ESC-50 is 44.1 kHz: ``cough_resample``)
+        and ``to_mono``.  ``download_esc50`` has no counterpart: a missing csv raises ``FileNotFoundError`` that says
+        where the checkout belongs."""
+        root = Path(data_dir)
+        waveforms, labels = [], []
+        for filename, label in esc50_rows(root / "meta" / "esc50.csv", is_training, fold, include_all_negatives):
+            waveform, sr = preprocessor.load_audio(str(root / "audio" / filename))
+            waveforms.append(preprocessor.to_mono(preprocessor.resample(waveform, sr)).cpu())
+            labels.append(label)
+        return cls(waveforms, labels, device=device)
+
+
+def prepare_dataset_split(data_dir_or_bank, preprocessor=None, val_split: float = 0.2, random_state: int = 42,
+                          device=None) -> Tuple[DeviceClipBank, DeviceClipBank]:
+    """``(train_bank, val_bank)`` as the reference's ``prepare_dataset_split`` (dataset.py:421-483): the clips of a
+    directory (``DeviceClipBank.from_directory(data_dir, preprocessor, device)``) or of a bank that exists already,
+    split by ``stratified_split(bank.labels, val_split, random_state)``.  The augmentors are not arguments: they belong
+    to the loader (``create_data_loaders``), not to the bank."""
+    bank = data_dir_or_bank
+    if not isinstance(bank, DeviceClipBank):
+        if preprocessor is None:
+            raise ValueError("prepare_dataset_split: reading a directory needs a preprocessor")
+        bank = DeviceClipBank.from_directory(str(bank), preprocessor, device=device)
+    train_idx, val_idx = stratified_split(bank.labels, val_split=val_split, random_state=random_state)
+    return bank.subset(train_idx), bank.subset(val_idx)
 
 
 class BatchPlan:
