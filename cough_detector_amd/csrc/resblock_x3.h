@@ -9,14 +9,22 @@
 //
 // One 4-wave workgroup = G clips.  A workgroup takes <= 80 KB of LDS, so that at least TWO share a CU and one's staging /
 // epilogue overlaps the other's MFMA phases, for block 0 up to 24 rows (images of up to 98 rows; the shipped 22 rows:
-// 73 KB) and block 1 at every height but 12 rows (the shipped 11x13, two clips: 81 440 B); block 0 at 26 / 27 rows
-// (87 / 89 KB) and block 1 at 12 rows (88 KB, two clips) run one workgroup per CU.
-//   * x is staged once into two un-bordered LDS planes (hi, lo).  A plane is chunk-planar -- [8-channel chunk][pixel]
-//     of 16-byte cells -- and its pixels are stored parity-split (even / odd image rows x even / odd columns, each
-//     sub-image with the row pitch of the OUTPUT image), so the output pixels of a tile read, for any tap of the
-//     stride-2 conv1 as for the stride-1 conv2 over h, CONSECUTIVE cells of one chunk plane, and a tap's address is
-//     the tile's base + a compile-time constant.  Taps outside the image read zero cells kept in the planes (no
-//     border, no predicated fragments).
+// 78 368 B) and block 1 at every height but 12 rows (the shipped 11x13, two clips: 81 440 B); block 0 at 26 / 27 rows
+// (91 / 89 KB) and block 1 at 12 rows (88 KB, two clips) run one workgroup per CU.
+//   * x is staged once into two LDS planes (hi, lo).  A plane is chunk-planar -- [8-channel chunk][pixel] of 16-byte
+//     cells -- and its pixels are stored parity-split (even / odd image rows x even / odd columns, each sub-image with
+//     the row pitch of the OUTPUT image), so the output pixels of a tile read, for any tap of the stride-2 conv1 as
+//     for the stride-1 conv2 over h, CONSECUTIVE cells of one chunk plane, and a tap's address is the tile's base + a
+//     compile-time constant.  No fragment is predicated; where a tap outside the image finds its zeros is a property of
+//     the instantiation (resnet_plan.h: rbx_layout, rbx_border_x):
+//       - bordered x planes (the 16x16x32 body of block 0 at 16, 17, 22 and 26 rows, where the LDS bound leaves room):
+//         the zeros lie where those taps point -- the unused column of the odd-column sub-images of the odd-width image
+//         and short zero runs in front of / behind the sub-images -- so conv1 and the projection read base + immediate
+//         and nothing else (no tap mask, no select);
+//       - everywhere else (block 0 at 23 / 24 rows and its 32x32x16 body, block 1, and h for conv2 in every body) the
+//         planes carry no border: a per-tap select redirects such a tap to zero cells kept beside the planes.  h
+//         stays so on purpose: a bordered h (row pitch OW + 1) puts two lanes of every ds_read_b128 lane group of
+//         conv2 on one bank, and the LDS cycles that costs outweigh the selects (profiles/r10_block_borders.txt).
 //   * conv1 (3x3 s2) accumulates into acc1; the 1x1 s2 projection of x then opens conv2's accumulator acc2, so x is
 //     dead afterwards and h = ReLU(conv1 + b1) is written (split) OVER the x planes; conv2 (3x3 s1) runs out of h.
 //   * MFMA operands are swapped (weights = A): a lane owns one pixel x 4 consecutive channels per accumulator quad,
@@ -27,8 +35,9 @@
 //         2 clips x 42 pixels = 6 tiles; no partial-tile code path), so CT (hi, lo) weight pairs per k32-step feed all
 //         the tiles.  Activation fragments are fetched P tiles ahead.  A fragment read puts lanes 16c..16c+15 in chunk
 //         plane c (+ 4 for block 1's second k32-step of a conv1 tap); planes are laid out so that the ds_read_b128
-//         lane groups cover all 16 cell residues mod 16, and zeros come from rows of 16 cells read at the residue of
-//         the lane's in-image cell, so border reads are bank-conflict-free too (RbxCfg).
+//         lane groups cover all 16 cell residues mod 16; border reads are bank-conflict-free too: in bordered planes
+//         they are reads like any other, elsewhere the zeros come from rows of 16 cells read at the residue of the
+//         lane's in-image cell (RbxCfg).
 //       - block 0 at 27 rows: v_mfma_f32_32x32x16_bf16; wave (mg, ng) owns up to MW 32-pixel tiles x one 32-channel
 //         tile; activation fragments are fetched one k-step ahead.  The 32 lanes of a chunk read 32 consecutive cells,
 //         conflict-free at any plane alignment.
@@ -39,7 +48,7 @@
 
 #include "common.h"
 #include "nn_common.h"
-#include "resnet_plan.h"   // rbx_t16: which body a block runs
+#include "resnet_plan.h"   // rbx_t16: which body a block runs; rbx_layout: where its pixels and zeros live in LDS
 
 namespace cough {
 namespace {
@@ -94,22 +103,30 @@ struct RbxCfg {
                   "T16: one or two 16-channel tiles per wave, one or two k32-steps per conv1 tap, at most one 16-pixel "
                   "tile straddling two clips");
     static constexpr int CHI = CIN / 8, CHO = COUT / 8;
+    // ---- the LDS layout: resnet_plan.h (rbx_layout) holds the arithmetic and the description of the planes ----
+    static constexpr RbxGeo L = rbx_geo(CIN, COUT, G, XH, XW);
+    static_assert(L.t16 == T16 && L.m == M && L.np == NP && L.chi == CHI && L.cho == CHO, "rbx_layout describes this instantiation");
     // x planes: parity-split pixel order.  Sub-image (row parity a, column parity b) holds pixels (2i + a, 2j + b) at
     // i * OW + j; RE / RO = number of even / odd rows; the odd-column sub-images of an odd XW carry one unused column.
-    static constexpr int RE = (XH + 1) / 2, RO = XH / 2;
-    static constexpr int NPP = 2 * XH * OW;                                  // cells of one clip in one chunk plane
-    static constexpr int PB01 = RE * OW, PB10 = 2 * RE * OW, PB11 = 2 * RE * OW + RO * OW;   // sub-image bases (PB00 = 0)
+    // BX: bordered x planes (rbx_border_x) -- the zeros lie where conv1's taps outside the image point, and a tap's
+    // address is the tile's base + a compile-time offset; else a tap outside the image is redirected to a zero cell.
+    static constexpr bool BX = L.border_x;
+    static constexpr int RE = L.re, RO = L.ro;
+    static constexpr int NPP = L.npp;                                        // cells of one clip in one chunk plane
+    static constexpr int PB01 = L.b01, PB10 = L.b10, PB11 = L.b11;           // sub-image bases (PB00 = 0)
+    static constexpr int NZX = BX ? rbx_x_nzero(RE, RO, OW) : 0;             // bordered x: zero cells of a chunk plane
     // x cells between the starts of two clips in a chunk plane.  T16 with two clips: NPP rounded so that NPPC - PER is
     // a multiple of 16, and the 16 pixels of a tile that straddles the clips still read 16 distinct residues mod 16.
-    static constexpr int NPPC = T16 && G > 1 ? PER + (NPP - PER + 15) / 16 * 16 : NPP;
+    static constexpr int NPPC = L.nppc;
     // Bytes of one x / h chunk plane and the zero cells that taps outside the image read.  32x32x16 body: one zero cell
     // at the end of each chunk plane (byte offset ZX / ZH inside the plane).
     // T16: a ds_read_b128 lane group (MI355X: lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same in the upper
     // half) takes complementary pixels from chunk planes (lane >> 4) = 0 and 1 (2 and 3), so planes read by lanes 16
-    // apart must lie a multiple of 256 B apart; zeros come from 256-B-aligned rows of 16 cells, and a lane whose tap
-    // lies outside the image reads the zero cell with the bank residue of its in-image cell.
-    //   x, CIN = 32 (conv1 and the projection read chunk plane lane >> 4 only): planes padded to 256 B, one zero row after
-    //     the four.
+    // apart must lie a multiple of 256 B apart; where a select supplies the zeros they come from 256-B-aligned rows of 16
+    // cells, and a lane whose tap lies outside the image reads the zero cell with the bank residue of its in-image cell.
+    //   x, CIN = 32 (conv1 and the projection read chunk plane lane >> 4 only): planes padded to 256 B; un-bordered, one
+    //     zero row after the four; bordered, the zeros are cells of the planes and a border read is as conflict-free as
+    //     any other (16 consecutive cells of one chunk plane per 16 lanes).
     //   x, CIN = 64: a tap's second k32-step reads plane 4 + (lane >> 4) at the immediate offset KX.  Planes are padded to
     //     64 B only (so that four of them span a multiple of 256 B), in the order
     //       [zero row][x0][x2][zero row][x4][x6][x1][x3][256 B unused][x5][x7],
@@ -118,27 +135,29 @@ struct RbxCfg {
     //     11x13 past 80 KB, and one workgroup per CU.
     //   h: planes padded to 256 B, one zero row at the end of each (conv2's k32-step c of a tap reads chunk plane
     //     4c + (lane >> 4) at an immediate offset).
-    static constexpr int ZC = T16 ? 16 : 1;
-    static constexpr int CPX = !T16 ? (G * NPP + 1) * 16 : CHI == 4 ? (G * NPPC * 16 + 255) / 256 * 256 : (G * NPPC * 16 + 63) / 64 * 64;
-    static constexpr int xoff(int c) {   // byte offset of x chunk plane c
-        if (!T16 || CHI == 4) return c * CPX;
-        const int s = (c & 1) * 4 + (c >> 1);
-        return 256 + s * CPX + (s >= 2 ? 256 : 0) + (s >= 6 ? 256 : 0);
-    }
-    static constexpr int ZX = !T16 ? G * NPP * 16 : CHI == 4 ? 4 * CPX : 0;
-    static constexpr int KX = T16 && CHI == 8 ? xoff(4) - xoff(0) : 0;
-    static constexpr int ZH = T16 ? (M * 16 + 255) / 256 * 256 : M * 16;
-    static constexpr int CPH = ZH + ZC * 16;
-    static constexpr int XBYTES = !T16 ? CHI * CPX : CHI == 4 ? 4 * CPX + 256 : xoff(7) + CPX, HBYTES = CHO * CPH;
-    static_assert(!T16 || (ZX % 256 == 0 && CPH % 256 == 0 && (G == 1 || (NPPC - PER) % 16 == 0)), "T16 bank residues");
+    static constexpr int ZC = L.zc;
+    static constexpr int CPX = L.cpx;
+    static constexpr int xoff(int c) { return rbx_xoff(T16, CHI, CPX, c); }   // byte offset of x chunk plane c
+    static constexpr int ZX = L.zx;
+    static constexpr int KX = L.kx;
+    static constexpr int ZH = L.zh;
+    static constexpr int CPH = L.cph;
+    static constexpr int XBYTES = L.xbytes, HBYTES = L.hbytes;
+    static_assert(!T16 || ((BX || ZX % 256 == 0) && CPX % (CHI == 4 ? 256 : 64) == 0 && CPH % 256 == 0 && (G == 1 || (NPPC - PER) % 16 == 0)),
+                  "T16 bank residues");
     static_assert(!T16 || CHI == 4 || ((xoff(1) - xoff(0)) % 256 == 0 && (xoff(3) - xoff(2)) % 256 == 0 &&
                                        xoff(5) - xoff(1) == KX && xoff(6) - xoff(2) == KX && xoff(7) - xoff(3) == KX &&
                                        xoff(0) >= ZX + 256 && xoff(2) + CPX <= ZX + KX && xoff(4) >= ZX + KX + 256),
                   "T16 x layout, CIN = 64");
-    static constexpr int PL = (((XBYTES > HBYTES ? XBYTES : HBYTES) + 255) / 256) * 256;   // pitch between the hi and lo planes
-    static constexpr int BIAS = 2 * PL;                                      // b1[COUT], b2[COUT] f32
-    static constexpr int HRED = BIAS + 2 * COUT * 4;                         // head reduction scratch [WAVES][2] f32
-    static constexpr int LDS = HRED + WAVES * 2 * 4;
+    // bordered x: four 256-B-padded chunk planes of one clip, odd XW; the largest cell any lane can form -- the last
+    // tile's padding rows at tap (2, 2) included -- lies inside its chunk plane
+    static_assert(!BX || (T16 && CHI == 4 && G == 1 && XW % 2 == 1 && (16 * NP - 1 + PB11 + 1) * 16 <= CPX &&
+                          PB11 + RO * OW + (RE > RO ? OW : 0) <= NPP && PB01 % 8 >= 2 && (PB11 - PB10) % 8 >= 2),
+                  "bordered x planes");
+    static constexpr int PL = L.pl;                                          // pitch between the hi and lo planes
+    static constexpr int BIAS = L.bias;                                      // b1[COUT], b2[COUT] f32
+    static constexpr int HRED = L.hred;                                      // head reduction scratch [WAVES][2] f32
+    static constexpr int LDS = L.lds;
     static constexpr int OP = COUT + 4;                                      // floats per row of the f32 output tile
     static_assert(T16 || (WAVES % NT == 0 && MG * MW * 32 >= M), "tile split");
     static_assert(OW == (XW + 1) / 2, "sub-image row pitch");
@@ -209,7 +228,16 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         constexpr int NB = UN <= Cfg::STAGE_MAX ? 1 : 2, UNB = (UN + NB - 1) / NB;
         const int valid = nvalid * NPX * QP;
         const float4* src = reinterpret_cast<const float4*>(a.x + (long long)clip0 * NPX * CIN);
-        if constexpr (T16) {
+        if constexpr (Cfg::BX) {
+            // the zero cells of every chunk plane, hi and lo: the unused column of the odd-column sub-images and the
+            // runs in front of / behind the sub-images (rbx_x_zero)
+            constexpr int NZX = Cfg::NZX;
+            for (int z = tid; z < 2 * CHI * NZX; z += THREADS) {
+                const int pl = z / NZX;
+                const int cell = rbx_x_zero(Cfg::PB01, Cfg::PB10, Cfg::PB11, OW, Cfg::RE, Cfg::RO, z % NZX);
+                *reinterpret_cast<uint4*>(smem + (pl / CHI) * PL + Cfg::xoff(pl % CHI) + cell * 16) = make_uint4(0, 0, 0, 0);
+            }
+        } else if constexpr (T16) {
             constexpr int NZ = CHI / 4;   // the zero rows (one per k32-step of a tap), hi and lo
             if (tid < 2 * NZ * ZC) {
                 const int k = tid / ZC;
@@ -234,8 +262,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 if (i < NPIECE) {
                     const int P = i / QP, q = i % QP;                      // raster pixel (clip, row, column), quarter-chunk
                     const int g = P / NPX, rem = P % NPX, ih = rem / XW, iw = rem % XW;
-                    const int cell = g * NPPC + ((ih & 1) ? ((iw & 1) ? Cfg::PB11 : Cfg::PB10) : ((iw & 1) ? Cfg::PB01 : 0)) +
-                                     (ih >> 1) * OW + (iw >> 1);
+                    const int cell = RBX_X_CELL(g * NPPC, Cfg::PB01, Cfg::PB10, Cfg::PB11, OW, ih, iw);
                     uint2 hi, lo;
                     if (i >= valid) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);   // clips beyond the batch read as zeros
                     split4(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
@@ -259,12 +286,8 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         if (a.fcw != nullptr && a.nanflag != nullptr && (tid & 127) == 0 && (tid >> 7) < nvalid) nan_clip = a.nanflag[clip0 + (tid >> 7)];
     }
 
-    // cell offset of conv1 tap (kh, kw) from cell (oh, ow) of sub-image (0, 0): input (2oh - 1 + kh, 2ow - 1 + kw) lies in
-    // the sub-image of parities ((kh + 1) & 1, (kw + 1) & 1) at (oh - [kh == 0], ow - [kw == 0])
-    auto tapx = [](int kh, int kw) constexpr -> int {
-        const int a = (kh + 1) & 1, b = (kw + 1) & 1;
-        return (a ? (b ? Cfg::PB11 : Cfg::PB10) : (b ? Cfg::PB01 : 0)) - (kh == 0 ? Cfg::OW : 0) - (kw == 0 ? 1 : 0);
-    };
+    // cell offset of conv1 tap (kh, kw) from cell (oh, ow) of sub-image (0, 0) (rbx_x_tap)
+    auto tapx = [](int kh, int kw) constexpr -> int { return rbx_x_tap(Cfg::PB01, Cfg::PB10, Cfg::PB11, Cfg::OW, kh, kw); };
 
     constexpr int NT = Cfg::NT, MW = Cfg::MW, KS1 = Cfg::KS1, KSP = Cfg::KSP, KS = Cfg::KS, D = DW;
     const int r = lane & 31, h = lane >> 5, ng = wave % NT, mg = wave / NT;
@@ -298,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         for (int tap = 0; tap < 9; ++tap) {
             const int kh = tap / 3, kw = tap % 3;
             const int ih = 2 * oh - 1 + kh, iw = 2 * ow - 1 + kw, jh = oh - 1 + kh, jw = ow - 1 + kw;
-            if (unsigned(ih) < unsigned(XH) && unsigned(iw) < unsigned(XW)) m |= 1u << tap;
+            if (!Cfg::BX && unsigned(ih) < unsigned(XH) && unsigned(iw) < unsigned(XW)) m |= 1u << tap;   // bordered x: no select
             if (unsigned(jh) < unsigned(OH) && unsigned(jw) < unsigned(OW)) m |= 1u << (9 + tap);
         }
         vm[t] = R < M ? m : 0u;   // a padding row reads the zero cell at every tap
@@ -338,7 +361,10 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
             constexpr int kt = (conv1 ? q : proj ? q - KQ1 : q - KQ1 - KQP) * 32;   // k inside this operand
             constexpr int C = (conv1 || proj) ? CIN : COUT;
             constexpr int tap = proj ? 4 : kt / C, c32 = (kt % C) / 32, kh = tap / 3, kw = tap % 3;
-            if constexpr (c32 == 0) {
+            if constexpr (Cfg::BX && (conv1 || proj)) {
+                // bordered x (one clip, one k32-step per tap): the lane's base + an immediate, inside or outside the image
+                return smem + lbx + (256 * t + 16 * tapx(kh, kw));
+            } else if constexpr (c32 == 0) {
                 if constexpr (conv1 || proj) {
                     constexpr bool strad = G > 1 && 16 * t < PER && 16 * t + 16 > PER;
                     constexpr int off = 256 * t + (G > 1 && 16 * t >= PER ? DX : 0) + 16 * tapx(kh, kw);

@@ -1,7 +1,7 @@
 // What a CoughDetectorResidual forward runs for an (H, W) feature image: plan_resnet alone decides it, in plain host
 // C++17 (no HIP header: tests/resnet_plan_dump.cpp builds this file with a host compiler and prints the plans).
 // resnet.hip executes the plan (run_plan) and instantiates the kernels the tables below name; resblock_x3.h takes its
-// body choice (rbx_t16) from here.  Every number the decision rests on is defined in this file and nowhere else.
+// body choice (rbx_t16) and its LDS layout (rbx_layout) from here.  Every number the decision rests on is defined in this file and nowhere else.
 #pragma once
 #include <cstddef>
 
@@ -77,6 +77,137 @@ constexpr bool rbx_t16_shape(int cin, int cout) { return (cin == 32 && cout == 6
 constexpr bool rbx_t16(int cin, int cout, int xh) {
     return rbx_t16_shape(cin, cout) && (cin == 64 || xh <= 26);
 }
+
+// ------------------------------------------------------------------------------------------------ split-bf16 blocks: LDS layout
+// Everything resblock_x3_kernel<CIN, COUT, G, XH, XW> knows about where a pixel lives in LDS (RbxCfg takes its values from
+// rbx_layout; tests/rbx_layout_check.cpp enumerates the same functions on the host).  A plane (hi or lo) holds CIN / 8
+// (x) or COUT / 8 (h) chunk planes of 16-byte cells; the x pixels of a clip are stored parity-split: sub-image (row parity
+// a, column parity b) holds pixel (2i + a, 2j + b) at cell base(a, b) + i * OW + j.
+//   un-bordered x (every body but the one below): the four sub-images back to back; a tap outside the image is
+//     redirected to a zero cell by a per-tap select in the kernel.
+//   bordered x (rbx_border_x: the 16x16x32 body of block 0 where the workgroups-per-CU bound leaves room): the zeros lie
+//     where the taps outside the image point, so a tap is the tile's base + a compile-time offset and nothing else.  Such
+//     a tap leaves through an odd-row or an odd-column sub-image only.  XW is odd, so the odd-column sub-images carry one
+//     unused column j = OW - 1: zeroed, it is the right border (kw = 2 at ow = OW - 1) and, rows being contiguous, the
+//     left border of the next row (kw = 0 at ow = 0).  Zero runs in front of the sub-images give row -1 and cell -1 of
+//     the first row, and OW cells behind the odd-row sub-images give row RO of an odd XH:
+//       [even, even][0-2 unused][1][even, odd][OW][odd, even][OW + 1][odd, odd][OW if XH is odd][padding up to 16 NP cells past b11]
+//     (the OW + 1 run serves the (odd, even) sub-image's row RO and the (odd, odd) one's row -1 / cell -1; the unused
+//     cells keep the staging stores of two neighbouring pixels on different banks, see rbx_layout).  The padding
+//     rows of the last 16-pixel tile (R >= M) read whatever lies at their offsets: a pixel is one column of the MFMA's B
+//     operand and their accumulators are never stored, but every such cell lies inside the chunk plane.
+//   h: pixel R at cell R; zero rows of 16 cells (16x16x32 body) or one zero cell (32x32x16 body) at the end of each chunk plane.
+constexpr int RBX_LDS_2WG = 80 * 1024, RBX_LDS_CU = 160 * 1024;   // two workgroups / one workgroup per CU
+constexpr int rbx_up(int v, int a) { return (v + a - 1) / a * a; }
+
+struct RbxGeo {
+    int cin, cout, g, xh, xw;
+    bool t16, border_x;
+    int oh, ow, npx, per, m, np;   // output image, pixels of a clip (in / out), of a workgroup, 16-pixel tiles
+    int chi, cho, re, ro;          // chunk planes of x / h, even / odd rows of x
+    int b01, b10, b11;             // sub-image bases in a chunk plane (cells; b00 = 0)
+    int npp, nppc;                 // x cells of one clip in a chunk plane, cells between the starts of two clips
+    int zc, cpx, zx, kx;           // zero cells per zero row, bytes of an x chunk plane, byte offsets of the zero row(s)
+    int zh, cph;                   // byte offset of an h chunk plane's zero cells, bytes of an h chunk plane
+    int xbytes, hbytes, pl, bias, hred, lds;
+};
+
+// byte offset of x chunk plane c inside a plane (RbxCfg explains the order at CIN = 64)
+constexpr int rbx_xoff(bool t16, int chi, int cpx, int c) {
+    if (!t16 || chi == 4) return c * cpx;
+    const int s = (c & 1) * 4 + (c >> 1);
+    return 256 + s * cpx + (s >= 2 ? 256 : 0) + (s >= 6 ? 256 : 0);
+}
+
+constexpr RbxGeo rbx_layout(int cin, int cout, int g, int xh, int xw, bool border_x) {
+    RbxGeo L{};
+    L.cin = cin; L.cout = cout; L.g = g; L.xh = xh; L.xw = xw;
+    L.t16 = rbx_t16(cin, cout, xh);
+    L.border_x = border_x;
+    L.oh = (xh - 1) / 2 + 1; L.ow = (xw - 1) / 2 + 1;
+    L.npx = xh * xw; L.per = L.oh * L.ow; L.m = g * L.per; L.np = (L.m + 15) / 16;
+    L.chi = cin / 8; L.cho = cout / 8; L.re = (xh + 1) / 2; L.ro = xh / 2;
+    L.zc = L.t16 ? 16 : 1;
+    if (border_x) {   // 16x16x32 body, CIN = 32, one clip, odd XW
+        // The staging stores 8 bytes per lane, 16 lanes = two raster neighbours x 8 quarter-chunks to a bank group; the
+        // four chunk planes of a pixel share their banks, and so do the two pixels unless their cells differ mod 8: cells
+        // j and b01 + j (even, odd column), or b01 + j and j + 1.  Unused cells in front of the zero cell keep b01 mod 8
+        // off 0 and 1; b11 - b10 is off them at every compiled height (RbxCfg asserts it).
+        L.b01 = L.re * L.ow + 1;
+        while (L.b01 % 8 < 2) ++L.b01;
+        L.b10 = L.b01 + L.re * L.ow + L.ow;
+        L.b11 = L.b10 + L.ro * L.ow + L.ow + 1;
+        L.npp = L.nppc = L.b11 + 16 * L.np;
+        L.cpx = rbx_up(L.npp * 16, 256);
+        L.zx = 0; L.kx = 0;
+        L.xbytes = L.chi * L.cpx;
+    } else {
+        L.b01 = L.re * L.ow; L.b10 = 2 * L.re * L.ow; L.b11 = 2 * L.re * L.ow + L.ro * L.ow;
+        L.npp = 2 * xh * L.ow;
+        // 16x16x32 body with two clips: rounded so that nppc - per is a multiple of 16, and the 16 pixels of a tile that
+        // straddles the clips still read 16 distinct residues mod 16
+        L.nppc = L.t16 && g > 1 ? L.per + rbx_up(L.npp - L.per, 16) : L.npp;
+        L.cpx = !L.t16 ? (g * L.npp + 1) * 16 : L.chi == 4 ? rbx_up(g * L.nppc * 16, 256) : rbx_up(g * L.nppc * 16, 64);
+        L.zx = !L.t16 ? g * L.npp * 16 : L.chi == 4 ? 4 * L.cpx : 0;
+        L.kx = L.t16 && L.chi == 8 ? rbx_xoff(true, 8, L.cpx, 4) - rbx_xoff(true, 8, L.cpx, 0) : 0;
+        L.xbytes = !L.t16 ? L.chi * L.cpx : L.chi == 4 ? 4 * L.cpx + 256 : rbx_xoff(true, 8, L.cpx, 7) + L.cpx;
+    }
+    L.zh = L.t16 ? rbx_up(L.m * 16, 256) : L.m * 16;
+    L.cph = L.zh + L.zc * 16;
+    L.hbytes = L.cho * L.cph;
+    L.pl = rbx_up(L.xbytes > L.hbytes ? L.xbytes : L.hbytes, 256);   // pitch between the hi and lo planes
+    L.bias = 2 * L.pl;                                              // b1[COUT], b2[COUT] f32
+    L.hred = L.bias + 2 * cout * 4;                                  // head reduction scratch [4 waves][2] f32
+    L.lds = L.hred + 4 * 2 * 4;
+    return L;
+}
+
+// Bordered x planes for block blk at xh input rows?  Only block 0's 16x16x32 body (one clip, four chunk planes, odd XW);
+// and only where the bordered layout stays within the workgroups-per-CU bound the un-bordered one meets: 80 KB for two
+// workgroups, else one CU's 160 KB.  Block 0: 16, 17, 22 and 26 rows; 23 and 24 rows (82 464 / 84 512 B bordered) keep the
+// selects.  Block 1 (the shipped 11x13 with two clips: 81 440 of 81 920 B) keeps them at every height.
+constexpr bool rbx_border_x(int blk, int xh) {
+    if (blk != 0 || !rbx_t16(NET_CH[0], NET_CH[1], xh) || RBX_COLS[0] % 2 == 0) return false;
+    const int sel = rbx_layout(NET_CH[0], NET_CH[1], 1, xh, RBX_COLS[0], false).lds;
+    const int bor = rbx_layout(NET_CH[0], NET_CH[1], 1, xh, RBX_COLS[0], true).lds;
+    return bor <= (sel <= RBX_LDS_2WG ? RBX_LDS_2WG : RBX_LDS_CU);
+}
+constexpr RbxGeo rbx_geo(int cin, int cout, int g, int xh, int xw) {
+    const bool bx = cin == NET_CH[0] && cout == NET_CH[1] && g == 1 && xw == RBX_COLS[0] && rbx_border_x(0, xh);
+    return rbx_layout(cin, cout, g, xh, xw, bx);
+}
+
+// x cell of input pixel (ih, iw) of the clip whose cells start at `clip` in a chunk plane: what the staging writes.  The
+// kernel expands the macro in place: through a function call the same arithmetic reaches the optimiser in another form, and
+// the staging code of every instantiation comes out differently scheduled (block 1: + 1.7 % vector instructions).
+#define RBX_X_CELL(clip, b01, b10, b11, ow, ih, iw) \
+    ((clip) + (((ih) & 1) ? (((iw) & 1) ? (b11) : (b10)) : (((iw) & 1) ? (b01) : 0)) + ((ih) >> 1) * (ow) + ((iw) >> 1))
+constexpr int rbx_x_cell(int clip, int b01, int b10, int b11, int ow, int ih, int iw) { return RBX_X_CELL(clip, b01, b10, b11, ow, ih, iw); }
+// cell offset of conv1 tap (kh, kw) from cell (oh, ow) of sub-image (0, 0): input (2 oh - 1 + kh, 2 ow - 1 + kw) lies in the
+// sub-image of parities ((kh + 1) & 1, (kw + 1) & 1) at (oh - [kh == 0], ow - [kw == 0]).  The projection is tap (1, 1).
+constexpr int rbx_x_tap(int b01, int b10, int b11, int ow, int kh, int kw) {
+    const int a = (kh + 1) & 1, b = (kw + 1) & 1;
+    return (a ? (b ? b11 : b10) : (b ? b01 : 0)) - (kh == 0 ? ow : 0) - (kw == 0 ? 1 : 0);
+}
+// bordered x: the zero cells of a chunk plane, k = 0 .. rbx_x_nzero - 1 (the unused column of the two odd-column
+// sub-images, then the four runs)
+constexpr int rbx_x_nzero(int re, int ro, int ow) { return re + ro + 1 + ow + ow + 1 + (re > ro ? ow : 0); }
+constexpr int rbx_x_zero(int b01, int b10, int b11, int ow, int re, int ro, int k) {
+    if (k < re) return b01 + k * ow + ow - 1;
+    k -= re;
+    if (k < ro) return b11 + k * ow + ow - 1;
+    k -= ro;
+    if (k < 1) return b01 - 1;
+    k -= 1;
+    if (k < ow) return b10 - ow + k;
+    k -= ow;
+    if (k < ow + 1) return b10 + ro * ow + k;
+    k -= ow + 1;
+    return b11 + ro * ow + k;
+}
+// h: cell of output pixel R of the workgroup, cell offset of conv2 tap (kh, kw)
+constexpr int rbx_h_cell(int R) { return R; }
+constexpr int rbx_h_tap(int ow, int kh, int kw) { return (kh - 1) * ow + kw - 1; }
 
 // ------------------------------------------------------------------------------------------------ single-bf16 blocks
 constexpr size_t RB_LDS_LIMIT = 160 * 1024;   // one workgroup must fit a CU's LDS (set by hipFuncSetAttribute at create time)
