@@ -9,7 +9,8 @@ BatchNorm have a true gradient of 0 and are bounded, not compared.
 Well-posedness (test_gpu_train_shapes.py explains both effects for the residual net).  conv1's weight and bias are put
 on a 2^-6 grid and the input on a grid fine enough to keep the image (``_on_grid``), so every conv1 output is exact in
 f32 and f64 and the first max-pool's windows tie exactly or differ by far more than rounding.  ReLU inputs within
-rounding of 0 are taken from the kernel's side by ``resolve_kinks`` before the gradient rule is applied.  The golden
+rounding of 0 are taken from the kernel's side by ``resolve_kinks`` before the gradient rule is applied; the one case
+with a later pool's window within rounding of a tie takes that window the same way (``ties=True``).  The golden
 head (classifier.4) gives logits of +-300 on these images, where the CE terms saturate; it is scaled by 1/100 so that
 the logits stay within a few units (the golden-step test keeps the golden weights and the logits' bound for the loss).
 """
@@ -59,7 +60,7 @@ def _batch(b, h, w, seed):
     return x, y, mask
 
 
-def _check(sd, b, h, w, seed, upstream_rtol=None):
+def _check(sd, b, h, w, seed, upstream_rtol=None, ties=False):
     x, y, mask = _batch(b, h, w, seed)
     tr = SmallTrainer(_model(sd), class_weights=CW)
     loss, logits = tr.forward_backward(x.cuda(), y.cuda(), dropout_mask=mask.cuda())
@@ -67,7 +68,8 @@ def _check(sd, b, h, w, seed, upstream_rtol=None):
     ref = RefStep(sd, class_weights=CW)
     rloss, rlogits, rg = ref.grads(x, y, mask, 0.3)
     g = {n: p.grad.detach().cpu().double() for n, p in tr.model.named_parameters()}
-    rg, kept = resolve_kinks(g, ref, rg)
+    rg, kept = resolve_kinks(g, ref, rg, ties=ties)
+    print(f"choices taken from the kernel's side: {kept}")
     # a BN over 2 values keeps only eps / (var + eps) of the size of dy (test_gpu_train_shapes.py): one f32 rounding
     # there is 2^-24 (var + eps) / eps of the result
     rule = 1e-4
@@ -83,11 +85,11 @@ def _check(sd, b, h, w, seed, upstream_rtol=None):
 @pytest.mark.parametrize("b,h,w", [(8, 90, 101), (64, 103, 101), (256, 64, 101), (5, 37, 29), (3, 8, 8), (2, 8, 8),
                                    (1, 16, 8), (1, 8, 16), (17, 15, 23), (1, 90, 101)])
 def test_step_matches_the_restatement(qsd, b, h, w):
-    # seed b * 7 + h + w at (64, 103, 101) draws a batch where one discrete choice (a max-pool window after a pw conv, or a
-    # ReLU input, within f32 rounding of a tie) falls the other way in float64: measured, this kernel and torch's own
-    # float32 step on the CPU agree (3.20e-3 and 3.20e-3 of conv1's weight gradient scale against float64, 1.2e-2 for
-    # features.10) and both differ from the restatement.  That draw is skipped over (+1), not the shape.
-    _check(qsd, b, h, w, seed=b * 7 + h + w + (1 if (b, h, w) == (64, 103, 101) else 0))
+    # seed b * 7 + h + w at (64, 103, 101) draws a batch where one window of the pool after features.11 has its top two
+    # values 3.6e-7 apart (relative): float64 and float32 route its gradient to different pixels, which moves
+    # features.10's weight gradient by 1.2e-2 of its scale (test_pool_ties_host.py).  That case takes the window from
+    # the kernel's side (ties=True); every other case resolves ReLU inputs only, as before.
+    _check(qsd, b, h, w, seed=b * 7 + h + w, ties=(b, h, w) == (64, 103, 101))
 
 
 def test_step_matches_the_restatement_at_1024_clips(qsd):

@@ -13,6 +13,8 @@ from typing import Dict, List
 import torch
 import torch.nn.functional as F
 
+import pool_ties_ref
+
 BNS = ["features.1", "features.6", "features.11", "features.16"]
 DWS = ["features.4", "features.9", "features.14"]
 PWS = ["features.5", "features.10", "features.15"]
@@ -74,16 +76,16 @@ class RefStep:
 
     def forward(self, x, mask, p):
         P = self.P
-        self.pre, self.flip, self.batch_var = {}, {}, {}
+        self.pre, self.flip, self.batch_var, self.pool_in, self.pick, self.pool_of = {}, {}, {}, {}, {}, {}
         h = F.conv2d(x, P["features.0.weight"], P["features.0.bias"], padding=1)
-        h = F.max_pool2d(self._relu(self._bn(h, BNS[0]), "stem"), 2)
+        h = pool_ties_ref.pool(self, self._relu(self._bn(h, BNS[0]), "stem"), "p0", relu="stem")
         for i in range(3):
             c = h.shape[1]
             h = F.conv2d(h, P[DWS[i] + ".weight"], P[DWS[i] + ".bias"], padding=1, groups=c)
             h = F.conv2d(h, P[PWS[i] + ".weight"], P[PWS[i] + ".bias"])
             h = self._relu(self._bn(h, BNS[i + 1]), f"b{i + 1}")
             if i < 2:
-                h = F.max_pool2d(h, 2)
+                h = pool_ties_ref.pool(self, h, f"p{i + 1}", relu=f"b{i + 1}")
         g = h.mean(dim=(2, 3))
         hid = self._relu(F.linear(g, P["classifier.1.weight"], P["classifier.1.bias"]), "fc")
         d = hid * (mask.to(self.dtype) * (1.0 / (1.0 - p))) if p < 1 else hid * 0.0
@@ -126,29 +128,28 @@ def _worst(g, rgrads):
                for n in PARAM_NAMES if n not in BN_FED_BIASES)
 
 
-def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4):
-    """train_ref.resolve_kinks for this network: ReLU inputs within ``kink`` of 0 are flipped one at a time on ``ref``
-    (after ``grads``) and kept where that brings the restatement closer to ``g``.  Returns (gradients, kept flips)."""
-    if _worst(g, rgrads) <= rtol:
-        return rgrads, []
-    cand = []
-    for name, v in ref.pre.items():
-        for idx in (v.abs() < kink).nonzero().tolist():
-            cand.append((abs(v[tuple(idx)].item()), name, tuple(idx)))
-    cand.sort()
-    kept, best = [], _worst(g, rgrads)
-    for _, name, idx in cand[:limit]:
-        ref.flip[name][idx] = True
-        trial = ref.regrad()
-        w = _worst(g, trial)
-        if w < best:
-            best, rgrads = w, trial
-            kept.append((name, idx, ref.pre[name][idx].item()))
-            if best <= rtol:
-                break
-        else:
-            ref.flip[name][idx] = False
-    return rgrads, kept
+def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4, ties=False):
+    """train_ref.resolve_kinks for this network (pool_ties_ref.resolve): ReLU inputs within ``kink`` of 0 are flipped
+    one at a time on ``ref`` (after ``grads``) and kept where that brings the restatement closer to ``g``.  With
+    ``ties`` the pool windows with a positive maximum whose top two values differ by less than ``kink`` of it are
+    candidates too (the runner-up takes the window), in one order of margin with the ReLU inputs; exact ties never are.
+    A last pass undoes every kept change that the others made unnecessary.  Returns (gradients, kept changes); the
+    gradients are ``rgrads`` itself when the plain comparison is within ``rtol``."""
+    return pool_ties_ref.resolve(g, ref, rgrads, _worst, kink=kink, limit=limit, rtol=rtol, ties=ties)
+
+
+def step_on_the_kernels_side(ref, g, x, y, mask, p, ties=False):
+    """``ref.step`` for a check against a float32 step whose unclipped gradients are ``g``: the same train_epoch
+    iteration, with the choices that are ambiguous in float32 (ReLU inputs within rounding of 0; with ``ties``,
+    near-tied pool windows) taken as that step took them (``resolve_kinks``), as train_std_ref's.  Returns ``step``'s tuple and
+    the kept changes."""
+    loss, logits, rg = ref.grads(x, y, mask, p)
+    rg, kept = resolve_kinks(g, ref, rg, ties=ties)
+    for n in PARAM_NAMES:
+        ref.P[n].grad = rg[n].clone()
+    norm = torch.nn.utils.clip_grad_norm_([ref.P[n] for n in PARAM_NAMES], max_norm=ref.max_norm)
+    ref.opt.step()
+    return loss, logits, rg, float(norm), kept
 
 
 def assert_step_matches(model, loss, logits, rloss, rlogits, rgrads, rsd, sd0, loss_on_logit_scale=False,

@@ -14,6 +14,8 @@ from typing import Dict, List
 import torch
 import torch.nn.functional as F
 
+import pool_ties_ref
+
 from train_ref import golden_index, golden_sample        # noqa: F401  (the golden's subsampling rule)
 from train_small_ref import _Relu
 
@@ -62,13 +64,13 @@ class RefStep:
 
     def forward(self, x, mask, p_block, p_fc):
         P = self.P
-        self.pre, self.flip, self.batch_var = {}, {}, {}
+        self.pre, self.flip, self.batch_var, self.pool_in, self.pick, self.pool_of = {}, {}, {}, {}, {}, {}
         mask = mask.to(self.dtype)
         h = x
         for i in range(4):
             c = f"conv_layers.{i}.conv"
             h = F.conv2d(h, P[c + ".weight"], P[c + ".bias"], padding=1)
-            h = F.max_pool2d(self._relu(self._bn(h, BNS[i]), f"b{i}"), 2)
+            h = pool_ties_ref.pool(self, self._relu(self._bn(h, BNS[i]), f"b{i}"), f"p{i}", relu=f"b{i}")
             keep = mask[:, MASK_OFF[i]:MASK_OFF[i + 1]]
             h = h * (keep * (1.0 / (1.0 - p_block)))[:, :, None, None] if p_block < 1 else h * 0.0
         g = h.mean(dim=(2, 3))
@@ -114,39 +116,24 @@ def _worst(g, rgrads):
                for n in PARAM_NAMES if n not in BN_FED_BIASES)
 
 
-def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4):
-    """train_small_ref.resolve_kinks for this network: ReLU inputs within ``kink`` of 0 are flipped one at a time on
-    ``ref`` (after ``grads``) and kept where that brings the restatement closer to ``g``.  Returns (gradients, flips)."""
-    if _worst(g, rgrads) <= rtol:
-        return rgrads, []
-    cand = []
-    for name, v in ref.pre.items():
-        for idx in (v.abs() < kink).nonzero().tolist():
-            cand.append((abs(v[tuple(idx)].item()), name, tuple(idx)))
-    cand.sort()
-    kept, best = [], _worst(g, rgrads)
-    for _, name, idx in cand[:limit]:
-        ref.flip[name][idx] = True
-        trial = ref.regrad()
-        w = _worst(g, trial)
-        if w < best:
-            best, rgrads = w, trial
-            kept.append((name, idx, ref.pre[name][idx].item()))
-            if best <= rtol:
-                break
-        else:
-            ref.flip[name][idx] = False
-    return rgrads, kept
+def resolve_kinks(g, ref, rgrads, kink=1e-6, limit=64, rtol=1e-4, ties=False):
+    """train_ref.resolve_kinks for this network (pool_ties_ref.resolve): ReLU inputs within ``kink`` of 0 are flipped
+    one at a time on ``ref`` (after ``grads``) and kept where that brings the restatement closer to ``g``.  With
+    ``ties`` the pool windows with a positive maximum whose top two values differ by less than ``kink`` of it are
+    candidates too (the runner-up takes the window), in one order of margin with the ReLU inputs; exact ties never are.
+    A last pass undoes every kept change that the others made unnecessary.  Returns (gradients, kept changes); the
+    gradients are ``rgrads`` itself when the plain comparison is within ``rtol``."""
+    return pool_ties_ref.resolve(g, ref, rgrads, _worst, kink=kink, limit=limit, rtol=rtol, ties=ties)
 
 
-def step_on_the_kernels_side(ref, g, x, y, mask, p_block, p_fc):
+def step_on_the_kernels_side(ref, g, x, y, mask, p_block, p_fc, ties=False):
     """``ref.step`` for a check against a float32 step whose unclipped gradients are ``g``: the same train_epoch
     iteration, with the ReLU derivatives that are ambiguous in float32 taken as that step took them (``resolve_kinks``,
     the rule of every single-step check here).  Without it a ReLU input within rounding of 0 moves a whole block's
-    gradients by 1e-2 of their scale, and with them the clip norm and every moment.  Returns ``step``'s tuple and the
-    kept flips."""
+    gradients by 1e-2 of their scale, and with them the clip norm and every moment.  ``ties``: near-tied pool windows
+    too.  Returns ``step``'s tuple and the kept changes."""
     loss, logits, rg = ref.grads(x, y, mask, p_block, p_fc)
-    rg, kept = resolve_kinks(g, ref, rg)
+    rg, kept = resolve_kinks(g, ref, rg, ties=ties)
     for n in PARAM_NAMES:
         ref.P[n].grad = rg[n].clone()
     norm = torch.nn.utils.clip_grad_norm_([ref.P[n] for n in PARAM_NAMES], max_norm=ref.max_norm)
