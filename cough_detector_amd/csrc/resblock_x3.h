@@ -22,7 +22,10 @@
 //         and short zero runs in front of / behind the sub-images -- so conv1 and the projection read base + immediate
 //         and nothing else (no tap mask, no select);
 //       - everywhere else (block 0 at 23 / 24 rows and its 32x32x16 body, block 1, and h for conv2 in every body) the
-//         planes carry no border: a per-tap select redirects such a tap to zero cells kept beside the planes.  h
+//         planes carry no border: a select redirects such a tap to zero cells kept beside the planes.  In the
+//         16x16x32 body the select is one v_cndmask_b32 per (tile, tap) pair whose 64-lane mask is a compile-time
+//         constant (rbx_taps.h: rbx_tap_mask -- a lane's pixel is 16 t + (lane & 15)) held in a scalar register pair;
+//         a pair with every lane inside the image (most of tap (1, 1)) takes none, and no per-lane tap mask exists.  h
 //         stays so on purpose: a bordered h (row pitch OW + 1) puts two lanes of every ds_read_b128 lane group of
 //         conv2 on one bank, and the LDS cycles that costs outweigh the selects (profiles/r10_block_borders.txt).
 //   * conv1 (3x3 s2) accumulates into acc1; the 1x1 s2 projection of x then opens conv2's accumulator acc2, so x is
@@ -49,6 +52,7 @@
 #include "common.h"
 #include "nn_common.h"
 #include "resnet_plan.h"   // rbx_t16: which body a block runs; rbx_layout: where its pixels and zeros live in LDS
+#include "rbx_taps.h"      // rbx_tap_mask: the lanes of a (tile, tap) whose tap lies inside the image; rbx_zero_cell
 
 namespace cough {
 namespace {
@@ -208,10 +212,21 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     // rows, NP = 4) holds 2 k32-steps, so that it stays within 168 VGPRs and three workgroups per CU.
     constexpr int CT = T16 ? Cfg::CT : 1;      // channel tiles per wave and k-step in the ring
     constexpr int DW = !T16 ? RBX_D : CT == 2 && G == 1 ? 2 : RBX_DQ;
-    const bf16_t* wbase = a.wf + size_t(T16 ? wave * CT : wave % Cfg::NT) * 1024 + lane * 8;
+    // A fragment's address is a scalar base (the array + the k-step's bytes, formed on the scalar unit; the empty asm
+    // keeps the compiler from folding the step into a 64-bit vector addition per load) + this lane's 32-bit offset + an
+    // immediate (channel tile, plane): global_load_dwordx4 v, voff, s[base:base+1] offset:imm.
+    // (The offset is extended to 64 bits next to the load only if it is defined in the load's basic block: WLANE_HERE,
+    // an empty asm too, re-defines it at the head of each k-loop.)
+    unsigned wlane = unsigned(T16 ? wave * CT : wave % Cfg::NT) * 2048u + lane * 16u;   // bytes
+#define WLANE_HERE() asm("" : "+v"(wlane))
     constexpr int WSTEP = T16 ? COUT / 16 : Cfg::NT;   // channel tiles per k-step in the fragment array
+    static_assert((CT * 2 - 1) * 1024 < 4096, "channel tile and plane inside the load's immediate offset");
     auto wfrag = [&](int s, int ct, int plane) -> bf16x8 {
-        return *reinterpret_cast<const bf16x8*>(wbase + ((size_t(s) * WSTEP + ct) * 2 + plane) * 512);
+        using gbytes = const __attribute__((address_space(1))) char*;
+        using gfrag = const __attribute__((address_space(1))) bf16x8*;
+        gbytes sb = (gbytes)a.wf + size_t(s) * WSTEP * 2048;
+        asm("" : "+s"(sb));
+        return *(gfrag)(sb + wlane + (ct * 2 + plane) * 1024);
     };
     bf16x8 ring[DW][CT][2];
 #pragma unroll
@@ -226,7 +241,6 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         // the shipped image stages in ONE batch (all loads in flight before the first split); a larger image (103- / 110-row
         // features) in two, so that the staging registers stay within the accumulators' budget
         constexpr int NB = UN <= Cfg::STAGE_MAX ? 1 : 2, UNB = (UN + NB - 1) / NB;
-        const int valid = nvalid * NPX * QP;
         const float4* src = reinterpret_cast<const float4*>(a.x + (long long)clip0 * NPX * CIN);
         if constexpr (Cfg::BX) {
             // the zero cells of every chunk plane, hi and lo: the unused column of the odd-column sub-images and the
@@ -246,32 +260,42 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         } else if (tid < 2 * CHI) {   // the zero cell of every chunk plane, hi and lo
             *reinterpret_cast<uint4*>(smem + (tid / CHI) * PL + (tid % CHI) * CPX + ZX) = make_uint4(0, 0, 0, 0);
         }
+        // FULL: every clip of the workgroup exists -- always with one clip per workgroup, and with two in every workgroup
+        // but the last of a launch -- so the clamp and the zeroing below compare with the compile-time NPIECE and the
+        // pieces carry no batch-end branch; the last workgroup of a two-clip launch takes the other instance.
+        auto stage = [&](auto fullc) {
+            constexpr bool FULL = decltype(fullc)::value;
+            const int valid = FULL ? NPIECE : nvalid * NPX * QP;
 #pragma unroll
-        for (int b0 = 0; b0 < UN; b0 += UNB) {
-            float4 v[UNB];
+            for (int b0 = 0; b0 < UN; b0 += UNB) {
+                float4 v[UNB];
 #pragma unroll
-            for (int u = 0; u < UNB; ++u) {
-                // unconditional, index-clamped loads: a load under a branch makes the compiler drain vmcnt to 0 before the
-                // first piece is split; clamped, the pieces are processed as they arrive (vmcnt(UNB - 1 - u))
-                const int i = tid + (b0 + u) * THREADS;
-                v[u] = src[i < valid ? i : valid - 1];
-            }
+                for (int u = 0; u < UNB; ++u) {
+                    // unconditional, index-clamped loads: a load under a branch makes the compiler drain vmcnt to 0 before the
+                    // first piece is split; clamped, the pieces are processed as they arrive (vmcnt(UNB - 1 - u))
+                    const int i = tid + (b0 + u) * THREADS;
+                    v[u] = src[i < valid ? i : valid - 1];
+                }
 #pragma unroll
-            for (int u = 0; u < UNB; ++u) {
-                const int i = tid + (b0 + u) * THREADS;
-                if (i < NPIECE) {
-                    const int P = i / QP, q = i % QP;                      // raster pixel (clip, row, column), quarter-chunk
-                    const int g = P / NPX, rem = P % NPX, ih = rem / XW, iw = rem % XW;
-                    const int cell = RBX_X_CELL(g * NPPC, Cfg::PB01, Cfg::PB10, Cfg::PB11, OW, ih, iw);
-                    uint2 hi, lo;
-                    if (i >= valid) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);   // clips beyond the batch read as zeros
-                    split4(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
-                    const int off = Cfg::xoff(q >> 1) + cell * 16 + (q & 1) * 8;
-                    *reinterpret_cast<uint2*>(smem + off) = hi;
-                    *reinterpret_cast<uint2*>(smem + off + PL) = lo;
+                for (int u = 0; u < UNB; ++u) {
+                    const int i = tid + (b0 + u) * THREADS;
+                    if (i < NPIECE) {
+                        const int P = i / QP, q = i % QP;                      // raster pixel (clip, row, column), quarter-chunk
+                        const int g = P / NPX, rem = P % NPX, ih = rem / XW, iw = rem % XW;
+                        const int cell = RBX_X_CELL(g * NPPC, Cfg::PB01, Cfg::PB10, Cfg::PB11, OW, ih, iw);
+                        uint2 hi, lo;
+                        if (!FULL && i >= valid) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);   // clips beyond the batch read as zeros
+                        split4(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
+                        const int off = Cfg::xoff(q >> 1) + cell * 16 + (q & 1) * 8;
+                        *reinterpret_cast<uint2*>(smem + off) = hi;
+                        *reinterpret_cast<uint2*>(smem + off + PL) = lo;
+                    }
                 }
             }
-        }
+        };
+        if constexpr (G == 1) stage(std::true_type{});
+        else if (nvalid == G) stage(std::true_type{});
+        else stage(std::false_type{});
     }
     if (tid < COUT) { lbias[tid] = bv1; lbias[COUT + tid] = bv2; }
     float fw0 = 0.f, fw1 = 0.f, fb0 = 0.f, fb1 = 0.f;   // fused head (block 1): Linear(128, 2) weights of channel tid & 127
@@ -311,31 +335,30 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     constexpr int NP = Cfg::NP, KQ1 = Cfg::KQ1, KQP = Cfg::KQP, KQ = Cfg::KQ, P = RBX_P, NB = P + 1;
     constexpr int NI = KQ * NP, I2 = (KQ1 + KQP) * NP;   // (k32-step, tile) pairs; the first pair of conv2
     const int px = lane & 15, tq = lane >> 4, n0 = 16 * CT * wave + 4 * tq;
-    // per tile: bit tap (0..8) = conv1 tap (kh, kw) = tap / 3, tap % 3 lies inside x; bit 9 + tap: conv2 tap inside h
-    unsigned vm[NP];
-#pragma unroll
-    for (int t = 0; t < NP; ++t) {
-        const int R = 16 * t + px, rem = G > 1 ? R % PER : R, oh = rem / OW, ow = rem % OW;
-        unsigned m = 0;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int kh = tap / 3, kw = tap % 3;
-            const int ih = 2 * oh - 1 + kh, iw = 2 * ow - 1 + kw, jh = oh - 1 + kh, jw = ow - 1 + kw;
-            if (!Cfg::BX && unsigned(ih) < unsigned(XH) && unsigned(iw) < unsigned(XW)) m |= 1u << tap;   // bordered x: no select
-            if (unsigned(jh) < unsigned(OH) && unsigned(jw) < unsigned(OW)) m |= 1u << (9 + tap);
-        }
-        vm[t] = R < M ? m : 0u;   // a padding row reads the zero cell at every tap
-    }
     // Pixel R of clip g has x cell g * NPPC + R - g * PER of sub-image (0, 0): tile t's cells are this lane's base +
     // 256 t bytes, + DX from the tile past the clip boundary on; the one tile that straddles it takes its base from lbs.
     // Pixel R's h cell is R.
+    // These bases are absolute LDS addresses: the workgroup's LDS base is folded in here, once, and what aaddr forms
+    // from them is the operand of the ds_read itself.
+    using lds_bytes = const __attribute__((address_space(3))) char*;
+    using lds_frag = const __attribute__((address_space(3))) bf16x8*;
+    const int lds0 = int(reinterpret_cast<size_t>((lds_bytes)smem));
     constexpr int DX = (NPPC - PER) * 16;
-    const int lbx = px * 16 + Cfg::xoff(tq), lbh = px * 16 + tq * CPH, zh = ZH + tq * CPH;
+    const int lbx = lds0 + px * 16 + Cfg::xoff(tq), lbh = lds0 + px * 16 + tq * CPH, zh = lds0 + ZH + tq * CPH, zx = lds0 + ZX;
     const int lbs = lbx + (G > 1 && px >= PER % 16 ? DX : 0);
     // the zero cell a lane reads for a tap outside the image: the one with the bank residue (mod 16 cells) of its
     // in-image cell; rx is the residue of the lane's x cell of tile 0 (x planes with CIN = 64 are not 256-B aligned)
     const int rx = px + (CHI == 4 ? 0 : Cfg::xoff(tq) / 16);
-    auto zcell = [&](int z, int res) { return z + (res & 15) * 16; };
+    // Which lanes of a (tile, tap) pair read their cell and which a zero cell is known here: the pixel of lane l of tile t
+    // is 16 t + (l & 15), so the 64-lane mask is a constant (rbx_taps.h: rbx_tap_mask; a padding row R >= M reads zeros at
+    // every tap).  It reaches v_cndmask_b32 as a scalar register pair the compiler fills with s_mov; the statement holds
+    // that one instruction, whose operands -- two vector registers written by vector instructions, a scalar pair
+    // written by the scalar unit -- need no wait states.  A pair whose 64 lanes all lie inside takes no select at all.
+    auto lane_select = [](unsigned long long inside, int cell, int zero) -> int {
+        int r;
+        asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(zero), "v"(cell), "s"(inside));
+        return r;
+    };
     RB_STAMP(1);
     __syncthreads();
     RB_STAMP(2);
@@ -351,11 +374,29 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
 #pragma unroll
             for (int t = 0; t < NP; ++t) { acc1[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
+        // The zero cell a lane reads for a tap depends on the lane and the tap, not on the tile.  ZREG: the nine cells of
+        // the operand stay in registers (made opaque, or the compiler forms each again at every select), so a select is
+        // one v_add_u32 (the cell) and the v_cndmask_b32.  Else -- block 1 with one clip, which stays within 168 VGPRs --
+        // the zero cell is formed from the cell's own residue with one v_and_or_b32 (the LDS base and the zero rows are
+        // 256-B aligned).
+        constexpr bool ZREG = !(CT == 2 && G == 1);
+        int zxc[9], zhc[9];
+        auto zero_cells = [&](auto opc) {
+            constexpr int op = decltype(opc)::value;
+            if constexpr (ZREG && !(op == RBX_OP_X && Cfg::BX)) {
+#pragma unroll
+                for (int tap = 0; tap < 9; ++tap) {
+                    int z = op == RBX_OP_X ? rbx_zero_cell(zx, rx + tapx(tap / 3, tap % 3)) : rbx_zero_cell(zh, px + rbx_h_tap(OW, tap / 3, tap % 3));
+                    asm("" : "+v"(z));
+                    (op == RBX_OP_X ? zxc : zhc)[tap] = z;
+                }
+            }
+        };
         // Address of the hi fragment of pair i = (k32-step i / NP, tile i % NP), compile-time at every call site.  The
         // tap's cell (base + compile-time offset) or the zero cell is chosen at the tap's first k32-step; further
         // k32-steps of the tap (chunk planes) and the lo plane are immediate offsets.
         int tadr[NP];
-        auto aaddr = [&](auto ic) -> const char* {
+        auto aaddr = [&](auto ic) -> int {
             constexpr int i = decltype(ic)::value, q = i / NP, t = i % NP;
             constexpr bool conv1 = q < KQ1, proj = !conv1 && q < KQ1 + KQP;
             constexpr int kt = (conv1 ? q : proj ? q - KQ1 : q - KQ1 - KQP) * 32;   // k inside this operand
@@ -363,25 +404,34 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
             constexpr int tap = proj ? 4 : kt / C, c32 = (kt % C) / 32, kh = tap / 3, kw = tap % 3;
             if constexpr (Cfg::BX && (conv1 || proj)) {
                 // bordered x (one clip, one k32-step per tap): the lane's base + an immediate, inside or outside the image
-                return smem + lbx + (256 * t + 16 * tapx(kh, kw));
+                return lbx + (256 * t + 16 * tapx(kh, kw));
             } else if constexpr (c32 == 0) {
                 if constexpr (conv1 || proj) {
                     constexpr bool strad = G > 1 && 16 * t < PER && 16 * t + 16 > PER;
                     constexpr int off = 256 * t + (G > 1 && 16 * t >= PER ? DX : 0) + 16 * tapx(kh, kw);
-                    tadr[t] = (vm[t] & (1u << tap)) ? (strad ? lbs : lbx) + off : zcell(ZX, rx + tapx(kh, kw));
+                    constexpr unsigned long long in = rbx_tap_mask(Cfg::L, RBX_OP_X, t, tap);
+                    const int cell = (strad ? lbs : lbx) + off;
+                    if constexpr (in == ~0ull) tadr[t] = cell;
+                    else tadr[t] = lane_select(in, cell, ZREG ? zxc[tap] : zx | (cell & 0xF0));
                 } else {
-                    constexpr int off = 256 * t + 16 * ((kh - 1) * OW + kw - 1);
-                    tadr[t] = (vm[t] & (1u << (9 + tap))) ? lbh + off : zcell(zh, px + (kh - 1) * OW + kw - 1);
+                    constexpr int off = 256 * t + 16 * rbx_h_tap(OW, kh, kw);
+                    constexpr unsigned long long in = rbx_tap_mask(Cfg::L, RBX_OP_H, t, tap);
+                    const int cell = lbh + off;
+                    if constexpr (in == ~0ull) tadr[t] = cell;
+                    else tadr[t] = lane_select(in, cell, ZREG ? zhc[tap] : zh | (cell & 0xF0));
                 }
             }
-            return smem + tadr[t] + c32 * ((conv1 || proj) ? KX : 4 * CPH);
+            return tadr[t] + c32 * ((conv1 || proj) ? KX : 4 * CPH);
         };
+        auto ldsfrag = [](int addr) -> bf16x8 { return *reinterpret_cast<lds_frag>(addr); };
+        zero_cells(std::integral_constant<int, RBX_OP_X>{});
         bf16x8 af[NB][2];
+        WLANE_HERE();
         auto fetch = [&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            const char* p = aaddr(ic);
-            af[i % NB][0] = *reinterpret_cast<const bf16x8*>(p);
-            af[i % NB][1] = *reinterpret_cast<const bf16x8*>(p + PL);
+            const int p = aaddr(ic);
+            af[i % NB][0] = ldsfrag(p);
+            af[i % NB][1] = ldsfrag(p + PL);
         };
         [&]<int... Js>(std::integer_sequence<int, Js...>) {
             (fetch(std::integral_constant<int, Js>{}), ...);
@@ -420,6 +470,8 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 }
                 __syncthreads();
                 RB_STAMP(4);
+                WLANE_HERE();
+                zero_cells(std::integral_constant<int, RBX_OP_H>{});
 #if RBX_PRIO
                 __builtin_amdgcn_s_setprio(1);
 #endif
@@ -435,7 +487,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
             constexpr bool pf = j < NI && (j < I2) == (i < I2);
             constexpr bool wl = t == NP - 1 && q + DW < KQ;
             const bf16x8 cur_hi = af[i % NB][0], cur_lo = af[i % NB][1];
-            const char* np = nullptr;
+            int np = 0;
             if constexpr (pf) np = aaddr(std::integral_constant<int, j>{});
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) {
                 ([&] {
@@ -446,8 +498,8 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                     if constexpr (q < KQ1) acc1[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc1[ct][t], 0, 0, 0);
                     else acc2[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc2[ct][t], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (pf && m == CT - 1) af[j % NB][0] = *reinterpret_cast<const bf16x8*>(np);
-                    if constexpr (pf && m == 2 * CT - 1) af[j % NB][1] = *reinterpret_cast<const bf16x8*>(np + PL);
+                    if constexpr (pf && m == CT - 1) af[j % NB][0] = ldsfrag(np);
+                    if constexpr (pf && m == 2 * CT - 1) af[j % NB][1] = ldsfrag(np + PL);
                     if constexpr (wl && kind == 1) ring[q % DW][ct][0] = wfrag(q + DW, ct, 0);
                     if constexpr (wl && kind == 2) ring[q % DW][ct][1] = wfrag(q + DW, ct, 1);
                 }(), ...);
@@ -531,6 +583,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
         };
 
         bf16x8 af[2][MWX][2];
+        WLANE_HERE();
 #pragma unroll
         for (int mt = 0; mt < MWX; ++mt) afrag(std::integral_constant<int, 0>{}, mt, af[0][mt][0], af[0][mt][1]);
 
@@ -563,6 +616,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
                 }
                 __syncthreads();
                 RB_STAMP(4);
+                WLANE_HERE();
 #if RBX_PRIO
                 __builtin_amdgcn_s_setprio(1);
 #endif
@@ -681,6 +735,7 @@ __global__ __launch_bounds__(256, 2) void resblock_x3_kernel(RbxArgs a) {
     }
     RB_STAMP(7);
 }
+#undef WLANE_HERE
 
 // Host: folded [N][K] weights of conv1, projection and conv2 -> split-bf16 32x32x16 fragments in stream order.
 inline void pack_x3_fragments(std::vector<bf16_t>& wf, const std::vector<float>& w1, int K1, const std::vector<float>& wp,
