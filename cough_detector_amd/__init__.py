@@ -17,6 +17,8 @@ from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, st
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
                     sweep_thresholds)
+from .audit import (LabelIssues, OutOfFoldScores, audit_labels, bank_files, find_label_issues, out_of_fold_scores,
+                    stratified_kfold)
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -28,4 +30,6 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "prepare_dataset_split", "stratified_split", "SegmentTable", "frame_energy", "find_segments", "extract_segments", "WindowScores", "ThresholdSweep",
            "EventTable", "score_bank", "sweep_thresholds", "detect_events", "event_windows", "detection_report",
            "draw_batch", "augment_rows_drawn", "warp_rows", "draw_speed", "speed_rate_pair",
-           "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length"]
+           "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length",
+           "stratified_kfold", "out_of_fold_scores", "OutOfFoldScores", "find_label_issues", "LabelIssues", "audit_labels",
+           "bank_files"]
