@@ -10,11 +10,13 @@ from .augmentation import AudioAugmentor, MixUp, SpecAugment, create_augmentatio
 from .training import HipAdamW, ResidualTrainer, SmallTrainer, StandardTrainer, create_trainer, train_epoch
 from .loop import (EarlyStopping, EpochMeter, class_weights_from_counts, fit, load_checkpoint, save_checkpoint,
                    train_epoch_async, validate)
-from .data import DeviceClipBank, DeviceDataLoader, create_data_loaders, prepare_dataset_split, stratified_split
+from .data import (DeviceClipBank, DeviceDataLoader, create_data_loaders, prepare_dataset_split, prepare_group_split,
+                   stratified_group_split, stratified_split)
 from .draws import augment_rows_drawn, draw_batch
 from .warp import draw_speed, speed_rate_pair, warp_rows
 from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
+from .slices import WindowTable, find_windows, inactive_clips, slice_bank, write_clips
 from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
                     sweep_thresholds)
 from .audit import (LabelIssues, OutOfFoldScores, audit_labels, bank_files, find_label_issues, out_of_fold_scores,
@@ -32,4 +34,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "draw_batch", "augment_rows_drawn", "warp_rows", "draw_speed", "speed_rate_pair",
            "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length",
            "stratified_kfold", "out_of_fold_scores", "OutOfFoldScores", "find_label_issues", "LabelIssues", "audit_labels",
-           "bank_files"]
+           "bank_files", "WindowTable", "find_windows", "slice_bank", "inactive_clips", "write_clips",
+           "stratified_group_split", "prepare_group_split"]

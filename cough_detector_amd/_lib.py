@@ -6,6 +6,11 @@ the environment variable ``COUGH_AMD[_NAME]_LIB``), the C-ABI header ``include/c
 the ABI version it must report and its prototypes.  ``load`` / ``check`` bind the main library's record, ``load_NAME`` /
 ``check_NAME`` a companion's; ``NAME_SYMBOLS`` are the prototypes' names.
 
+There are two tables.  ``LIBRARIES`` is closed: its nine records, their order, symbol counts and ABI versions are pinned by
+``tests/test_libraries_host.py``, which later work must leave as it is.  ``LATER`` is open-ended: a library that comes
+after the nine gets its record there (``build.LATER_UNITS`` is its counterpart), with the same naming rules and the same
+module-level names ``load_NAME`` / ``check_NAME`` / ``NAME_SYMBOLS`` / ``NAME_LIB_PATH``.
+
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
 from __future__ import annotations
@@ -284,12 +289,25 @@ def _libraries() -> dict:
     )}
 
 
+def _later() -> dict:
+    vp, i, d, s = C.c_void_p, C.c_int, C.c_double, C.c_char_p
+    return {lib.name: lib for lib in (
+        # include/cough_amd_slices.h: fixed-length windows of long recordings, kept by their activity
+        Library("slices", 1, {
+            "cough_slices_abi_version": (i, None), "cough_slices_last_error": (s, None),
+            "cough_window_activity": (None, [vp, vp, vp, vp, i, i, i, i, i, i, d, d, d, vp, vp, vp, vp, vp, vp]),
+            "cough_list_windows": (None, [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]),
+        }),
+    )}
+
+
 LIBRARIES = _libraries()
+LATER = _later()
 
 # the names the rest of the package uses, bound to the records: the main library's carry no prefix
 load, check, SYMBOLS, LIB_PATH = (LIBRARIES["amd"].load, LIBRARIES["amd"].check, LIBRARIES["amd"].symbols,
                                   LIBRARIES["amd"].path)
-for _r in list(LIBRARIES.values())[1:]:
+for _r in (*list(LIBRARIES.values())[1:], *LATER.values()):
     globals().update({f"load_{_r.name}": _r.load, f"check_{_r.name}": _r.check,
                       f"{_r.name.upper()}_SYMBOLS": _r.symbols, f"{_r.name.upper()}_LIB_PATH": _r.path})
 del _r

@@ -5,6 +5,11 @@ name: ``libcough_amd[_NAME].so`` beside this file, the version script ``csrc/exp
 ``include/cough_amd[_NAME].h`` (``amd``, the main library, carries no suffix).  Every translation unit is compiled to
 an object file of its own (in parallel, cached under ``build/`` by the newest source / header time) and each library
 is linked from the objects of its own units.  The libraries are build products and stay out of git.
+
+There are two tables.  ``UNITS`` is closed: its nine libraries, their order and their units are pinned by
+``tests/test_libraries_host.py``, which later work must leave as it is.  ``LATER_UNITS`` is open-ended: a library that
+comes after the nine is entered there, under the same naming rules, and is built, checked for staleness and linked
+exactly like the nine.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
 from __future__ import annotations
@@ -47,7 +52,13 @@ def _named(stem: str, name: str, ext: str) -> str:
     return stem + ("" if name == "amd" else "_" + name) + ext
 
 
+# the libraries after the nine (module docstring): same rules, a table that may grow
+LATER_UNITS = {
+    "slices": ("slices.hip",),      # corpus curation: fixed-length windows of long recordings, kept by their activity
+}
+
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}
+LATER_LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in LATER_UNITS}
 LIB = LIBS["amd"]
 # -fno-slp-vectorize: left alone, -O3 packs adjacent f32 adds / multiplies of the FFT butterflies into v_pk_*_f32, which issue
 # slower than the two scalar operations they replace on gfx950 (same-box A/B: K1 -2.4 %, STFT stage -3.2 %, classifier unchanged;
@@ -72,24 +83,39 @@ def _version_script(name: str) -> str:
 
 def _headers_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps += [os.path.join(HERE, "..", "include", _named("cough_amd", name, ".h")) for name in UNITS]
+    deps += [os.path.join(HERE, "..", "include", _named("cough_amd", name, ".h")) for name in (*UNITS, *LATER_UNITS)]
     deps.append(os.path.abspath(__file__))   # the flags live here
-    deps += [_version_script(name) for name in UNITS]
+    deps += [_version_script(name) for name in (*UNITS, *LATER_UNITS)]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    if not all(os.path.exists(p) for p in LIBS.values()):
+    libs = (*LIBS.values(), *LATER_LIBS.values())
+    if not all(os.path.exists(p) for p in libs):
         return True
-    t = min(os.path.getmtime(p) for p in LIBS.values())
-    sources = {u if isinstance(u, str) else u[0] for units in UNITS.values() for u in units}
+    t = min(os.path.getmtime(p) for p in libs)
+    sources = {u if isinstance(u, str) else u[0] for units in (*UNITS.values(), *LATER_UNITS.values()) for u in units}
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in sources)
 
 
-def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB) -> str:
-    """Compile (only what changed, unless ``force`` / ``extra_flags``) and link the libraries.  ``extra_flags`` (e.g.
-    ``-DCOUGH_K1_STAMPS``) build a variant of libcough_amd.so alone at ``out`` with objects of its own."""
-    if not force and not extra_flags and not is_stale():
+def later_stale(name: str) -> bool:
+    """A library of ``LATER_UNITS`` is missing, or older than one of its sources, a header, its version script or this
+    file."""
+    lib = LATER_LIBS[name]
+    if not os.path.exists(lib):
+        return True
+    t = os.path.getmtime(lib)
+    sources = {u if isinstance(u, str) else u[0] for u in LATER_UNITS[name]}
+    return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in sources)
+
+
+def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB, force_later: bool = False) -> str:
+    """Compile (only what changed, unless ``force`` / ``extra_flags``) and link the libraries of both tables.
+    ``extra_flags`` (e.g. ``-DCOUGH_K1_STAMPS``) build a variant of libcough_amd.so alone at ``out`` with objects of its
+    own.  ``force`` rebuilds the nine libraries of ``UNITS`` -- the link list of a forced build is pinned to exactly
+    those nine -- while a library of ``LATER_UNITS`` is rebuilt when it is stale (``later_stale``) or ``force_later`` is
+    set; the command line's ``--force`` sets both."""
+    if not force and not force_later and not extra_flags and not is_stale():
         return LIB
     hipcc = _hipcc()
     objdir = OBJ if not extra_flags else OBJ + "_" + str(abs(hash(tuple(extra_flags))) % 10**8)
@@ -99,20 +125,23 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
     def compile_one(unit) -> str:
         src, flags, suffix = unit if isinstance(unit, tuple) else (unit, (), "")
         s, o = os.path.join(CSRC, src), os.path.join(objdir, src.replace(".hip", suffix + ".o"))
-        if force or not os.path.exists(o) or os.path.getmtime(o) < max(hdr, os.path.getmtime(s)):
+        if force or force_later or not os.path.exists(o) or os.path.getmtime(o) < max(hdr, os.path.getmtime(s)):
             cmd = [hipcc, *CFLAGS, *extra_flags, *flags, "-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)
         return o
 
-    targets = {"amd": out} if extra_flags or out != LIB else LIBS
-    units = [u for name in targets for u in UNITS[name]]
+    all_units = {**UNITS, **LATER_UNITS}
+    targets = {"amd": out}
+    if not extra_flags and out == LIB:
+        targets = {**LIBS, **{name: lib for name, lib in LATER_LIBS.items() if force_later or later_stale(name)}}
+    units = [u for name in targets for u in all_units[name]]
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1)) as pool:
         obj = dict(zip(units, pool.map(compile_one, units)))
     for name, target in targets.items():
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + _version_script(name),
-               "-o", target, *(obj[u] for u in UNITS[name])]
+               "-o", target, *(obj[u] for u in all_units[name])]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
@@ -120,5 +149,5 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
 
 
 if __name__ == "__main__":
-    build_library(force="--force" in sys.argv)
+    build_library(force="--force" in sys.argv, force_later="--force" in sys.argv)
     print(LIB)

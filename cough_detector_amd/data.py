@@ -136,6 +136,32 @@ def stratified_split(labels: Sequence[int], val_split: float = 0.2, random_state
     return [int(i) for i in train], [int(i) for i in test]
 
 
+def stratified_group_split(labels: Sequence[int], groups: Sequence[int], val_split: float = 0.2,
+                           random_state: int = 42) -> Tuple[List[int], List[int]]:
+    """``(train_idx, val_idx)`` of a split that keeps every group on one side: for clips cut from recordings
+    (``groups=table.clip`` of a ``WindowTable`` or ``SegmentTable``), pieces of one recording never land on both
+    sides.  The groups are taken in ``np.unique`` order, each with the label its members share (two different labels
+    in one group raise ``ValueError``); those labels go through ``stratified_split(group_labels, val_split,
+    random_state)`` unchanged, so ``val_split`` is a share of the groups.  Each side is its groups in the order
+    ``stratified_split`` returned them, the members of a group in ascending index."""
+    y = np.asarray(labels.tolist() if isinstance(labels, torch.Tensor) else labels)
+    g = np.asarray(groups.tolist() if isinstance(groups, torch.Tensor) else groups)
+    if y.ndim != 1 or g.shape != y.shape:
+        raise ValueError(f"stratified_group_split: labels and groups must be one-dimensional and of one length, got "
+                         f"shapes {y.shape} and {g.shape}")
+    names, member_of = np.unique(g, return_inverse=True)
+    order = np.argsort(member_of, kind="mergesort")               # members of a group in ascending index
+    members = np.split(order, np.cumsum(np.bincount(member_of, minlength=len(names)))[:-1]) if len(names) else []
+    group_labels = []
+    for name, idx in zip(names.tolist(), members):
+        if (y[idx] != y[idx[0]]).any():
+            raise ValueError(f"stratified_group_split: group {name!r} holds clips of different labels "
+                             f"({sorted(set(y[idx].tolist()))}); a group is one recording and has one label")
+        group_labels.append(y[idx[0]])
+    train_groups, val_groups = stratified_split(group_labels, val_split=val_split, random_state=random_state)
+    return ([int(i) for k in train_groups for i in members[k]], [int(i) for k in val_groups for i in members[k]])
+
+
 def esc50_rows(csv_path, is_training: bool = True, fold: Optional[int] = None,
                include_all_negatives: bool = True) -> List[Tuple[str, int]]:
     """``[(filename, label)]`` of ``ESC50Dataset`` (dataset.py:227-264) from ``meta/esc50.csv``, in csv order: with
@@ -373,13 +399,25 @@ def prepare_dataset_split(data_dir_or_bank, preprocessor=None, val_split: float 
     """``(train_bank, val_bank)`` as the reference's ``prepare_dataset_split`` (dataset.py:421-483): the clips of a
     directory (``DeviceClipBank.from_directory(data_dir, preprocessor, device)``) or of a bank that exists already,
     split by ``stratified_split(bank.labels, val_split, random_state)``.  The augmentors are not arguments: they belong
-    to the loader (``create_data_loaders``), not to the bank."""
+    to the loader (``create_data_loaders``), not to the bank.  For clips cut from recordings see
+    ``prepare_group_split``."""
     bank = data_dir_or_bank
     if not isinstance(bank, DeviceClipBank):
         if preprocessor is None:
             raise ValueError("prepare_dataset_split: reading a directory needs a preprocessor")
         bank = DeviceClipBank.from_directory(str(bank), preprocessor, device=device)
     train_idx, val_idx = stratified_split(bank.labels, val_split=val_split, random_state=random_state)
+    return bank.subset(train_idx), bank.subset(val_idx)
+
+
+def prepare_group_split(bank: DeviceClipBank, groups: Sequence[int], val_split: float = 0.2,
+                        random_state: int = 42) -> Tuple[DeviceClipBank, DeviceClipBank]:
+    """``(train_bank, val_bank)`` of a bank of clips cut from recordings: ``prepare_dataset_split`` with
+    ``stratified_group_split(bank.labels, groups, val_split, random_state)`` in the place of ``stratified_split``, so a
+    recording stays on one side.  ``groups`` has one entry per clip: ``table.clip`` of ``slice_bank`` or
+    ``extract_segments``.  (A function of its own because ``prepare_dataset_split`` keeps the reference's argument
+    list.)"""
+    train_idx, val_idx = stratified_group_split(bank.labels, groups, val_split=val_split, random_state=random_state)
     return bank.subset(train_idx), bank.subset(val_idx)
 
 

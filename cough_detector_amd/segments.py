@@ -15,7 +15,8 @@ gives the loader its middle second, whatever that second holds.  Here a ``Device
    end of the clip's last segment is dropped; at most ``max_segments`` per clip (``cough_pick_segments``).
 
 Three kernels of ``libcough_amd_segments.so`` (``include/cough_amd_segments.h``) on the packed bank; the one value the
-host reads back is the per-clip segment count, which sizes the outputs.
+host reads back is the per-clip segment count, which sizes the outputs.  For negatives -- every active second of a
+recording, not its loudest frames -- see ``slices.py`` (``find_windows`` / ``slice_bank``).
 """
 from __future__ import annotations
 
@@ -159,14 +160,11 @@ def find_segments(bank: DeviceClipBank, preprocessor, **params) -> SegmentTable:
     return SegmentTable(clip_dev, starts.view(-1)[flat_dev], lengths.view(-1)[flat_dev], peak_db.view(-1)[flat_dev], counts)
 
 
-def extract_segments(bank: DeviceClipBank, preprocessor, **params) -> Tuple[DeviceClipBank, SegmentTable]:
-    """``(segments, table)``: a ``DeviceClipBank`` on ``bank``'s device whose clip ``j`` is samples ``table.start[j] ..
-    + table.length[j]`` of source clip ``table.clip[j]`` with that clip's label -- a bank like any other (``subset``,
-    ``DeviceDataLoader``, ``create_data_loaders``).  A corpus without a segment gives an empty bank.  ``params`` as
-    ``find_segments``."""
-    table = find_segments(bank, preprocessor, **params)
-    dev, seg_len = bank.device, int(preprocessor.segment_samples)
-    per_clip = table.counts.numpy().astype(np.int64)
+def _copy_rows(bank: DeviceClipBank, counts: torch.Tensor, starts: torch.Tensor, seg_len: int) -> DeviceClipBank:
+    """The bank of the rows of a table: ``counts[k]`` (host) rows of source clip ``k``, row ``j`` the ``min(seg_len, n)``
+    samples of its clip from ``starts[j]`` (device int32) on, with that clip's label."""
+    dev = bank.device
+    per_clip = counts.numpy().astype(np.int64)
     clip = np.repeat(np.arange(len(bank), dtype=np.int64), per_clip)
     lengths = np.minimum(bank.lengths.numpy()[clip], seg_len).astype(np.int32)      # min(seg_len, n): known to the host
     dst = np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int64)
@@ -177,7 +175,16 @@ def extract_segments(bank: DeviceClipBank, preprocessor, **params) -> Tuple[Devi
     if clip.size:
         offs, _ = _upload(dev, np.concatenate([bank.offsets.numpy()[clip], dst[:-1]]), np.zeros(0, np.int32))
         _lib.check_segments(_lib.load_segments().cough_copy_segments(
-            bank.data.data_ptr(), offs[:clip.size].data_ptr(), table.start.data_ptr(), out.lengths_dev.data_ptr(),
+            bank.data.data_ptr(), offs[:clip.size].data_ptr(), starts.data_ptr(), out.lengths_dev.data_ptr(),
             offs[clip.size:].data_ptr(), int(clip.size), int(lengths.max()), out.data.data_ptr(), _stream(dev)),
             "cough_copy_segments")
-    return out, table
+    return out
+
+
+def extract_segments(bank: DeviceClipBank, preprocessor, **params) -> Tuple[DeviceClipBank, SegmentTable]:
+    """``(segments, table)``: a ``DeviceClipBank`` on ``bank``'s device whose clip ``j`` is samples ``table.start[j] ..
+    + table.length[j]`` of source clip ``table.clip[j]`` with that clip's label -- a bank like any other (``subset``,
+    ``DeviceDataLoader``, ``create_data_loaders``).  A corpus without a segment gives an empty bank.  ``params`` as
+    ``find_segments``."""
+    table = find_segments(bank, preprocessor, **params)
+    return _copy_rows(bank, table.counts, table.start, int(preprocessor.segment_samples)), table
