@@ -17,6 +17,8 @@ from .warp import draw_speed, speed_rate_pair, warp_rows
 from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .slices import WindowTable, find_windows, inactive_clips, slice_bank, write_clips
+from .duplicates import (DuplicateTable, Fingerprints, drop_duplicates, duplicate_groups, find_duplicates, fingerprint_bank,
+                         fingerprint_images, label_conflicts)
 from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, detection_report, event_windows, score_bank,
                     sweep_thresholds)
 from .audit import (LabelIssues, OutOfFoldScores, audit_labels, bank_files, find_label_issues, out_of_fold_scores,
@@ -35,4 +37,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "stretch_rows", "pitch_shift_rows", "draw_pitch", "pitch_rate", "pitch_rate_pair", "stretched_length",
            "stratified_kfold", "out_of_fold_scores", "OutOfFoldScores", "find_label_issues", "LabelIssues", "audit_labels",
            "bank_files", "WindowTable", "find_windows", "slice_bank", "inactive_clips", "write_clips",
-           "stratified_group_split", "prepare_group_split"]
+           "stratified_group_split", "prepare_group_split", "Fingerprints", "DuplicateTable", "fingerprint_images",
+           "fingerprint_bank", "find_duplicates", "duplicate_groups", "label_conflicts", "drop_duplicates"]

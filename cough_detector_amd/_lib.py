@@ -10,6 +10,8 @@ There are two tables.  ``LIBRARIES`` is closed: its nine records, their order, s
 ``tests/test_libraries_host.py``, which later work must leave as it is.  ``LATER`` is open-ended: a library that comes
 after the nine gets its record there (``build.LATER_UNITS`` is its counterpart), with the same naming rules and the same
 module-level names ``load_NAME`` / ``check_NAME`` / ``NAME_SYMBOLS`` / ``NAME_LIB_PATH``.
+``LATER`` is pinned too by now (``tests/test_slices_host.py``), so the libraries after it get their records in ``OPEN``
+(``build.OPEN_UNITS``): same rules, same module-level names, and tests only ever ask whether their own library is in it.
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.
 """
@@ -301,13 +303,29 @@ def _later() -> dict:
     )}
 
 
+def _open() -> dict:
+    vp, i, s, sz = C.c_void_p, C.c_int, C.c_char_p, C.c_size_t
+    match = [vp, vp, i, i, i, i, i]                  # words, live, n, Tw, L, max_err_1024, min_live
+    return {lib.name: lib for lib in (
+        # include/cough_amd_dups.h: binary fingerprints of the feature images and the all-pairs matcher
+        Library("dups", 1, {
+            "cough_dups_abi_version": (i, None), "cough_dups_last_error": (s, None),
+            "cough_fingerprint_images": (None, [vp, i, i, i, C.POINTER(i), i, i, vp, vp, vp]),
+            "cough_match_workspace_bytes": (sz, [i, i]),
+            "cough_count_matches": (None, match + [vp, vp, vp, sz, vp]),
+            "cough_list_matches": (None, match + [vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        }),
+    )}
+
+
 LIBRARIES = _libraries()
 LATER = _later()
+OPEN = _open()
 
 # the names the rest of the package uses, bound to the records: the main library's carry no prefix
 load, check, SYMBOLS, LIB_PATH = (LIBRARIES["amd"].load, LIBRARIES["amd"].check, LIBRARIES["amd"].symbols,
                                   LIBRARIES["amd"].path)
-for _r in (*list(LIBRARIES.values())[1:], *LATER.values()):
+for _r in (*list(LIBRARIES.values())[1:], *LATER.values(), *OPEN.values()):
     globals().update({f"load_{_r.name}": _r.load, f"check_{_r.name}": _r.check,
                       f"{_r.name.upper()}_SYMBOLS": _r.symbols, f"{_r.name.upper()}_LIB_PATH": _r.path})
 del _r

@@ -15,7 +15,8 @@ per-clip Python, no host read; the probabilities are scattered into one ``(n, 2)
 eval-mode handle is built from them.
 
 The audit judges each clip as the loader sees it: ``cough_prepare_rows`` keeps the centre ``segment_duration`` of a
-longer clip, so long recordings go through ``extract_segments`` first.  Duplicate search and k-NN are out of scope.
+longer clip, so long recordings go through ``extract_segments`` first.  Copies of one clip on both sides of a fold make
+these scores optimistic: ``cough_detector_amd.duplicates`` finds them (and copies filed under both labels) beforehand.
 
     python -m cough_detector_amd.audit data --model-type small --folds 5 --epochs 20 --top 50
 """

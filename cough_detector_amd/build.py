@@ -10,6 +10,9 @@ There are two tables.  ``UNITS`` is closed: its nine libraries, their order and 
 ``tests/test_libraries_host.py``, which later work must leave as it is.  ``LATER_UNITS`` is open-ended: a library that
 comes after the nine is entered there, under the same naming rules, and is built, checked for staleness and linked
 exactly like the nine.
+That second table turned out to be pinned as well (``tests/test_slices_host.py`` fixes its contents), so the libraries
+after it live in ``OPEN_UNITS``: same naming rules, same build, staleness and link steps, and tests of a library there
+assert that their own name is in it, never what else is -- the next library is one more entry.
 Usage: ``python -m cough_detector_amd.build [--force]``.
 """
 from __future__ import annotations
@@ -57,8 +60,14 @@ LATER_UNITS = {
     "slices": ("slices.hip",),      # corpus curation: fixed-length windows of long recordings, kept by their activity
 }
 
+# the open table (module docstring): a new library is one more entry here and one more record in _lib.OPEN
+OPEN_UNITS = {
+    "dups": ("dups.hip",),          # corpus curation: binary fingerprints of the feature images, the all-pairs matcher
+}
+
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}
 LATER_LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in LATER_UNITS}
+OPEN_LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in OPEN_UNITS}
 LIB = LIBS["amd"]
 # -fno-slp-vectorize: left alone, -O3 packs adjacent f32 adds / multiplies of the FFT butterflies into v_pk_*_f32, which issue
 # slower than the two scalar operations they replace on gfx950 (same-box A/B: K1 -2.4 %, STFT stage -3.2 %, classifier unchanged;
@@ -83,37 +92,38 @@ def _version_script(name: str) -> str:
 
 def _headers_mtime() -> float:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps += [os.path.join(HERE, "..", "include", _named("cough_amd", name, ".h")) for name in (*UNITS, *LATER_UNITS)]
+    deps += [os.path.join(HERE, "..", "include", _named("cough_amd", name, ".h")) for name in (*UNITS, *LATER_UNITS, *OPEN_UNITS)]
     deps.append(os.path.abspath(__file__))   # the flags live here
-    deps += [_version_script(name) for name in (*UNITS, *LATER_UNITS)]
+    deps += [_version_script(name) for name in (*UNITS, *LATER_UNITS, *OPEN_UNITS)]
     return max(os.path.getmtime(d) for d in deps)
 
 
 def is_stale() -> bool:
-    libs = (*LIBS.values(), *LATER_LIBS.values())
+    libs = (*LIBS.values(), *LATER_LIBS.values(), *OPEN_LIBS.values())
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
-    sources = {u if isinstance(u, str) else u[0] for units in (*UNITS.values(), *LATER_UNITS.values()) for u in units}
+    sources = {u if isinstance(u, str) else u[0] for units in (*UNITS.values(), *LATER_UNITS.values(), *OPEN_UNITS.values())
+               for u in units}
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in sources)
 
 
 def later_stale(name: str) -> bool:
-    """A library of ``LATER_UNITS`` is missing, or older than one of its sources, a header, its version script or this
-    file."""
-    lib = LATER_LIBS[name]
+    """A library of ``LATER_UNITS`` or ``OPEN_UNITS`` is missing, or older than one of its sources, a header, its version
+    script or this file."""
+    lib = LATER_LIBS[name] if name in LATER_LIBS else OPEN_LIBS[name]
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    sources = {u if isinstance(u, str) else u[0] for u in LATER_UNITS[name]}
+    sources = {u if isinstance(u, str) else u[0] for u in (LATER_UNITS[name] if name in LATER_UNITS else OPEN_UNITS[name])}
     return _headers_mtime() > t or any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in sources)
 
 
 def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out: str = LIB, force_later: bool = False) -> str:
-    """Compile (only what changed, unless ``force`` / ``extra_flags``) and link the libraries of both tables.
+    """Compile (only what changed, unless ``force`` / ``extra_flags``) and link the libraries of all tables.
     ``extra_flags`` (e.g. ``-DCOUGH_K1_STAMPS``) build a variant of libcough_amd.so alone at ``out`` with objects of its
     own.  ``force`` rebuilds the nine libraries of ``UNITS`` -- the link list of a forced build is pinned to exactly
-    those nine -- while a library of ``LATER_UNITS`` is rebuilt when it is stale (``later_stale``) or ``force_later`` is
+    those nine -- while a library of ``LATER_UNITS`` or ``OPEN_UNITS`` is rebuilt when it is stale (``later_stale``) or ``force_later`` is
     set; the command line's ``--force`` sets both."""
     if not force and not force_later and not extra_flags and not is_stale():
         return LIB
@@ -132,10 +142,11 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags=(), out
             subprocess.run(cmd, check=True)
         return o
 
-    all_units = {**UNITS, **LATER_UNITS}
+    all_units = {**UNITS, **LATER_UNITS, **OPEN_UNITS}
     targets = {"amd": out}
     if not extra_flags and out == LIB:
-        targets = {**LIBS, **{name: lib for name, lib in LATER_LIBS.items() if force_later or later_stale(name)}}
+        targets = {**LIBS, **{name: lib for name, lib in (*LATER_LIBS.items(), *OPEN_LIBS.items())
+                                if force_later or later_stale(name)}}
     units = [u for name in targets for u in all_units[name]]
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1)) as pool:
         obj = dict(zip(units, pool.map(compile_one, units)))

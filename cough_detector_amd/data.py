@@ -421,6 +421,18 @@ def prepare_group_split(bank: DeviceClipBank, groups: Sequence[int], val_split: 
     return bank.subset(train_idx), bank.subset(val_idx)
 
 
+def _featurise_rows(pre, dev: torch.device, src: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """Features (B, F, T) of B rows of the flat buffer ``src`` as the loader sees them: ``cough_prepare_rows`` (centre
+    crop / zero pad to ``segment_samples``, peak-normalised), then the featuriser.  The loader and the duplicate search
+    (``duplicates.fingerprint_bank``) both judge a clip by this image."""
+    b = lens.numel()
+    seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
+    _lib.check_data(_lib.load_data().cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
+                                                        seg.data_ptr(), pre.segment_samples, _lib.PREP_NORMALIZE,
+                                                        _stream(dev)), "cough_prepare_rows")
+    return pre.featurize_batch(seg, normalize=False)
+
+
 class BatchPlan:
     """The host draws of one batch: ``clips`` (a ``CoughAugClip`` per item, or None without waveform augmentation),
     ``gaussian`` (the ``torch.randn`` rows of ``noise="host"``, or None), ``seed`` (the device generator's) and ``masks``
@@ -592,12 +604,7 @@ class DeviceDataLoader:
 
     def _featurise(self, src: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
         """Unmasked features (B, F, T) of B rows of the flat buffer ``src``: ``cough_prepare_rows``, the featuriser."""
-        pre, dev, b = self.preprocessor, self.bank.device, lens.numel()
-        seg = torch.empty((b, pre.segment_samples), dtype=torch.float32, device=dev)
-        _lib.check_data(_lib.load_data().cough_prepare_rows(src.data_ptr(), offsets.data_ptr(), lens.data_ptr(), b,
-                                                            seg.data_ptr(), pre.segment_samples, _lib.PREP_NORMALIZE,
-                                                            _stream(dev)), "cough_prepare_rows")
-        return pre.featurize_batch(seg, normalize=False)
+        return _featurise_rows(self.preprocessor, self.bank.device, src, offsets, lens)
 
     def _fill_cache(self) -> None:
         n, f_t = len(self.bank), self.feature_shape()
