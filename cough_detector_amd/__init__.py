@@ -23,6 +23,8 @@ from .score import (EventTable, ThresholdSweep, WindowScores, detect_events, det
                     sweep_thresholds)
 from .audit import (LabelIssues, OutOfFoldScores, audit_labels, bank_files, find_label_issues, out_of_fold_scores,
                     stratified_kfold)
+from .scenes import (EventSweep, ScenePlan, TruthTable, compose_scenes, draw_scene_plan, event_report, match_events,
+                     missed_events, pick_threshold, truth_window_ranges)
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -38,4 +40,6 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "stratified_kfold", "out_of_fold_scores", "OutOfFoldScores", "find_label_issues", "LabelIssues", "audit_labels",
            "bank_files", "WindowTable", "find_windows", "slice_bank", "inactive_clips", "write_clips",
            "stratified_group_split", "prepare_group_split", "Fingerprints", "DuplicateTable", "fingerprint_images",
-           "fingerprint_bank", "find_duplicates", "duplicate_groups", "label_conflicts", "drop_duplicates"]
+           "fingerprint_bank", "find_duplicates", "duplicate_groups", "label_conflicts", "drop_duplicates",
+           "ScenePlan", "TruthTable", "EventSweep", "draw_scene_plan", "compose_scenes", "truth_window_ranges",
+           "match_events", "event_report", "pick_threshold", "missed_events"]

@@ -304,8 +304,9 @@ def _later() -> dict:
 
 
 def _open() -> dict:
-    vp, i, s, sz = C.c_void_p, C.c_int, C.c_char_p, C.c_size_t
+    vp, i, s, sz, ll, d = C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_longlong, C.c_double
     match = [vp, vp, i, i, i, i, i]                  # words, live, n, Tw, L, max_err_1024, min_live
+    walk = [vp, vp, i, ll]                           # smoothed, window offsets, n_clips, n_windows
     return {lib.name: lib for lib in (
         # include/cough_amd_dups.h: binary fingerprints of the feature images and the all-pairs matcher
         Library("dups", 1, {
@@ -314,6 +315,15 @@ def _open() -> dict:
             "cough_match_workspace_bytes": (sz, [i, i]),
             "cough_count_matches": (None, match + [vp, vp, vp, sz, vp]),
             "cough_list_matches": (None, match + [vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        }),
+        # include/cough_amd_scenes.h: soundscapes with known cough times, detections matched to them
+        Library("scenes", 1, {
+            "cough_scenes_abi_version": (i, None), "cough_scenes_last_error": (s, None),
+            "cough_span_power": (None, [vp, ll, vp, vp, vp, vp, i, vp, vp]),
+            "cough_scene_gains": (None, [vp, vp, i, vp, i, vp, vp, vp, i, vp, vp]),
+            "cough_mix_scenes": (None, [vp, ll, vp, vp, vp, vp, vp, vp, vp, i, vp, ll, vp, vp, vp, vp, i, vp, i, vp, ll, vp]),
+            "cough_match_events": (None, walk + [vp, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]),
+            "cough_list_event_matches": (None, walk + [d, i, vp, vp, vp, i, vp, vp, ll, vp, vp]),
         }),
     )}
 

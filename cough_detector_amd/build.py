@@ -63,6 +63,9 @@ LATER_UNITS = {
 # the open table (module docstring): a new library is one more entry here and one more record in _lib.OPEN
 OPEN_UNITS = {
     "dups": ("dups.hip",),          # corpus curation: binary fingerprints of the feature images, the all-pairs matcher
+    # soundscapes with known cough times: span powers, gains, the mix, detections matched to events (it includes
+    # csrc/score_walk.h, the walking rule score.hip decides with)
+    "scenes": ("scenes.hip",),
 }
 
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}
