@@ -200,6 +200,22 @@ def _upload(dev: torch.device, i64: np.ndarray, i32: np.ndarray) -> Tuple[torch.
     return d[:n64 * 8].view(torch.int64), d[n64 * 8:n64 * 8 + n32 * 4].view(torch.int32)
 
 
+def _offsets(counts) -> np.ndarray:
+    """int64 ``[n + 1]``: 0, then the running sum of ``counts`` (an array, a host tensor or a list of n >= 0 counts)."""
+    return np.concatenate([[0], np.cumsum(np.asarray(counts), dtype=np.int64)]).astype(np.int64)
+
+
+def _owner(counts) -> np.ndarray:
+    """int64 ``[total]``: the row of every element when row ``k`` holds ``counts[k]`` of them, row after row."""
+    return np.repeat(np.arange(len(counts), dtype=np.int64), np.asarray(counts, dtype=np.int64))
+
+
+def _ragged(counts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(offsets, owner, rank)``: ``_offsets(counts)``, ``_owner(counts)`` and every element's place within its row (int64)."""
+    offsets, owner = _offsets(counts), _owner(counts)
+    return offsets, owner, np.arange(owner.size, dtype=np.int64) - offsets[:-1][owner]
+
+
 def mix_draws(seed: int, b: int, alpha: float) -> Tuple[np.ndarray, np.ndarray]:
     """``(perm int32 (b,), lam float64 (b,))`` of a ``draws="device"`` batch: a permutation, then ``Beta(alpha, alpha)``
     variates, from ``numpy.random.Generator(Philox(key=seed mod 2^64))`` on the host."""
@@ -282,19 +298,56 @@ class DeviceClipBank:
         lengths = [int(c.numel()) for c in clips]
         if lengths and max(lengths) > 2**31 - 1:
             raise ValueError("DeviceClipBank: a clip is longer than 2^31 - 1 samples")
-        self.device = torch.device(device) if device is not None else cuda_device()
         packed = torch.cat(clips) if clips else torch.zeros(0, dtype=torch.float32)
-        self._set(packed.to(self.device), lengths, labels)
+        data = packed.to(torch.device(device) if device is not None else cuda_device())
+        self.device = data.device                # where the data lives: "cuda" has become the current GPU
+        self._set(data, lengths, labels)
 
-    def _set(self, data: torch.Tensor, lengths: List[int], labels: List[int]) -> None:
+    def _set(self, data: torch.Tensor, lengths: Sequence[int], labels: Sequence[int]) -> None:
         self.data = data
         self.lengths = torch.tensor(lengths, dtype=torch.int32)
-        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)[:-1]]) if lengths else [],
-                                    dtype=torch.int64)
+        self.offsets = torch.tensor(_offsets(lengths)[:-1], dtype=torch.int64)
         self.labels = torch.tensor(labels, dtype=torch.int64)
         self.offsets_dev = self.offsets.to(self.device)
         self.lengths_dev = self.lengths.to(self.device)
         self.labels_dev = self.labels.to(self.device)
+
+    @classmethod
+    def from_packed(cls, data: torch.Tensor, lengths: Sequence[int], labels: Sequence[int]) -> "DeviceClipBank":
+        """The bank of samples that are packed already: ``data`` (1-D contiguous float32, where the bank is to live) holds
+        clips of ``lengths`` end to end.  Only what the host knows is checked; nothing is read from the device."""
+        lengths, labels = np.asarray(lengths, dtype=np.int64).reshape(-1), np.asarray(labels, dtype=np.int64).reshape(-1)
+        if data.dim() != 1 or data.dtype != torch.float32:
+            raise ValueError(f"DeviceClipBank.from_packed: data is {data.dtype} {tuple(data.shape)}, not one-dimensional float32")
+        if lengths.size != labels.size:
+            raise ValueError(f"DeviceClipBank.from_packed: {lengths.size} lengths but {labels.size} labels")
+        if int(lengths.sum()) != data.numel():
+            raise ValueError(f"DeviceClipBank.from_packed: lengths of {int(lengths.sum())} samples, data of {data.numel()}")
+        out = object.__new__(cls)
+        out.device = data.device
+        out._set(data, lengths, labels)
+        return out
+
+    def cut(self, clips: np.ndarray, starts, lengths: np.ndarray, labels: Optional[Sequence[int]] = None) -> "DeviceClipBank":
+        """A bank of spans of this one's clips: row ``j`` is samples ``starts[j] .. starts[j] + lengths[j]`` of clip
+        ``clips[j]`` (host int64), labelled ``labels[j]`` or, without ``labels``, as that clip.  ``starts``: an int32 tensor
+        on the bank's device or a host array; ``lengths``: a host array of entries >= 1; the caller sees to it that every
+        span lies inside its clip.  One upload and one launch (``cough_copy_segments``), none without rows; no waiting."""
+        if self.device.type != "cuda":
+            raise RuntimeError(f"DeviceClipBank.cut: the bank lives on {self.device}; the kernels need it on the GPU (there "
+                               "is no CPU fallback)")
+        clips, lengths = np.asarray(clips, dtype=np.int64), np.asarray(lengths)
+        dev, r = self.device, int(clips.size)
+        out = self.from_packed(torch.empty(int(lengths.sum()), dtype=torch.float32, device=dev), lengths,
+                               self.labels.numpy()[clips] if labels is None else labels)
+        if r:
+            on_host = not isinstance(starts, torch.Tensor)
+            i64, i32 = _upload(dev, np.concatenate([self.offsets.numpy()[clips], out.offsets.numpy()]),
+                               np.asarray(starts).astype(np.int32) if on_host else np.zeros(0, np.int32))
+            _lib.check_segments(_lib.load_segments().cough_copy_segments(
+                self.data.data_ptr(), i64[:r].data_ptr(), (i32 if on_host else starts).data_ptr(), out.lengths_dev.data_ptr(),
+                i64[r:].data_ptr(), r, int(lengths.max()), out.data.data_ptr(), _stream(dev)), "cough_copy_segments")
+        return out
 
     def __len__(self) -> int:
         return int(self.labels.numel())
@@ -324,12 +377,9 @@ class DeviceClipBank:
         n = len(self)
         if any(i < -n or i >= n for i in idx):
             raise IndexError(f"DeviceClipBank.subset: indices must lie in 0..{n - 1}")
-        out = object.__new__(DeviceClipBank)
-        out.device = self.device
         parts = [self.clip(i)[0] for i in idx]
         data = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32, device=self.device)
-        out._set(data, [int(self.lengths[i]) for i in idx], [int(self.labels[i]) for i in idx])
-        return out
+        return DeviceClipBank.from_packed(data, [int(self.lengths[i]) for i in idx], [int(self.labels[i]) for i in idx])
 
     @classmethod
     def from_directory(cls, data_dir: str, preprocessor, device=None) -> "DeviceClipBank":
@@ -371,11 +421,8 @@ class DeviceClipBank:
         if len(devices) != 1:
             raise ValueError(f"DeviceClipBank.concat: the banks live on {sorted(str(d) for d in devices)}; they must "
                              "share one device")
-        out = object.__new__(cls)
-        out.device = banks[0].device
-        out._set(torch.cat([b.data for b in banks]), [n for b in banks for n in b.lengths.tolist()],
-                 [v for b in banks for v in b.labels.tolist()])
-        return out
+        return cls.from_packed(torch.cat([b.data for b in banks]), [n for b in banks for n in b.lengths.tolist()],
+                               [v for b in banks for v in b.labels.tolist()])
 
     @classmethod
     def from_esc50(cls, data_dir: str, preprocessor, is_training: bool = True, fold: Optional[int] = None,

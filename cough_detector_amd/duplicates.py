@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import DeviceClipBank, _featurise_rows, _stream, _upload
+from .data import DeviceClipBank, _featurise_rows, _offsets, _stream, _upload
 from .segments import _check_device
 
 ROWS, MAX_FRAMES, HIST_BINS, MAX_CLIPS = 33, 256, 65, 65536   # COUGH_DUPS_ROWS / _MAX_FRAMES / _HIST_BINS / _MAX_CLIPS
@@ -183,7 +183,7 @@ def find_duplicates(fp: Fingerprints, max_lag: int = 8, max_ber: float = 0.25, m
     _lib.check_dups(lib.cough_count_matches(*head, counts_dev.data_ptr(), hist.data_ptr(), ws.data_ptr(), ws_bytes,
                                             _stream(dev)), "cough_count_matches")
     counts = counts_dev.cpu().numpy()                            # the one host read: it sizes the list
-    row_offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+    row_offsets = _offsets(counts)
     rows = int(row_offsets[-1])
     out = torch.empty((5, max(rows, 1)), dtype=torch.int32, device=dev)
     if rows:

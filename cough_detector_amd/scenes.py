@@ -56,7 +56,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import DeviceClipBank, _stream, _upload
+from .data import DeviceClipBank, _offsets, _ragged, _stream, _upload
 from .score import (WindowScores, _check_bank, _check_device, _check_thresholds, _number, debounce_gap)
 
 TILE = 4096                    # COUGH_SCENES_TILE
@@ -233,7 +233,7 @@ class TruthTable:
     @property
     def offsets(self) -> np.ndarray:
         """int64 ``[n + 1]``: recording ``c`` owns the events ``offsets[c] : offsets[c + 1]``."""
-        return np.concatenate([[0], np.cumsum(self.counts, dtype=np.int64)]).astype(np.int64)
+        return _offsets(self.counts)
 
     @classmethod
     def from_intervals(cls, clip, onset, offset, n_clips: Optional[int] = None) -> "TruthTable":
@@ -294,10 +294,8 @@ def span_power(bank: DeviceClipBank, clips, starts, lengths) -> torch.Tensor:
 
 def scene_tiles(lengths: np.ndarray) -> np.ndarray:
     """int32 ``[n_tiles, 2]``: ``(scene, first sample)`` of every tile of ``TILE`` samples, scene by scene."""
-    per = (np.asarray(lengths, dtype=np.int64) + TILE - 1) // TILE
-    scene = np.repeat(np.arange(per.size, dtype=np.int64), per)
-    first = (np.arange(int(per.sum()), dtype=np.int64) - np.concatenate([[0], np.cumsum(per)[:-1]])[scene]) * TILE
-    return np.stack([scene, first], axis=1).astype(np.int32)
+    _, scene, rank = _ragged((np.asarray(lengths, dtype=np.int64) + TILE - 1) // TILE)
+    return np.stack([scene, rank * TILE], axis=1).astype(np.int32)
 
 
 def compose_scenes(backgrounds: DeviceClipBank, events: DeviceClipBank, plan: ScenePlan) -> Tuple[DeviceClipBank, TruthTable]:
@@ -316,16 +314,13 @@ def compose_scenes(backgrounds: DeviceClipBank, events: DeviceClipBank, plan: Sc
         raise ValueError(f"{what}: {tiles.shape[0]} tiles do not fit one launch")
     dev = _check_device(what, backgrounds.device)
     counts = np.bincount(plan.event_scene, minlength=n).astype(np.int64)
-    out = object.__new__(DeviceClipBank)
-    out.device = dev
-    out._set(torch.empty(int(plan.length.sum()), dtype=torch.float32, device=dev), plan.length.tolist(),
-             (counts > 0).astype(np.int64).tolist())
+    out = DeviceClipBank.from_packed(torch.empty(int(plan.length.sum()), dtype=torch.float32, device=dev), plan.length,
+                                     counts > 0)
     used, which = np.unique(plan.event_clip, return_inverse=True)         # every event clip's power once
     p_bg = _spans(backgrounds, plan.background, plan.bg_start, plan.length)
     p_ev = _spans(events, used, np.zeros(used.size, np.int64), el[used])
-    ev_offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     snr_linear = 10.0 ** (plan.snr_db / 10.0)
-    i64, i32 = _upload(dev, np.concatenate([backgrounds.offsets.numpy()[plan.background], out.offsets.numpy(), ev_offsets,
+    i64, i32 = _upload(dev, np.concatenate([backgrounds.offsets.numpy()[plan.background], out.offsets.numpy(), _offsets(counts),
                                             events.offsets.numpy()[plan.event_clip], snr_linear.view(np.int64)]),
                        np.concatenate([bl[plan.background], plan.bg_start, plan.bg_gain.view(np.int32), plan.length,
                                        el[plan.event_clip], plan.onset, plan.event_scene, which,
@@ -465,7 +460,7 @@ def list_matches(scores: WindowScores, truth: TruthTable, threshold: float, debo
         offs, lo_dev, hi_dev, _ = _truth_upload(dev, truth, k_lo, k_hi)
         ev_offs = None
         if per is not None and classes.numel():
-            ev_offs, _ = _upload(dev, np.concatenate([[0], np.cumsum(per)]).astype(np.int64), np.zeros(0, np.int32))
+            ev_offs, _ = _upload(dev, _offsets(per), np.zeros(0, np.int32))
         nw = scores.smoothed.numel()
         _lib.check_scenes(_lib.load_scenes().cough_list_event_matches(
             scores.smoothed.data_ptr() if nw else None, scores.window_offsets_dev.data_ptr(), n, nw, float(t[0]), gap,
@@ -540,20 +535,9 @@ def missed_events(scenes: DeviceClipBank, truth: TruthTable, scores: WindowScore
     if (truth.offset > scenes.lengths.numpy().astype(np.int64)[truth.clip]).any():
         raise ValueError(f"{what}: a truth event reaches past the end of its recording")
     window, _ = list_matches(scores, truth, threshold, debounce_seconds, min_overlap_seconds, collar_seconds)
-    dev = _check_device(what, scenes.device)
+    _check_device(what, scenes.device)
     missed = np.flatnonzero(window.cpu().numpy() < 0)                     # the one host read
-    lengths = (truth.offset - truth.onset)[missed]
-    out = object.__new__(DeviceClipBank)
-    out.device = dev
-    out._set(torch.empty(int(lengths.sum()), dtype=torch.float32, device=dev), lengths.tolist(), [1] * missed.size)
-    if missed.size:
-        e = int(missed.size)
-        i64, i32 = _upload(dev, np.concatenate([scenes.offsets.numpy()[truth.clip[missed]], out.offsets.numpy()]),
-                           truth.onset[missed].astype(np.int32))
-        _lib.check_segments(_lib.load_segments().cough_copy_segments(
-            scenes.data.data_ptr(), i64[:e].data_ptr(), i32.data_ptr(), out.lengths_dev.data_ptr(), i64[e:].data_ptr(), e,
-            int(lengths.max()), out.data.data_ptr(), _stream(dev)), "cough_copy_segments")
-    return out, missed
+    return scenes.cut(truth.clip[missed], truth.onset[missed], (truth.offset - truth.onset)[missed], [1] * missed.size), missed
 
 
 # ------------------------------------------------------------------------------------------------ CLI

@@ -45,7 +45,7 @@ import torch
 
 from . import _lib
 from ._native import cuda_device
-from .data import CLASSES, DeviceClipBank, _stream, _upload
+from .data import CLASSES, DeviceClipBank, _offsets, _owner, _ragged, _stream, _upload
 
 
 @dataclass
@@ -91,7 +91,7 @@ class WindowScores:
             raise ValueError(f"WindowScores.from_probabilities: {tuple(p.shape)} probabilities for {int(per_clip.sum())} windows")
         dev = torch.device(device) if device is not None else (p.device if p.is_cuda else cuda_device())
         _check_device("WindowScores.from_probabilities", dev)
-        offsets = np.concatenate([[0], np.cumsum(per_clip, dtype=np.int64)]).astype(np.int64)
+        offsets = _offsets(per_clip)
         offs_dev, _ = _upload(dev, offsets, np.zeros(0, np.int32))
         p = p.to(device=dev, dtype=torch.float32).contiguous()
         return cls(p, _smooth(p, offs_dev, len(per_clip), w), torch.from_numpy(offsets), offs_dev, int(hop_samples),
@@ -214,11 +214,9 @@ def score_bank(bank: DeviceClipBank, pipeline, hop_duration: float = 0.25, smoot
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
         raise ValueError(f"{what}: batch={batch!r} must be a positive integer")
     dev = _check_device(what, bank.device)
-    per_clip = windows_per_clip(bank.lengths.numpy(), window, hop)
-    offsets = np.concatenate([[0], np.cumsum(per_clip, dtype=np.int64)]).astype(np.int64)
+    offsets, clip, rank = _ragged(windows_per_clip(bank.lengths.numpy(), window, hop))
     n = int(offsets[-1])
-    clip = np.repeat(np.arange(len(bank), dtype=np.int64), per_clip)
-    rows = bank.offsets.numpy()[clip] + (np.arange(n, dtype=np.int64) - offsets[:-1][clip]) * hop
+    rows = bank.offsets.numpy()[clip] + rank * hop
     i64, row_lens = _upload(dev, np.concatenate([offsets, rows]), np.full(n, window, dtype=np.int32))
     offs_dev, rows_dev = i64[:len(bank) + 1], i64[len(bank) + 1:]
     prob = torch.empty(n, dtype=torch.float32, device=dev)
@@ -271,9 +269,8 @@ def detect_events(scores: WindowScores, threshold: float = 0.5, debounce_seconds
     dev, n = _check_device(what, scores.device), len(scores)
     counts = _sweep(scores, t, gap, False)[0].view(-1).cpu()             # the one host read
     per_clip = counts.numpy().astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(per_clip, dtype=np.int64)]).astype(np.int64)
+    offsets, clip = _offsets(per_clip), _owner(per_clip)
     n_events = int(offsets[-1])
-    clip = np.repeat(np.arange(n, dtype=np.int64), per_clip)
     i64, _ = _upload(dev, np.concatenate([offsets, clip]), np.zeros(0, np.int32))
     window = torch.empty(n_events, dtype=torch.int32, device=dev)
     conf = torch.empty(n_events, dtype=torch.float64, device=dev)
@@ -298,19 +295,9 @@ def event_windows(bank: DeviceClipBank, scores: WindowScores, events: EventTable
     _check_bank(what, bank, scores)
     if len(events.counts) != len(bank):
         raise ValueError(f"{what}: the events count {len(events.counts)} recordings, the bank holds {len(bank)}")
-    dev, window, e = _check_device(what, bank.device), scores.window_samples, len(events)
-    clip = np.repeat(np.arange(len(bank), dtype=np.int64), events.counts.numpy().astype(np.int64))
-    out = object.__new__(DeviceClipBank)
-    out.device = dev
-    out._set(torch.empty(e * window, dtype=torch.float32, device=dev), [window] * e, bank.labels.numpy()[clip].tolist())
-    if e:
-        offs, _ = _upload(dev, np.concatenate([bank.offsets.numpy()[clip], np.arange(e, dtype=np.int64) * window]),
-                          np.zeros(0, np.int32))
-        starts = (events.window.to(torch.int64) * scores.hop_samples).to(torch.int32)
-        _lib.check_segments(_lib.load_segments().cough_copy_segments(
-            bank.data.data_ptr(), offs[:e].data_ptr(), starts.data_ptr(), out.lengths_dev.data_ptr(), offs[e:].data_ptr(),
-            e, window, out.data.data_ptr(), _stream(dev)), "cough_copy_segments")
-    return out
+    _check_device(what, bank.device)
+    starts = (events.window.to(torch.int64) * scores.hop_samples).to(torch.int32)
+    return bank.cut(_owner(events.counts), starts, np.full(len(events), scores.window_samples, dtype=np.int64))
 
 
 def detection_report(bank: DeviceClipBank, scores: WindowScores, sweep: ThresholdSweep) -> dict:

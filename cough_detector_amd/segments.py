@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import DeviceClipBank, _stream, _upload
+from .data import DeviceClipBank, _offsets, _owner, _ragged, _stream, _upload
 
 
 @dataclass
@@ -75,19 +75,17 @@ def _frame_energy(bank: DeviceClipBank, frame_length: int, hop_length: int):
     """-> (energy float64 [total frames] on the device, frame offsets on the host (numpy int64 [n + 1]) and on the device)"""
     dev, lib, n = bank.device, _lib.load_segments(), len(bank)
     frames = frame_counts(bank.lengths.numpy(), frame_length, hop_length)
-    frame_offsets = np.concatenate([[0], np.cumsum(frames, dtype=np.int64)]).astype(np.int64)
+    frame_offsets = _offsets(frames)
     energy = torch.empty(int(frame_offsets[-1]), dtype=torch.float64, device=dev)
     if n == 0:
         return energy, frame_offsets, torch.zeros(1, dtype=torch.int64, device=dev)
     tile_frames = lib.cough_frame_energy_tile_frames(frame_length, hop_length)
-    tiles_per_clip = (frames + tile_frames - 1) // tile_frames
-    n_tiles = int(tiles_per_clip.sum())
+    tile_offsets, tile_clip, tile_rank = _ragged((frames + tile_frames - 1) // tile_frames)
+    n_tiles = int(tile_offsets[-1])
     if n_tiles > 2**31 - 1:
         raise ValueError(f"frame_energy: {n_tiles} tiles do not fit one launch; split the bank")
     tiles = np.empty((n_tiles, 2), dtype=np.int32)
-    tiles[:, 0] = np.repeat(np.arange(n, dtype=np.int32), tiles_per_clip)
-    first_tile = np.concatenate([[0], np.cumsum(tiles_per_clip)[:-1]])
-    tiles[:, 1] = (np.arange(n_tiles, dtype=np.int64) - np.repeat(first_tile, tiles_per_clip)) * tile_frames
+    tiles[:, 0], tiles[:, 1] = tile_clip, tile_rank * tile_frames
     offs_dev, tiles_dev = _upload(dev, frame_offsets, tiles.reshape(-1))
     _lib.check_segments(lib.cough_frame_energy(bank.data.data_ptr(), bank.offsets_dev.data_ptr(),
                                                bank.lengths_dev.data_ptr(), offs_dev.data_ptr(), n, tiles_dev.data_ptr(),
@@ -106,24 +104,29 @@ def frame_energy(bank: DeviceClipBank, frame_length: int = 400, hop_length: int 
     return energy, torch.from_numpy(frame_offsets)
 
 
+def _db_ratios(what: str, threshold_db, floor_db, **number) -> Tuple[float, float]:
+    """``(10**(threshold_db/10), 10**(floor_db/10))``, once the two and the further ``number`` (by name) are finite numbers."""
+    for name, v in (("threshold_db", threshold_db), ("floor_db", floor_db), *number.items()):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+            raise ValueError(f"{what}: {name}={v!r} must be a finite number")
+    try:
+        return 10.0 ** (float(threshold_db) / 10.0), 10.0 ** (float(floor_db) / 10.0)
+    except OverflowError:
+        raise ValueError(f"{what}: threshold_db={threshold_db} / floor_db={floor_db} overflow a double") from None
+
+
 def _params(what: str, preprocessor, frame_length=400, hop_length=160, threshold_db=-30.0, floor_db=-60.0,
             min_duration=0.1, max_segments=8):
     frame_length, hop_length = _check_frames(what, frame_length, hop_length)
     if isinstance(max_segments, bool) or not isinstance(max_segments, (int, np.integer)) or \
             not 1 <= max_segments <= _lib.MAX_SEGMENTS:
         raise ValueError(f"{what}: max_segments={max_segments!r} must be an integer in 1..{_lib.MAX_SEGMENTS}")
-    for name, v in (("threshold_db", threshold_db), ("floor_db", floor_db), ("min_duration", min_duration)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-            raise ValueError(f"{what}: {name}={v!r} must be a finite number")
+    ratio, floor = _db_ratios(what, threshold_db, floor_db, min_duration=min_duration)
     if min_duration < 0:
         raise ValueError(f"{what}: min_duration={min_duration} must not be negative")
     seg_len, sr = int(preprocessor.segment_samples), int(preprocessor.sample_rate)
     if seg_len < 1 or sr < 1:
         raise ValueError(f"{what}: the preprocessor's segment_samples={seg_len} and sample_rate={sr} must be positive")
-    try:
-        ratio, floor = 10.0 ** (float(threshold_db) / 10.0), 10.0 ** (float(floor_db) / 10.0)
-    except OverflowError:
-        raise ValueError(f"{what}: threshold_db={threshold_db} / floor_db={floor_db} overflow a double") from None
     min_frames = max(1, math.ceil(float(min_duration) * sr / hop_length))
     if min_frames > 2**31 - 1:
         raise ValueError(f"{what}: min_duration={min_duration} is {min_frames} frames")
@@ -151,34 +154,18 @@ def find_segments(bank: DeviceClipBank, preprocessor, **params) -> SegmentTable:
         min_frames, max_segments, ratio, floor, counts_dev.data_ptr(), starts.data_ptr(), lengths.data_ptr(),
         peak_db.data_ptr(), _stream(dev)), "cough_pick_segments")
     counts = counts_dev.cpu()                                    # the one host read: it sizes the table
-    per_clip = counts.numpy().astype(np.int64)
-    clip = np.repeat(np.arange(n, dtype=np.int64), per_clip)
-    first = np.concatenate([[0], np.cumsum(per_clip)[:-1]])
-    flat = clip * max_segments + (np.arange(clip.size, dtype=np.int64) - np.repeat(first, per_clip))
+    _, clip, rank = _ragged(counts)
+    flat = clip * max_segments + rank
     idx, _ = _upload(dev, np.concatenate([clip, flat]), np.zeros(0, np.int32))
     clip_dev, flat_dev = idx[:clip.size], idx[clip.size:]
     return SegmentTable(clip_dev, starts.view(-1)[flat_dev], lengths.view(-1)[flat_dev], peak_db.view(-1)[flat_dev], counts)
 
 
-def _copy_rows(bank: DeviceClipBank, counts: torch.Tensor, starts: torch.Tensor, seg_len: int) -> DeviceClipBank:
-    """The bank of the rows of a table: ``counts[k]`` (host) rows of source clip ``k``, row ``j`` the ``min(seg_len, n)``
-    samples of its clip from ``starts[j]`` (device int32) on, with that clip's label."""
-    dev = bank.device
-    per_clip = counts.numpy().astype(np.int64)
-    clip = np.repeat(np.arange(len(bank), dtype=np.int64), per_clip)
-    lengths = np.minimum(bank.lengths.numpy()[clip], seg_len).astype(np.int32)      # min(seg_len, n): known to the host
-    dst = np.concatenate([[0], np.cumsum(lengths, dtype=np.int64)]).astype(np.int64)
-    out = object.__new__(DeviceClipBank)
-    out.device = dev
-    out._set(torch.empty(int(dst[-1]), dtype=torch.float32, device=dev), lengths.tolist(),
-             bank.labels.numpy()[clip].tolist())
-    if clip.size:
-        offs, _ = _upload(dev, np.concatenate([bank.offsets.numpy()[clip], dst[:-1]]), np.zeros(0, np.int32))
-        _lib.check_segments(_lib.load_segments().cough_copy_segments(
-            bank.data.data_ptr(), offs[:clip.size].data_ptr(), starts.data_ptr(), out.lengths_dev.data_ptr(),
-            offs[clip.size:].data_ptr(), int(clip.size), int(lengths.max()), out.data.data_ptr(), _stream(dev)),
-            "cough_copy_segments")
-    return out
+def _cut_rows(bank: DeviceClipBank, table, seg_len: int) -> DeviceClipBank:
+    """The bank of the rows of a table: ``table.counts[k]`` (host) rows of source clip ``k``, row ``j`` the ``min(seg_len,
+    n)`` samples of its clip from ``table.start[j]`` (device int32) on, with that clip's label."""
+    clip = _owner(table.counts)
+    return bank.cut(clip, table.start, np.minimum(bank.lengths.numpy()[clip], seg_len))   # min(seg_len, n): known to the host
 
 
 def extract_segments(bank: DeviceClipBank, preprocessor, **params) -> Tuple[DeviceClipBank, SegmentTable]:
@@ -187,4 +174,4 @@ def extract_segments(bank: DeviceClipBank, preprocessor, **params) -> Tuple[Devi
     ``DeviceDataLoader``, ``create_data_loaders``).  A corpus without a segment gives an empty bank.  ``params`` as
     ``find_segments``."""
     table = find_segments(bank, preprocessor, **params)
-    return _copy_rows(bank, table.counts, table.start, int(preprocessor.segment_samples)), table
+    return _cut_rows(bank, table, int(preprocessor.segment_samples)), table

@@ -26,7 +26,6 @@ with ``cough_copy_segments``.  ``table.clip`` names the recording of every clip 
 from __future__ import annotations
 
 import json
-import math
 import wave
 from dataclasses import dataclass
 from pathlib import Path
@@ -36,8 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import CLASSES, DeviceClipBank, _stream, _upload
-from .segments import _check_device, _check_frames, _copy_rows, _frame_energy
+from .data import CLASSES, DeviceClipBank, _offsets, _stream, _upload
+from .segments import _check_device, _check_frames, _cut_rows, _db_ratios, _frame_energy
 
 NO_CAP = 2**31 - 1
 
@@ -79,15 +78,9 @@ def _params(what: str, preprocessor, stride=None, frame_length=400, hop_length=1
     for name, v in (("stride", stride),) + ((("max_per_clip", max_per_clip),) if max_per_clip is not None else ()):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 2**31 - 1:
             raise ValueError(f"{what}: {name}={v!r} must be a positive integer that fits 32 bits")
-    for name, v in (("threshold_db", threshold_db), ("floor_db", floor_db), ("min_active", min_active)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
-            raise ValueError(f"{what}: {name}={v!r} must be a finite number")
+    ratio, floor = _db_ratios(what, threshold_db, floor_db, min_active=min_active)
     if not 0.0 <= min_active <= 1.0:
         raise ValueError(f"{what}: min_active={min_active} must lie in 0..1")
-    try:
-        ratio, floor = 10.0 ** (float(threshold_db) / 10.0), 10.0 ** (float(floor_db) / 10.0)
-    except OverflowError:
-        raise ValueError(f"{what}: threshold_db={threshold_db} / floor_db={floor_db} overflow a double") from None
     return (frame_length, hop_length, seg_len, int(stride), NO_CAP if max_per_clip is None else int(max_per_clip), ratio,
             floor, float(min_active))
 
@@ -109,7 +102,7 @@ def find_windows(bank: DeviceClipBank, preprocessor, stride: Optional[int] = Non
                            torch.zeros(0, dtype=torch.int32))
     lib = _lib.load_slices()
     per_clip = window_counts(bank.lengths.numpy(), seg_len, stride)
-    window_offsets = np.concatenate([[0], np.cumsum(per_clip, dtype=np.int64)]).astype(np.int64)
+    window_offsets = _offsets(per_clip)
     energy, _, offs_dev = _frame_energy(bank, frame_length, hop_length)
     woffs_dev, windows_dev = _upload(dev, window_offsets, per_clip.astype(np.int32))
     total = int(window_offsets[-1])
@@ -120,7 +113,7 @@ def find_windows(bank: DeviceClipBank, preprocessor, stride: Optional[int] = Non
         hop_length, seg_len, stride, cap, ratio, floor, min_active, peak.data_ptr(), clip_active.data_ptr(),
         active.data_ptr(), keep.data_ptr(), counts_dev.data_ptr(), _stream(dev)), "cough_window_activity")
     counts = counts_dev.cpu()                                    # the one host read: it sizes the table
-    row_offsets = np.concatenate([[0], np.cumsum(counts.numpy(), dtype=np.int64)]).astype(np.int64)
+    row_offsets = _offsets(counts)
     rows = int(row_offsets[-1])
     roffs_dev, _ = _upload(dev, row_offsets, np.zeros(0, np.int32))
     clip = torch.empty(rows, dtype=torch.int64, device=dev)
@@ -140,7 +133,7 @@ def slice_bank(bank: DeviceClipBank, preprocessor, **params) -> Tuple[DeviceClip
     + table.length[j]`` of source clip ``table.clip[j]`` with that clip's label -- a bank like any other.  A corpus
     without a kept window gives an empty bank.  ``params`` as ``find_windows``."""
     table = find_windows(bank, preprocessor, **params)
-    return _copy_rows(bank, table.counts, table.start, int(preprocessor.segment_samples)), table
+    return _cut_rows(bank, table, int(preprocessor.segment_samples)), table
 
 
 def inactive_clips(table: WindowTable) -> torch.Tensor:

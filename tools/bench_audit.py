@@ -51,10 +51,7 @@ def test_corpus():
 def device_corpus(count):
     """``count`` clips of 16000 samples generated where they stay, seeds 0 .. count - 1."""
     clips = synth.device_clips(0, count)
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = clips.device
-    bank._set(clips.reshape(-1), [synth.N] * count, [int(s % 6 == 0) for s in range(count)])
-    return bank
+    return cda.DeviceClipBank.from_packed(clips.reshape(-1), [synth.N] * count, [int(s % 6 == 0) for s in range(count)])
 
 
 def parts(bank, pre, a, p_augment, draws, rounds):

@@ -45,10 +45,7 @@ def synthetic_bank(n_clips: int, seed: int) -> cda.DeviceClipBank:
     labels = (rng.random(n_clips) < 0.25).astype(int).tolist()
     total = sum(lengths)
     audio = synth.device_clips(seed, (total + synth.N - 1) // synth.N).reshape(-1)[:total]
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, lengths, labels)
-    return bank
+    return cda.DeviceClipBank.from_packed(audio, lengths, labels)
 
 
 def once(fn) -> float:

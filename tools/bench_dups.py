@@ -65,10 +65,7 @@ def burst_bank(n_clips: int, samples: int, seed: int, chunk: int = 2048) -> cda.
             phase = ((t[None, :] - start) / length).clamp(0.0, 1.0)
             x += level * noise * torch.cos(2.0 * np.pi * freq / 16000.0 * t[None, :]) * torch.sin(np.pi * phase) ** 2
         parts.append(x / x.abs().amax(dim=1, keepdim=True) * 0.8)
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = parts[0].device
-    bank._set(torch.cat(parts).reshape(-1), [samples] * n_clips, [k % 2 for k in range(n_clips)])
-    return bank
+    return cda.DeviceClipBank.from_packed(torch.cat(parts).reshape(-1), [samples] * n_clips, [k % 2 for k in range(n_clips)])
 
 
 def steps_per_pair(tw: int, lags: int) -> int:

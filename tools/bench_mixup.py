@@ -123,9 +123,7 @@ def bench_mix(args, lines) -> None:
 def bench_loader(args, lines) -> None:
     pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
     audio = synth.device_clips(4100, args.clips).reshape(-1)
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, [synth.N] * args.clips, [k % 2 for k in range(args.clips)])
+    bank = cda.DeviceClipBank.from_packed(audio, [synth.N] * args.clips, [k % 2 for k in range(args.clips)])
     lines.append(f"  loader: an epoch of train_epoch_async (SmallTrainer) over {args.clips} clips of {synth.N} samples at batch 32, "
                  "waveform augmentation and SpecAugment at p = 0.5, host clock around the epoch")
     for draws in ("host", "device"):

@@ -221,9 +221,7 @@ def bench_lock(args, lines) -> None:
     # one 32-row batch of the loader, device draws, every row with a pitch coin
     pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
     audio = synth.device_clips(4100, 64).reshape(-1)
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, [synth.N] * 64, [k % 2 for k in range(64)])
+    bank = cda.DeviceClipBank.from_packed(audio, [synth.N] * 64, [k % 2 for k in range(64)])
     loaders = {lock: cda.DeviceDataLoader(bank, pre, batch_size=32, draws="device", generator=torch.Generator().manual_seed(2),
                                           audio_augmentor=cda.AudioAugmentor(p_augment=1.0, pitch=True, phase_lock=lock),
                                           spec_augmentor=cda.SpecAugment(p=0.5)) for lock in (False, True)}
@@ -244,9 +242,7 @@ def bench_lock(args, lines) -> None:
 def bench_loader(args, lines) -> None:
     pre = cda.AudioPreprocessor(device="cuda", **SHIPPED)
     audio = synth.device_clips(4100, args.clips).reshape(-1)
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, [synth.N] * args.clips, [k % 2 for k in range(args.clips)])
+    bank = cda.DeviceClipBank.from_packed(audio, [synth.N] * args.clips, [k % 2 for k in range(args.clips)])
     lines.append(f"  loader: an epoch over {args.clips} clips of {synth.N} samples at batch 32, waveform augmentation and SpecAugment "
                  "at p = 0.5, host clock around the epoch; 'alone' iterates the loader, 'training' feeds train_epoch_async "
                  "(SmallTrainer)")

@@ -40,10 +40,7 @@ SR, HBM_PEAK = 16000, 8.0e12
 
 
 def flat_bank(data: torch.Tensor, lengths, label: int) -> cda.DeviceClipBank:
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = data.device
-    bank._set(data, [int(v) for v in lengths], [label] * len(lengths))
-    return bank
+    return cda.DeviceClipBank.from_packed(data, lengths, [label] * len(lengths))
 
 
 def timed(fn) -> float:

@@ -44,10 +44,7 @@ BATCH = 4096
 def synthetic_bank(n_clips: int, samples: int, seed: int) -> cda.DeviceClipBank:
     total = n_clips * samples
     audio = synth.device_clips(seed, (total + synth.N - 1) // synth.N).reshape(-1)[:total]
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, [samples] * n_clips, [k % 2 for k in range(n_clips)])
-    return bank
+    return cda.DeviceClipBank.from_packed(audio, [samples] * n_clips, [k % 2 for k in range(n_clips)])
 
 
 def host_time(fn) -> float:

@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import cough_detector_amd as cda                                  # noqa: E402
 from cough_detector_amd import _lib, segments as cseg, synth     # noqa: E402
-from cough_detector_amd.data import _stream, _upload              # noqa: E402
+from cough_detector_amd.data import _ragged, _stream, _upload     # noqa: E402
 from cough_detector_amd.hostcpu import bound_torch_threads        # noqa: E402
 
 SHIPPED = dict(use_pcen=False, use_pre_emphasis=False, use_delta_delta=False, use_spectral_contrast=False)
@@ -41,10 +41,7 @@ FRAME, HOP = 400, 160
 def synthetic_bank(n_clips: int, samples: int, seed: int) -> cda.DeviceClipBank:
     total = n_clips * samples
     audio = synth.device_clips(seed, (total + synth.N - 1) // synth.N).reshape(-1)[:total]
-    bank = object.__new__(cda.DeviceClipBank)
-    bank.device = audio.device
-    bank._set(audio, [samples] * n_clips, [k % 2 for k in range(n_clips)])
-    return bank
+    return cda.DeviceClipBank.from_packed(audio, [samples] * n_clips, [k % 2 for k in range(n_clips)])
 
 
 def device_times(fn, warmup: int, repeats: int):
@@ -109,10 +106,8 @@ def main() -> None:
     if "kernel" in args.steps:
         lib = _lib.load_segments()
         tile_frames = lib.cough_frame_energy_tile_frames(FRAME, HOP)
-        per_clip = (frames + tile_frames - 1) // tile_frames
-        tiles = np.empty((int(per_clip.sum()), 2), dtype=np.int32)
-        tiles[:, 0] = np.repeat(np.arange(n, dtype=np.int32), per_clip)
-        tiles[:, 1] = np.concatenate([np.arange(c, dtype=np.int64) * tile_frames for c in per_clip])
+        _, tile_clip, tile_rank = _ragged((frames + tile_frames - 1) // tile_frames)
+        tiles = np.stack([tile_clip, tile_rank * tile_frames], axis=1).astype(np.int32)
         _, tiles_dev = _upload(dev, np.zeros(0, np.int64), tiles.reshape(-1))
         out = torch.empty_like(energy)
 

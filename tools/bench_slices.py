@@ -38,7 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import cough_detector_amd as cda                                  # noqa: E402
 from cough_detector_amd import _lib, segments as cseg, slices as cslices   # noqa: E402
-from cough_detector_amd.data import _stream, _upload              # noqa: E402
+from cough_detector_amd.data import _offsets, _stream, _upload    # noqa: E402
 from cough_detector_amd.hostcpu import bound_torch_threads        # noqa: E402
 import slices_ref                                                 # noqa: E402
 from bench_segments import SHIPPED, synthetic_bank                # noqa: E402
@@ -74,7 +74,7 @@ def kernels(bank, energy, offs_dev, seg_len: int, stride: int, ratio: float, flo
     """Both kernels and the read between them, as ``find_windows`` runs them -> counts on the host."""
     lib, dev, n = _lib.load_slices(), bank.device, len(bank)
     per_clip = cslices.window_counts(bank.lengths.numpy(), seg_len, stride)
-    woffs, _ = _upload(dev, np.concatenate([[0], np.cumsum(per_clip)]).astype(np.int64), np.zeros(0, np.int32))
+    woffs, _ = _upload(dev, _offsets(per_clip), np.zeros(0, np.int32))
     i32 = dict(dtype=torch.int32, device=dev)
     total = int(per_clip.sum())
     peak, clip_active, counts_dev = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, **i32), torch.empty(n, **i32)
@@ -85,7 +85,7 @@ def kernels(bank, energy, offs_dev, seg_len: int, stride: int, ratio: float, flo
         counts_dev.data_ptr(), _stream(dev)), "cough_window_activity")
     counts = counts_dev.cpu()
     rows = int(counts.sum())
-    roffs, _ = _upload(dev, np.concatenate([[0], np.cumsum(counts.numpy(), dtype=np.int64)]).astype(np.int64), np.zeros(0, np.int32))
+    roffs, _ = _upload(dev, _offsets(counts), np.zeros(0, np.int32))
     clip = torch.empty(rows, dtype=torch.int64, device=dev)
     start, length, row_active = torch.empty(rows, **i32), torch.empty(rows, **i32), torch.empty(rows, **i32)
     if rows:
