@@ -15,6 +15,7 @@ from .data import (DeviceClipBank, DeviceDataLoader, create_data_loaders, prepar
 from .draws import augment_rows_drawn, draw_batch
 from .warp import draw_speed, speed_rate_pair, warp_rows
 from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
+from .reverb import RirBank, draw_reverb, reverb_rows, reverberate_bank, synth_rirs
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .slices import WindowTable, find_windows, inactive_clips, slice_bank, write_clips
 from .duplicates import (DuplicateTable, Fingerprints, drop_duplicates, duplicate_groups, find_duplicates, fingerprint_bank,
@@ -42,4 +43,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "stratified_group_split", "prepare_group_split", "Fingerprints", "DuplicateTable", "fingerprint_images",
            "fingerprint_bank", "find_duplicates", "duplicate_groups", "label_conflicts", "drop_duplicates",
            "ScenePlan", "TruthTable", "EventSweep", "draw_scene_plan", "compose_scenes", "truth_window_ranges",
-           "match_events", "event_report", "pick_threshold", "missed_events"]
+           "match_events", "event_report", "pick_threshold", "missed_events",
+           "RirBank", "synth_rirs", "reverb_rows", "draw_reverb", "reverberate_bank"]

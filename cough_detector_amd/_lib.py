@@ -325,6 +325,14 @@ def _open() -> dict:
             "cough_match_events": (None, walk + [vp, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]),
             "cough_list_event_matches": (None, walk + [d, i, vp, vp, vp, i, vp, vp, ll, vp, vp]),
         }),
+        # include/cough_amd_reverb.h: room reverberation, FFT convolution with a prepared bank of impulse responses
+        Library("reverb", 1, {
+            "cough_reverb_abi_version": (i, None), "cough_reverb_last_error": (s, None),
+            "cough_reverb_bank_bytes": (sz, [i]),
+            "cough_reverb_prepare": (None, [vp, C.POINTER(ll), C.POINTER(i), i, vp, sz, vp]),
+            "cough_reverb_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, i, vp]),
+            "cough_draw_reverb": (None, [C.c_ulonglong, i, vp, d, i, vp, vp]),
+        }),
     )}
 
 

@@ -27,6 +27,12 @@ length.  The default ``pitch=False`` changes no result and moves no random strea
 ``pitch=True``) stretches with identity phase locking, which keeps a steady tone's level where the plain vocoder returns
 it at 0.6; it draws nothing, and the default ``phase_lock=False`` is the plain vocoder, bit for bit.
 
+``AudioAugmentor(reverb=RirBank(...))`` adds a step the reference does not have: the clip convolved with a room impulse
+response of the bank (``cough_reverb_rows``, ``cough_detector_amd/reverb.py``), behind the pitch step and before gain,
+gaussian noise and the noise bank -- noise in a room is not convolved with the talker's response.  It keeps the clip's
+length (the tail is dropped).  Its draws (coin, ``random.randrange(len(bank))``) sit behind the pitch step's and before
+the gain's.  The default ``reverb=None`` draws nothing and changes no result, no random stream and no launch.
+
 Differences a caller can observe: results come back where the input lives, as float32.  With ``pitch=False``
 ``pitch_shift`` draws its coin and semitones as the reference does and returns its input unchanged -- the reference's
 own result when sox is absent (its ``except`` branch) -- and ``augment`` never calls it.  The noise bank decodes WAVE files only (``load_wave``); other files
@@ -46,6 +52,7 @@ import torch
 from . import _lib, _tables
 from . import chain as _chain
 from . import pitch as _pitch
+from . import reverb as _reverb
 from . import warp as _warp
 from ._native import cuda_device
 from .preprocessing import load_wave
@@ -155,8 +162,11 @@ def _repeated_length(entry_len: int, target_len: int) -> int:
 class AudioAugmentor:
     def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
                  speed: bool = False, speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
-                 pitch_range: Tuple[int, int] = (-2, 2), phase_lock: bool = False):
+                 pitch_range: Tuple[int, int] = (-2, 2), phase_lock: bool = False, reverb=None):
         self.sample_rate = sample_rate
+        if reverb is not None and not isinstance(reverb, _reverb.RirBank):
+            raise TypeError(f"AudioAugmentor: reverb must be a RirBank or None, got {type(reverb).__name__}")
+        self.reverb = reverb                             # the reverb step's bank of room impulse responses; None: no step
         self.p_augment = p_augment
         self.speed = bool(speed)
         self.speed_range = (float(speed_range[0]), float(speed_range[1]))
@@ -259,6 +269,12 @@ class AudioAugmentor:
             return None
         return random.randint(*(shift_range or self.pitch_range))
 
+    def _draw_reverb(self) -> Optional[int]:
+        """The reverb step's draws: coin, ``random.randrange`` over the bank."""
+        if not self._coin():
+            return None
+        return random.randrange(len(self.reverb))
+
     def _draw_gain(self, gain_range=_GAIN_RANGE) -> Optional[float]:
         return random.uniform(*gain_range) if self._coin() else None
 
@@ -289,12 +305,21 @@ class AudioAugmentor:
         """``draw_item`` with the pitch step: ``(record, rate pair, n', n_steps)``.  With ``pitch=True`` the pitch step
         draws its coin and its semitones behind the speed step and before the gain -- shift, speed, pitch coin,
         semitones, gain, gaussian, bank -- and ``n_steps`` is None when the coin did not fire (0 is a drawn value that
-        shifts nothing).  With ``pitch=False`` it draws nothing and ``n_steps`` is None.  The pitch step keeps ``n'``."""
+        shifts nothing).  With ``pitch=False`` it draws nothing and ``n_steps`` is None.  The pitch step keeps ``n'``.
+        With a ``reverb`` bank this makes ``draw_item_reverb``'s draws and drops the response: call that one."""
+        return self.draw_item_reverb(n)[:4]
+
+    def draw_item_reverb(self, n: int) -> Tuple[_lib.CoughAugClip, Optional[Tuple[int, int]], int, Optional[int], Optional[int]]:
+        """``draw_item_pitched`` with the reverb step: ``(record, rate pair, n', n_steps, rir)``.  With a ``reverb`` bank
+        the step draws its coin and its response behind the pitch step and before the gain -- shift, speed, pitch,
+        reverb coin, ``random.randrange(len(bank))``, gain, gaussian, bank -- and ``rir`` is None when the coin did not
+        fire.  Without a bank it draws nothing and ``rir`` is None.  The reverb step keeps ``n'``."""
         c = self._blank()
         c.shift = self._draw_shift(n)
         pair = self._draw_speed() if self.speed else None         # speed=False: speed_perturbation draws nothing
         n = n if pair is None else _warp.warped_length(n, *pair)
         steps = self._draw_pitch() if self.pitch else None       # pitch=False: pitch_shift is not part of the chain
+        rir = self._draw_reverb() if self.reverb is not None else None      # no bank: the step draws nothing
         gain = self._draw_gain()
         if gain is not None:
             c.gain = gain
@@ -305,7 +330,7 @@ class AudioAugmentor:
             d = self._draw_bank(n)
             if d is not None:
                 c.bank_index, c.bank_start, c.bank_snr_db = d
-        return c, pair, n, steps
+        return c, pair, n, steps, rir
 
     def draw_batch(self, lengths: Sequence[int]) -> List[_lib.CoughAugClip]:
         """The draws of ``augment_batch``: ``draw_clip`` for each clip in order, as a Dataset calls ``augment`` per item."""
@@ -343,17 +368,20 @@ class AudioAugmentor:
 
     def _run_chain(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
                    pairs: Optional[Sequence[Optional[Tuple[int, int]]]], steps: Optional[Sequence[Optional[int]]],
-                   gaussian: Optional[torch.Tensor], seed: int) -> torch.Tensor:
-        """``_run`` behind the speed and pitch steps (``cough_detector_amd/chain.py``): ``cough_warp_rows`` when a speed
+                   gaussian: Optional[torch.Tensor], seed: int,
+                   rirs: Optional[Sequence[Optional[int]]] = None) -> torch.Tensor:
+        """``_run`` behind the speed, pitch and reverb steps (``cough_detector_amd/chain.py``): ``cough_warp_rows`` when a speed
         coin fired (shift and resampling; a row without a pair is copied), ``cough_stretch_rows`` and ``cough_warp_rows``
         when a row has semitones (a row without is copied by both; with ``phase_lock`` the stretch locks the phases of
-        the rows with semitones), then ``cough_augment_waveforms`` on the result with
+        the rows with semitones), ``cough_reverb_rows`` when a row of ``rirs`` (per row a response of the ``reverb`` bank
+        or None; None as a whole without the step) has a response, then ``cough_augment_waveforms`` on the result with
         the records' shifts zeroed and the lengths ``n'``.  ``pairs`` / ``steps`` are None when the step is switched
         off.  Returns (B, max n') with a speed step and (B, N) without.  ``gaussian`` is cut to the width of the rows that
         ``_run`` gets.  When nothing fired the launches are skipped and the path is ``_run``'s."""
         b, n = x.shape
         lens = [int(v) for v in lengths] if lengths is not None else [n] * b
-        plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n, self.phase_lock)
+        plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n, self.phase_lock,
+                                  reverb=rirs)
         width = plans.width if plans.arrays else n
         if gaussian is not None and gaussian.shape[1] != width:
             gaussian = gaussian[:, :width].contiguous()
@@ -363,11 +391,13 @@ class AudioAugmentor:
         dev = cuda_device()
         src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
         a, put = plans.arrays, lambda v: torch.from_numpy(v).to(dev)      # noqa: E731
-        both = "warp" in a and "stretch" in a            # the pitch step then reads the speed step's (B, width) output
+        launches = sum(name in a for name in ("warp", "stretch", "reverb"))
+        both = launches > 1                              # a later step then reads an earlier step's (B, width) output
         speed = (put(a["warp"]), put(a["new_lengths"]) if both else None, plans.width) if "warp" in a else None
         pitch = (put(a["stretch"]), put(a["back"]), plans.stretch_width, plans.width) if "stretch" in a else None
+        reverb = (put(a["reverb"]), self.reverb, plans.width) if "reverb" in a else None
         rows, _, _ = _chain.run(src.reshape(-1), _chain.dense_offsets(b, n, dev), torch.tensor(lens, dtype=torch.int32).to(dev),
-                                speed, pitch, _chain.dense_offsets(b, plans.width, dev) if both else None)
+                                speed, pitch, _chain.dense_offsets(b, plans.width, dev) if both else None, reverb=reverb)
         return self._run(rows, _chain.unshifted(clips), plans.new_lengths, gaussian, seed).to(x.device)
 
     @staticmethod
@@ -458,11 +488,11 @@ class AudioAugmentor:
     def augment(self, waveform: torch.Tensor) -> torch.Tensor:
         """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
         self._one_clip(waveform, "augment")
-        c, pair, n_new, steps = self.draw_item_pitched(waveform.shape[1])
-        if steps or pair is not None:                            # the pitch or the speed step fired: (1, n')
+        c, pair, n_new, steps, rir = self.draw_item_reverb(waveform.shape[1])
+        if steps or pair is not None or rir is not None:         # the pitch, the speed or the reverb step fired: (1, n')
             gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
             return self._run_chain(waveform, [c], None, [pair] if self.speed else None, [steps], gaussian,
-                                   0).to(waveform.dtype)
+                                   0, rirs=[rir] if self.reverb is not None else None).to(waveform.dtype)
         if c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
             return waveform
         return self._single(waveform, c)
@@ -489,10 +519,11 @@ class AudioAugmentor:
             lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
             if len(lengths) != b or any(v < 1 or v > n for v in lengths):
                 raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
-        items = [self.draw_item_pitched(v) for v in (lengths if lengths is not None else [n] * b)]
+        items = [self.draw_item_reverb(v) for v in (lengths if lengths is not None else [n] * b)]
         clips, new_lens = [it[0] for it in items], [it[2] for it in items]
         pairs = [it[1] for it in items] if self.speed else None
         steps = [it[3] for it in items] if self.pitch else None
+        rirs = [it[4] for it in items] if self.reverb is not None else None
         gaussian = None
         if noise == "host":
             # rows of n' samples; _run_chain cuts the matrix to (B, max n') when a speed step fired
@@ -502,7 +533,7 @@ class AudioAugmentor:
                     gaussian[i, :new_lens[i]] = torch.randn(new_lens[i])
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
-        out = self._run_chain(waveforms, clips, lengths, pairs, steps, gaussian, int(seed))
+        out = self._run_chain(waveforms, clips, lengths, pairs, steps, gaussian, int(seed), rirs=rirs)
         return (out, torch.tensor(new_lens, dtype=torch.int32)) if return_lengths else out
 
 
@@ -598,10 +629,11 @@ def create_augmentation_pipeline(sample_rate: int = 16000, noise_dir: Optional[s
                                  use_spec_augment: bool = True, speed: bool = False,
                                  speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
                                  pitch_range: Tuple[int, int] = (-2, 2),
-                                 phase_lock: bool = False) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
+                                 phase_lock: bool = False, reverb=None) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
     """(AudioAugmentor, SpecAugment or None), reference :372-398; ``speed`` / ``speed_range`` / ``pitch`` /
-    ``pitch_range`` / ``phase_lock`` go to the augmentor."""
+    ``pitch_range`` / ``phase_lock`` / ``reverb`` go to the augmentor."""
     audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment, speed=speed,
-                               speed_range=speed_range, pitch=pitch, pitch_range=pitch_range, phase_lock=phase_lock)
+                               speed_range=speed_range, pitch=pitch, pitch_range=pitch_range, phase_lock=phase_lock,
+                               reverb=reverb)
     spec_aug = SpecAugment(p=p_augment) if use_spec_augment else None
     return audio_aug, spec_aug

@@ -66,6 +66,8 @@ OPEN_UNITS = {
     # soundscapes with known cough times: span powers, gains, the mix, detections matched to events (it includes
     # csrc/score_walk.h, the walking rule score.hip decides with)
     "scenes": ("scenes.hip",),
+    # room reverberation: FFT overlap-save with a prepared bank of impulse responses, the transform held in LDS
+    "reverb": ("reverb.hip",),
 }
 
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}

@@ -67,6 +67,7 @@ from . import _lib
 from . import chain as _chain
 from . import draws as _draws
 from . import pitch as _pitch
+from . import reverb as _reverb
 from . import warp as _warp
 from ._native import _stream, cuda_device
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
@@ -487,16 +488,23 @@ class BatchPlan:
     ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None.  With an augmentor that
     has ``speed=True``, ``pairs`` (per item the speed step's ``(orig, new)``, None when its coin did not fire) and
     ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples.  With an augmentor that
-    has ``pitch=True``, ``steps`` (per item the pitch step's semitones, None when its coin did not fire); else None."""
+    has ``pitch=True``, ``steps`` (per item the pitch step's semitones, None when its coin did not fire); else None.
+    With an augmentor that has a ``reverb`` bank, ``rirs`` (per item the reverb step's response, None when its coin did
+    not fire); else None."""
 
-    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps")
+    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps", "rirs")
 
     def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None, pairs=None, new_lengths=None,
-                 steps=None):
+                 steps=None, rirs=None):
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
         self.perm, self.lam = perm, lam
         self.pairs, self.new_lengths = pairs, new_lengths
         self.steps = steps
+        self.rirs = rirs
+
+    def reverbs(self) -> bool:
+        """Whether a reverb step fired in this batch."""
+        return self.rirs is not None and any(r is not None for r in self.rirs)
 
     def pitches(self) -> bool:
         """Whether a pitch step fired (with semitones other than 0) in this batch."""
@@ -607,12 +615,15 @@ class DeviceDataLoader:
         f, t = self.feature_shape()
         speed = self._augments and self.audio_augmentor.speed
         pitch = self._augments and self.audio_augmentor.pitch
+        reverb = self._augments and self.audio_augmentor.reverb is not None
         if self._augments:
             plan.clips = []
             if speed:
                 plan.pairs, plan.new_lengths = [], []
             if pitch:
                 plan.steps = []
+            if reverb:
+                plan.rirs = []
             if self.noise == "host":
                 aug = self.audio_augmentor
                 wide = _warp.drawn_width(max(lengths), aug.speed_range, aug.sample_rate) if speed else max(lengths)
@@ -621,10 +632,12 @@ class DeviceDataLoader:
             plan.masks = []
         for row, n in enumerate(lengths):
             if self._augments:
-                c, pair, n, steps = self.audio_augmentor.draw_item_pitched(n)    # n' from here on; n without a speed step
+                c, pair, n, steps, rir = self.audio_augmentor.draw_item_reverb(n)   # n' from here on; n without a speed step
                 plan.clips.append(c)
                 if pitch:
                     plan.steps.append(steps)
+                if reverb:
+                    plan.rirs.append(rir)
                 if speed:
                     plan.pairs.append(pair)
                     plan.new_lengths.append(n)
@@ -709,9 +722,10 @@ class DeviceDataLoader:
             words.add("coef", mix_coefficients(plan.lam), align8=True)
             words.add("perm", np.asarray(plan.perm).astype(np.int32))
         plans = None
-        if plan.clips is not None and (plan.warps() or plan.pitches()):  # the plans ride behind the other words
+        if plan.clips is not None and (plan.warps() or plan.pitches() or plan.reverbs()):  # the plans ride behind the other words
             plans = _chain.host_plans([c.shift for c in plan.clips], plan.pairs, plan.steps, host_lens,
-                                      self.audio_augmentor.sample_rate, row_len, self.audio_augmentor.phase_lock)
+                                      self.audio_augmentor.sample_rate, row_len, self.audio_augmentor.phase_lock,
+                                      reverb=plan.rirs)
             row_len = plans.width
             for name, array in plans.arrays.items():
                 words.add(name, array, align8=name == "stretch")
@@ -731,7 +745,8 @@ class DeviceDataLoader:
                     d = {name: words.view(i32, name) for name in plans.arrays}
                     speed = (d["warp"], d["new_lengths"], row_len) if "warp" in d else None
                     pitch = (d["stretch"], d["back"], plans.stretch_width, row_len) if "stretch" in d else None
-                    src, _, lens = _chain.run(src, offsets, lens, speed, pitch, out_offsets)
+                    reverb = (d["reverb"], self.audio_augmentor.reverb, row_len) if "reverb" in d else None
+                    src, _, lens = _chain.run(src, offsets, lens, speed, pitch, out_offsets, reverb=reverb)
                     clips, lens_now = _chain.unshifted(plan.clips), plans.new_lengths
                 gaussian = plan.gaussian
                 if gaussian is not None:
@@ -752,7 +767,10 @@ class DeviceDataLoader:
         then shifts and resamples the rows from the bank, and the augmentation runs on its output with the shifts
         cleared.  With ``pitch=True``, ``cough_draw_pitch`` draws the two plans of the pitch step for the (new) lengths;
         ``cough_stretch_rows`` and ``cough_warp_rows`` run behind the speed step -- the time shift rides in the stretch's
-        read when there is no speed step: its word is copied from the records into the stretch plans on the device."""
+        read when there is no speed step: its word is copied from the records into the stretch plans on the device.
+        With a ``reverb`` bank, ``cough_draw_reverb`` draws the rows' responses (Philox counter ``(0, row, 0, 4)``) and
+        ``cough_reverb_rows`` runs behind the pitch step with ``out_len`` the row's current length; the time shift rides in
+        its read when neither of the other steps exists, copied into its plans in the same way."""
         idx, host_lens, words = self._head(indices)
         b, bank = len(idx), self.bank
         row_len = int(host_lens.max())
@@ -776,6 +794,9 @@ class DeviceDataLoader:
                                                                        aug.phase_lock)).to(bank.device)
             pitch = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
                                       self._pitch_table)[:2] + (_pitch.drawn_width(row_len, aug.pitch_range), row_len)
+        reverb = None
+        if aug is not None and aug.reverb is not None:           # out_len is the row's current length: the step keeps it
+            reverb = (_reverb.draw_reverb(seed, lens_new, aug.p_augment, aug.reverb), aug.reverb, row_len)
         clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,
                                          self.feature_shape())
 
@@ -788,10 +809,14 @@ class DeviceDataLoader:
                 elif pitch is not None:          # the records' shift words into the stretch plans' (both lead their struct)
                     pitch[0].view(torch.int32).view(b, _pitch.PLAN_BYTES // 4)[:, 0] = \
                         clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
-                if speed is not None or pitch is not None:
+                elif reverb is not None:         # likewise into the reverb plans' when the reverb reads the bank's rows
+                    reverb[0][:, 0] = clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
+                if speed is not None or pitch is not None or reverb is not None:
                     _warp.clear_shifts(clips)
                 if pitch is not None:            # in a call of its own: the records lose their shift between the steps
                     src, offsets, lens_now = _chain.run(src, offsets, lens_now, pitch=pitch, out_offsets=out_offsets)
+                if reverb is not None:
+                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, reverb=reverb, out_offsets=out_offsets)
                 src, offsets = _draws.augment_rows_drawn(src, offsets, lens_now, row_len, clips, aug, seed), out_offsets
             rows = (src, offsets, lens_now)
         return self._tail(i64, rows, masks, (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
