@@ -16,6 +16,7 @@ from .draws import augment_rows_drawn, draw_batch
 from .warp import draw_speed, speed_rate_pair, warp_rows
 from .pitch import draw_pitch, pitch_rate, pitch_rate_pair, pitch_shift_rows, stretch_rows, stretched_length
 from .reverb import RirBank, draw_reverb, reverb_rows, reverberate_bank, synth_rirs
+from .channel import ChannelBank, channel_rows, draw_channel, synth_channels
 from .segments import SegmentTable, extract_segments, find_segments, frame_energy
 from .slices import WindowTable, find_windows, inactive_clips, slice_bank, write_clips
 from .duplicates import (DuplicateTable, Fingerprints, drop_duplicates, duplicate_groups, find_duplicates, fingerprint_bank,
@@ -44,4 +45,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "fingerprint_bank", "find_duplicates", "duplicate_groups", "label_conflicts", "drop_duplicates",
            "ScenePlan", "TruthTable", "EventSweep", "draw_scene_plan", "compose_scenes", "truth_window_ranges",
            "match_events", "event_report", "pick_threshold", "missed_events",
-           "RirBank", "synth_rirs", "reverb_rows", "draw_reverb", "reverberate_bank"]
+           "RirBank", "synth_rirs", "reverb_rows", "draw_reverb", "reverberate_bank",
+           "ChannelBank", "synth_channels", "channel_rows", "draw_channel"]

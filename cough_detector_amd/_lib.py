@@ -333,6 +333,14 @@ def _open() -> dict:
             "cough_reverb_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, i, vp]),
             "cough_draw_reverb": (None, [C.c_ulonglong, i, vp, d, i, vp, vp]),
         }),
+        # include/cough_amd_channel.h: the capture channel, a biquad cascade out of a prepared bank and a hard clip
+        Library("channel", 1, {
+            "cough_channel_abi_version": (i, None), "cough_channel_last_error": (s, None),
+            "cough_channel_bank_bytes": (sz, [i]),
+            "cough_channel_prepare": (None, [C.POINTER(d), C.POINTER(i), i, vp, sz, vp]),
+            "cough_channel_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, i, vp]),
+            "cough_draw_channel": (None, [C.c_ulonglong, i, d, i, d, d, d, vp, vp]),
+        }),
     )}
 
 

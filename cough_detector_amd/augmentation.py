@@ -33,6 +33,14 @@ gaussian noise and the noise bank -- noise in a room is not convolved with the t
 length (the tail is dropped).  Its draws (coin, ``random.randrange(len(bank))``) sit behind the pitch step's and before
 the gain's.  The default ``reverb=None`` draws nothing and changes no result, no random stream and no launch.
 
+``AudioAugmentor(channel=ChannelBank(...))`` adds the last link: the device that records.  The matrix the augmentation
+kernel wrote goes through a microphone response of the bank and a hard clip relative to the clip's own peak
+(``cough_channel_rows``, ``cough_detector_amd/channel.py``) -- behind the noise, because a microphone hears the room and
+the noise.  Its draws come last in an item's sequence, behind the noise bank's: coin, ``random.randrange(len(bank))``,
+then ``random.random() < p_clip`` gives ``random.uniform(*clip_range)``.  It keeps the clip's length.  The default
+``channel=None`` draws nothing and changes no result, no random stream and no launch; a batch in which no channel coin
+fired runs the launches it ran before.
+
 Differences a caller can observe: results come back where the input lives, as float32.  With ``pitch=False``
 ``pitch_shift`` draws its coin and semitones as the reference does and returns its input unchanged -- the reference's
 own result when sox is absent (its ``except`` branch) -- and ``augment`` never calls it.  The noise bank decodes WAVE files only (``load_wave``); other files
@@ -52,6 +60,7 @@ import torch
 from . import _lib, _tables
 from . import chain as _chain
 from . import pitch as _pitch
+from . import channel as _channel
 from . import reverb as _reverb
 from . import warp as _warp
 from ._native import cuda_device
@@ -162,8 +171,13 @@ def _repeated_length(entry_len: int, target_len: int) -> int:
 class AudioAugmentor:
     def __init__(self, sample_rate: int = 16000, noise_dir: Optional[str] = None, p_augment: float = 0.5,
                  speed: bool = False, speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
-                 pitch_range: Tuple[int, int] = (-2, 2), phase_lock: bool = False, reverb=None):
+                 pitch_range: Tuple[int, int] = (-2, 2), phase_lock: bool = False, reverb=None, channel=None,
+                 p_clip: float = 0.3, clip_range: Tuple[float, float] = (0.25, 1.0)):
         self.sample_rate = sample_rate
+        if channel is not None and not isinstance(channel, _channel.ChannelBank):
+            raise TypeError(f"AudioAugmentor: channel must be a ChannelBank or None, got {type(channel).__name__}")
+        self.channel = channel                           # the channel step's bank of microphone responses; None: no step
+        self.p_clip, self.clip_range = _channel.check_clip(p_clip, clip_range, "AudioAugmentor")
         if reverb is not None and not isinstance(reverb, _reverb.RirBank):
             raise TypeError(f"AudioAugmentor: reverb must be a RirBank or None, got {type(reverb).__name__}")
         self.reverb = reverb                             # the reverb step's bank of room impulse responses; None: no step
@@ -275,6 +289,14 @@ class AudioAugmentor:
             return None
         return random.randrange(len(self.reverb))
 
+    def _draw_channel(self) -> Optional[Tuple[int, float]]:
+        """The channel step's draws: coin, ``random.randrange`` over the bank, the clip coin (``random.random() <
+        p_clip``) and, when that fires, ``random.uniform(*clip_range)``: ``(filter, ratio)``, the ratio 1.0 without a clip."""
+        if not self._coin():
+            return None
+        which = random.randrange(len(self.channel))
+        return which, (random.uniform(*self.clip_range) if random.random() < self.p_clip else 1.0)
+
     def _draw_gain(self, gain_range=_GAIN_RANGE) -> Optional[float]:
         return random.uniform(*gain_range) if self._coin() else None
 
@@ -331,6 +353,25 @@ class AudioAugmentor:
             if d is not None:
                 c.bank_index, c.bank_start, c.bank_snr_db = d
         return c, pair, n, steps, rir
+
+    def draw_item_channel(self, n: int):
+        """``draw_item_reverb`` with the channel step: ``(record, rate pair, n', n_steps, rir, channel)``.  With a
+        ``channel`` bank the step draws last in the item's sequence, behind the noise bank's draws -- the microphone is the
+        last link -- and ``channel`` is ``(filter, clip_ratio)``, or None when the coin did not fire.  Without a bank it
+        draws nothing and ``channel`` is None.  The step keeps ``n'``."""
+        item = self.draw_item_reverb(n)
+        return (*item, self._draw_channel() if self.channel is not None else None)
+
+    def _run_channel(self, x: torch.Tensor, lengths: Sequence[int], plans: Sequence[Optional[Tuple[int, float]]]) -> torch.Tensor:
+        """The channel step on the (B, N) matrix the augmentation kernel wrote: one ``cough_channel_rows`` launch, row b
+        its first ``lengths[b]`` samples with ``plans[b]`` (None: the row is copied); the result where ``x`` lives."""
+        dev = cuda_device()
+        src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        b, n = src.shape
+        host = _channel.plan_array([p if p is not None else (-1, 1.0) for p in plans], len(self.channel))
+        out = _channel.channel_rows(src.reshape(-1), _chain.dense_offsets(b, n, dev), torch.tensor([int(v) for v in lengths],
+                                    dtype=torch.int32).to(dev), host, n, self.channel)
+        return out.to(device=x.device, dtype=x.dtype)
 
     def draw_batch(self, lengths: Sequence[int]) -> List[_lib.CoughAugClip]:
         """The draws of ``augment_batch``: ``draw_clip`` for each clip in order, as a Dataset calls ``augment`` per item."""
@@ -488,14 +529,17 @@ class AudioAugmentor:
     def augment(self, waveform: torch.Tensor) -> torch.Tensor:
         """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
         self._one_clip(waveform, "augment")
-        c, pair, n_new, steps, rir = self.draw_item_reverb(waveform.shape[1])
+        c, pair, n_new, steps, rir, mic = self.draw_item_channel(waveform.shape[1])
         if steps or pair is not None or rir is not None:         # the pitch, the speed or the reverb step fired: (1, n')
             gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
-            return self._run_chain(waveform, [c], None, [pair] if self.speed else None, [steps], gaussian,
-                                   0, rirs=[rir] if self.reverb is not None else None).to(waveform.dtype)
-        if c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
-            return waveform
-        return self._single(waveform, c)
+            out = self._run_chain(waveform, [c], None, [pair] if self.speed else None, [steps], gaussian,
+                                  0, rirs=[rir] if self.reverb is not None else None).to(waveform.dtype)
+        elif c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
+            out = waveform
+        else:
+            out = self._single(waveform, c)
+        # the channel step hears what the kernel wrote: the room and the noise
+        return out if mic is None else self._run_channel(out, [out.shape[1]], [mic])
 
     def augment_batch(self, waveforms: torch.Tensor, lengths=None, noise: str = "device",
                       seed: Optional[int] = None, return_lengths: bool = False):
@@ -519,7 +563,7 @@ class AudioAugmentor:
             lengths = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
             if len(lengths) != b or any(v < 1 or v > n for v in lengths):
                 raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
-        items = [self.draw_item_reverb(v) for v in (lengths if lengths is not None else [n] * b)]
+        items = [self.draw_item_channel(v) for v in (lengths if lengths is not None else [n] * b)]
         clips, new_lens = [it[0] for it in items], [it[2] for it in items]
         pairs = [it[1] for it in items] if self.speed else None
         steps = [it[3] for it in items] if self.pitch else None
@@ -534,6 +578,8 @@ class AudioAugmentor:
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
         out = self._run_chain(waveforms, clips, lengths, pairs, steps, gaussian, int(seed), rirs=rirs)
+        if any(it[5] is not None for it in items):       # no channel coin fired: the launches of a batch without the step
+            out = self._run_channel(out, new_lens, [it[5] for it in items])
         return (out, torch.tensor(new_lens, dtype=torch.int32)) if return_lengths else out
 
 
@@ -629,11 +675,12 @@ def create_augmentation_pipeline(sample_rate: int = 16000, noise_dir: Optional[s
                                  use_spec_augment: bool = True, speed: bool = False,
                                  speed_range: Tuple[float, float] = (0.9, 1.1), pitch: bool = False,
                                  pitch_range: Tuple[int, int] = (-2, 2),
-                                 phase_lock: bool = False, reverb=None) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
+                                 phase_lock: bool = False, reverb=None, channel=None, p_clip: float = 0.3,
+                                 clip_range: Tuple[float, float] = (0.25, 1.0)) -> Tuple[AudioAugmentor, Optional[SpecAugment]]:
     """(AudioAugmentor, SpecAugment or None), reference :372-398; ``speed`` / ``speed_range`` / ``pitch`` /
-    ``pitch_range`` / ``phase_lock`` / ``reverb`` go to the augmentor."""
+    ``pitch_range`` / ``phase_lock`` / ``reverb`` / ``channel`` / ``p_clip`` / ``clip_range`` go to the augmentor."""
     audio_aug = AudioAugmentor(sample_rate=sample_rate, noise_dir=noise_dir, p_augment=p_augment, speed=speed,
                                speed_range=speed_range, pitch=pitch, pitch_range=pitch_range, phase_lock=phase_lock,
-                               reverb=reverb)
+                               reverb=reverb, channel=channel, p_clip=p_clip, clip_range=clip_range)
     spec_aug = SpecAugment(p=p_augment) if use_spec_augment else None
     return audio_aug, spec_aug

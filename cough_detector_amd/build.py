@@ -68,6 +68,8 @@ OPEN_UNITS = {
     "scenes": ("scenes.hip",),
     # room reverberation: FFT overlap-save with a prepared bank of impulse responses, the transform held in LDS
     "reverb": ("reverb.hip",),
+    # the capture channel: a biquad cascade per row, run block-parallel by a scan over the workgroup, and the hard clip
+    "channel": ("channel.hip",),
 }
 
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}

@@ -67,6 +67,7 @@ from . import _lib
 from . import chain as _chain
 from . import draws as _draws
 from . import pitch as _pitch
+from . import channel as _channel
 from . import reverb as _reverb
 from . import warp as _warp
 from ._native import _stream, cuda_device
@@ -490,17 +491,23 @@ class BatchPlan:
     ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples.  With an augmentor that
     has ``pitch=True``, ``steps`` (per item the pitch step's semitones, None when its coin did not fire); else None.
     With an augmentor that has a ``reverb`` bank, ``rirs`` (per item the reverb step's response, None when its coin did
-    not fire); else None."""
+    not fire); else None.  With an augmentor that has a ``channel`` bank, ``channels`` (per item the channel step's
+    ``(filter, clip_ratio)``, None when its coin did not fire); else None."""
 
-    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps", "rirs")
+    __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps", "rirs", "channels")
 
     def __init__(self, clips=None, gaussian=None, seed=0, masks=None, perm=None, lam=None, pairs=None, new_lengths=None,
-                 steps=None, rirs=None):
+                 steps=None, rirs=None, channels=None):
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
         self.perm, self.lam = perm, lam
         self.pairs, self.new_lengths = pairs, new_lengths
         self.steps = steps
         self.rirs = rirs
+        self.channels = channels
+
+    def mics(self) -> bool:
+        """Whether a channel step fired in this batch."""
+        return self.channels is not None and any(c is not None for c in self.channels)
 
     def reverbs(self) -> bool:
         """Whether a reverb step fired in this batch."""
@@ -616,8 +623,11 @@ class DeviceDataLoader:
         speed = self._augments and self.audio_augmentor.speed
         pitch = self._augments and self.audio_augmentor.pitch
         reverb = self._augments and self.audio_augmentor.reverb is not None
+        channel = self._augments and self.audio_augmentor.channel is not None
         if self._augments:
             plan.clips = []
+            if channel:
+                plan.channels = []
             if speed:
                 plan.pairs, plan.new_lengths = [], []
             if pitch:
@@ -632,8 +642,10 @@ class DeviceDataLoader:
             plan.masks = []
         for row, n in enumerate(lengths):
             if self._augments:
-                c, pair, n, steps, rir = self.audio_augmentor.draw_item_reverb(n)   # n' from here on; n without a speed step
+                c, pair, n, steps, rir, mic = self.audio_augmentor.draw_item_channel(n)   # n' from here on; n without a speed step
                 plan.clips.append(c)
+                if channel:
+                    plan.channels.append(mic)
                 if pitch:
                     plan.steps.append(steps)
                 if reverb:
@@ -729,6 +741,9 @@ class DeviceDataLoader:
             row_len = plans.width
             for name, array in plans.arrays.items():
                 words.add(name, array, align8=name == "stretch")
+        if plan.clips is not None and plan.mics():       # the channel step's plans ride in the same upload
+            mics = _channel.plan_array([c if c is not None else (-1, 1.0) for c in plan.channels], len(self.audio_augmentor.channel))
+            words.add("channel", mics.view(np.int32).reshape(-1, 2))
         i64, i32 = self._send(idx, row_len, words)
 
         rows = None
@@ -754,6 +769,9 @@ class DeviceDataLoader:
                         gaussian = gaussian[:, :row_len].contiguous()
                     gaussian = gaussian.to(dev, non_blocking=True)
                 src, offsets = self.audio_augmentor._run(src, clips, lens_now, gaussian, plan.seed), out_offsets
+                if "channel" in words:           # the microphone hears the room and the noise: on the kernel's matrix, in place
+                    _channel.channel_rows(src.view(-1), offsets, lens, words.view(i32, "channel"), row_len,
+                                          self.audio_augmentor.channel, out=src)
             rows = (src, offsets, lens)
         return self._tail(i64, rows, words.view(i32, "masks") if n_masks else None,
                           (words.view(i32, "coef"), words.view(i32, "perm")) if plan.perm is not None else None)
@@ -770,7 +788,9 @@ class DeviceDataLoader:
         read when there is no speed step: its word is copied from the records into the stretch plans on the device.
         With a ``reverb`` bank, ``cough_draw_reverb`` draws the rows' responses (Philox counter ``(0, row, 0, 4)``) and
         ``cough_reverb_rows`` runs behind the pitch step with ``out_len`` the row's current length; the time shift rides in
-        its read when neither of the other steps exists, copied into its plans in the same way."""
+        its read when neither of the other steps exists, copied into its plans in the same way.  With a ``channel`` bank,
+        ``cough_draw_channel`` draws the rows' plans (Philox counter ``(0, row, 0, 5)``) and ``cough_channel_rows`` runs on
+        the matrix the augmentation kernel wrote, in place."""
         idx, host_lens, words = self._head(indices)
         b, bank = len(idx), self.bank
         row_len = int(host_lens.max())
@@ -818,6 +838,9 @@ class DeviceDataLoader:
                 if reverb is not None:
                     src, offsets, lens_now = _chain.run(src, offsets, lens_now, reverb=reverb, out_offsets=out_offsets)
                 src, offsets = _draws.augment_rows_drawn(src, offsets, lens_now, row_len, clips, aug, seed), out_offsets
+                if aug.channel is not None:
+                    mics = _channel.draw_channel(seed, b, aug.p_augment, aug.channel, aug.p_clip, aug.clip_range, bank.device)
+                    _channel.channel_rows(src.view(-1), offsets, lens_now, mics, row_len, aug.channel, out=src)
             rows = (src, offsets, lens_now)
         return self._tail(i64, rows, masks, (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
 
