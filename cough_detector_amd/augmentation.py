@@ -201,6 +201,7 @@ class AudioAugmentor:
         self._bank_lengths: List[int] = []
         self._bank_dev = None
         self._bank_tables = None                         # (device, int64 offsets, int32 lengths) on the device
+        self._pitch_table: Optional[torch.Tensor] = None     # cough_draw_pitch's table, on the device
         if noise_dir and Path(noise_dir).exists():
             self._load_noise_samples(noise_dir)
 
@@ -312,30 +313,30 @@ class AudioAugmentor:
         return k, start, random.uniform(*snr_range)
 
     def draw_clip(self, n: int) -> _lib.CoughAugClip:
-        """One ``augment`` call's draws for a clip of ``n`` samples (reference :249-268): ``draw_item``'s record."""
-        return self.draw_item(n)[0]
+        """One ``augment`` call's draws for a clip of ``n`` samples (reference :249-268): the item's record."""
+        return self.draw_item_channel(n).record
 
     def draw_item(self, n: int) -> Tuple[_lib.CoughAugClip, Optional[Tuple[int, int]], int]:
-        """``(record, rate pair, n')`` of one ``augment`` call on a clip of ``n`` samples.  With ``speed=True`` the speed
-        step draws between the shift and the gain -- its place in the chain -- and the noise-bank step, which crops
-        ``n'`` samples, is drawn for the warped length ``n'``; the record's shift is the one drawn for ``n``.  The pair is
-        None (and ``n' = n``) when the step is switched off or its coin did not fire.  With ``pitch=True`` this makes
-        ``draw_item_pitched``'s draws and drops the semitones: call that one."""
-        return self.draw_item_pitched(n)[:3]
+        """``(record, rate pair, n')``: the first three fields of ``draw_item_channel``, as a plain tuple."""
+        return self.draw_item_channel(n)[:3]
 
     def draw_item_pitched(self, n: int) -> Tuple[_lib.CoughAugClip, Optional[Tuple[int, int]], int, Optional[int]]:
-        """``draw_item`` with the pitch step: ``(record, rate pair, n', n_steps)``.  With ``pitch=True`` the pitch step
-        draws its coin and its semitones behind the speed step and before the gain -- shift, speed, pitch coin,
-        semitones, gain, gaussian, bank -- and ``n_steps`` is None when the coin did not fire (0 is a drawn value that
-        shifts nothing).  With ``pitch=False`` it draws nothing and ``n_steps`` is None.  The pitch step keeps ``n'``.
-        With a ``reverb`` bank this makes ``draw_item_reverb``'s draws and drops the response: call that one."""
-        return self.draw_item_reverb(n)[:4]
+        """``(record, rate pair, n', n_steps)``: the first four fields of ``draw_item_channel``, as a plain tuple."""
+        return self.draw_item_channel(n)[:4]
 
     def draw_item_reverb(self, n: int) -> Tuple[_lib.CoughAugClip, Optional[Tuple[int, int]], int, Optional[int], Optional[int]]:
-        """``draw_item_pitched`` with the reverb step: ``(record, rate pair, n', n_steps, rir)``.  With a ``reverb`` bank
-        the step draws its coin and its response behind the pitch step and before the gain -- shift, speed, pitch,
-        reverb coin, ``random.randrange(len(bank))``, gain, gaussian, bank -- and ``rir`` is None when the coin did not
-        fire.  Without a bank it draws nothing and ``rir`` is None.  The reverb step keeps ``n'``."""
+        """``(record, rate pair, n', n_steps, rir)``: the first five fields of ``draw_item_channel``, as a plain tuple."""
+        return self.draw_item_channel(n)[:5]
+
+    def draw_item_channel(self, n: int) -> _chain.ItemDraw:
+        """All draws of one ``augment`` call on a clip of ``n`` samples, in the chain's order -- shift, speed, pitch,
+        reverb, gain, gaussian, noise bank, channel -- as ``chain.ItemDraw``: ``(record, pair, length, steps, rir,
+        channel)``.  A step that is switched off draws nothing and leaves None; so does, behind its coin, a step whose
+        coin did not fire.  ``speed=True``: the noise-bank step, which crops ``n'`` samples, is drawn for the warped
+        length ``n'`` (``length``; ``n`` without a pair); the record's shift is the one drawn for ``n``.  ``pitch=True``:
+        coin and semitones (0 is a drawn value that shifts nothing).  A ``reverb`` bank: coin and
+        ``random.randrange(len(bank))``.  Neither changes ``n'``.  A ``channel`` bank: ``(filter, clip_ratio)``.  Every
+        other draw method (``draw_clip``, ``draw_batch``, ``draw_item*``) calls this one and so consumes the channel's draws too."""
         c = self._blank()
         c.shift = self._draw_shift(n)
         pair = self._draw_speed() if self.speed else None         # speed=False: speed_perturbation draws nothing
@@ -352,26 +353,25 @@ class AudioAugmentor:
             d = self._draw_bank(n)
             if d is not None:
                 c.bank_index, c.bank_start, c.bank_snr_db = d
-        return c, pair, n, steps, rir
-
-    def draw_item_channel(self, n: int):
-        """``draw_item_reverb`` with the channel step: ``(record, rate pair, n', n_steps, rir, channel)``.  With a
-        ``channel`` bank the step draws last in the item's sequence, behind the noise bank's draws -- the microphone is the
-        last link -- and ``channel`` is ``(filter, clip_ratio)``, or None when the coin did not fire.  Without a bank it
-        draws nothing and ``channel`` is None.  The step keeps ``n'``."""
-        item = self.draw_item_reverb(n)
-        return (*item, self._draw_channel() if self.channel is not None else None)
+        mic = self._draw_channel() if self.channel is not None else None     # no bank: the step draws nothing
+        return tuple.__new__(_chain.ItemDraw, (c, pair, n, steps, rir, mic))  # per item: skips the Python-level __new__
 
     def _run_channel(self, x: torch.Tensor, lengths: Sequence[int], plans: Sequence[Optional[Tuple[int, float]]]) -> torch.Tensor:
-        """The channel step on the (B, N) matrix the augmentation kernel wrote: one ``cough_channel_rows`` launch, row b
-        its first ``lengths[b]`` samples with ``plans[b]`` (None: the row is copied); the result where ``x`` lives."""
+        """The channel step on the (B, N) matrix the kernel wrote (``chain.finish`` into a new matrix: ``src`` is ``x`` itself
+        when ``x`` is float32 on the device), row b its first ``lengths[b]`` samples with ``plans[b]`` (None: a copy)."""
         dev = cuda_device()
         src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
         b, n = src.shape
-        host = _channel.plan_array([p if p is not None else (-1, 1.0) for p in plans], len(self.channel))
-        out = _channel.channel_rows(src.reshape(-1), _chain.dense_offsets(b, n, dev), torch.tensor([int(v) for v in lengths],
-                                    dtype=torch.int32).to(dev), host, n, self.channel)
+        mics = torch.from_numpy(_chain.channel_plans(plans, len(self.channel))).to(dev)
+        out = _chain.finish(src, _chain.dense_offsets(b, n, dev), torch.tensor([int(v) for v in lengths], dtype=torch.int32).to(dev),
+                            mics, self.channel)
         return out.to(device=x.device, dtype=x.dtype)
+
+    def pitch_table(self, dev: torch.device) -> torch.Tensor:
+        """``cough_draw_pitch``'s table on the device, uploaded once; the stretch mode rides in its entries."""
+        if self._pitch_table is None or self._pitch_table.device != dev:
+            self._pitch_table = torch.from_numpy(_pitch.step_table(self.pitch_range, self.sample_rate, self.phase_lock)).to(dev)
+        return self._pitch_table
 
     def draw_batch(self, lengths: Sequence[int]) -> List[_lib.CoughAugClip]:
         """The draws of ``augment_batch``: ``draw_clip`` for each clip in order, as a Dataset calls ``augment`` per item."""
@@ -409,16 +409,13 @@ class AudioAugmentor:
 
     def _run_chain(self, x: torch.Tensor, clips: List[_lib.CoughAugClip], lengths: Optional[Sequence[int]],
                    pairs: Optional[Sequence[Optional[Tuple[int, int]]]], steps: Optional[Sequence[Optional[int]]],
-                   gaussian: Optional[torch.Tensor], seed: int,
-                   rirs: Optional[Sequence[Optional[int]]] = None) -> torch.Tensor:
-        """``_run`` behind the speed, pitch and reverb steps (``cough_detector_amd/chain.py``): ``cough_warp_rows`` when a speed
-        coin fired (shift and resampling; a row without a pair is copied), ``cough_stretch_rows`` and ``cough_warp_rows``
-        when a row has semitones (a row without is copied by both; with ``phase_lock`` the stretch locks the phases of
-        the rows with semitones), ``cough_reverb_rows`` when a row of ``rirs`` (per row a response of the ``reverb`` bank
-        or None; None as a whole without the step) has a response, then ``cough_augment_waveforms`` on the result with
-        the records' shifts zeroed and the lengths ``n'``.  ``pairs`` / ``steps`` are None when the step is switched
-        off.  Returns (B, max n') with a speed step and (B, N) without.  ``gaussian`` is cut to the width of the rows that
-        ``_run`` gets.  When nothing fired the launches are skipped and the path is ``_run``'s."""
+                   gaussian: Optional[torch.Tensor], seed: int, rirs: Optional[Sequence[Optional[int]]] = None) -> torch.Tensor:
+        """``_run`` behind the speed, pitch and reverb steps (``chain.host_plans`` has the rules, ``chain.run`` the
+        launches): ``cough_warp_rows`` when a speed coin fired, ``cough_stretch_rows`` and ``cough_warp_rows`` when a row
+        has semitones, ``cough_reverb_rows`` when a row of ``rirs`` has a response, then ``cough_augment_waveforms`` on
+        the result with the records' shifts zeroed and the lengths ``n'``.  ``pairs`` / ``steps`` / ``rirs`` are None
+        when the step is switched off.  Returns (B, max n') with a speed step and (B, N) without.  ``gaussian`` is cut to
+        the width of the rows that ``_run`` gets.  When nothing fired the launches are skipped and the path is ``_run``'s."""
         b, n = x.shape
         lens = [int(v) for v in lengths] if lengths is not None else [n] * b
         plans = _chain.host_plans([c.shift for c in clips], pairs, steps, lens, self.sample_rate, n, self.phase_lock,
@@ -431,14 +428,9 @@ class AudioAugmentor:
             return out[:, :plans.width].contiguous() if pairs is not None else out
         dev = cuda_device()
         src = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        a, put = plans.arrays, lambda v: torch.from_numpy(v).to(dev)      # noqa: E731
-        launches = sum(name in a for name in ("warp", "stretch", "reverb"))
-        both = launches > 1                              # a later step then reads an earlier step's (B, width) output
-        speed = (put(a["warp"]), put(a["new_lengths"]) if both else None, plans.width) if "warp" in a else None
-        pitch = (put(a["stretch"]), put(a["back"]), plans.stretch_width, plans.width) if "stretch" in a else None
-        reverb = (put(a["reverb"]), self.reverb, plans.width) if "reverb" in a else None
+        go = _chain.launches(plans, lambda name: torch.from_numpy(plans.arrays[name]).to(dev), self)
         rows, _, _ = _chain.run(src.reshape(-1), _chain.dense_offsets(b, n, dev), torch.tensor(lens, dtype=torch.int32).to(dev),
-                                speed, pitch, _chain.dense_offsets(b, plans.width, dev) if both else None, reverb=reverb)
+                                go.speed, go.pitch, _chain.dense_offsets(b, plans.width, dev) if go.chained else None, reverb=go.reverb)
         return self._run(rows, _chain.unshifted(clips), plans.new_lengths, gaussian, seed).to(x.device)
 
     @staticmethod
@@ -529,17 +521,18 @@ class AudioAugmentor:
     def augment(self, waveform: torch.Tensor) -> torch.Tensor:
         """The reference's chain on one (1, N) clip (:249-268) in one launch; the input itself when no step fired."""
         self._one_clip(waveform, "augment")
-        c, pair, n_new, steps, rir, mic = self.draw_item_channel(waveform.shape[1])
-        if steps or pair is not None or rir is not None:         # the pitch, the speed or the reverb step fired: (1, n')
-            gaussian = torch.randn((1, n_new), dtype=torch.float32) if c.gaussian else None
-            out = self._run_chain(waveform, [c], None, [pair] if self.speed else None, [steps], gaussian,
-                                  0, rirs=[rir] if self.reverb is not None else None).to(waveform.dtype)
+        item = self.draw_item_channel(waveform.shape[1])
+        c = item.record
+        if item.steps or item.pair is not None or item.rir is not None:     # the pitch, the speed or the reverb step fired: (1, n')
+            gaussian = torch.randn((1, item.length), dtype=torch.float32) if c.gaussian else None
+            out = self._run_chain(waveform, [c], None, [item.pair] if self.speed else None, [item.steps], gaussian,
+                                  0, rirs=[item.rir] if self.reverb is not None else None).to(waveform.dtype)
         elif c.shift == 0 and c.gain == 1.0 and not c.gaussian and c.bank_index < 0:
             out = waveform
         else:
             out = self._single(waveform, c)
         # the channel step hears what the kernel wrote: the room and the noise
-        return out if mic is None else self._run_channel(out, [out.shape[1]], [mic])
+        return out if item.channel is None else self._run_channel(out, [out.shape[1]], [item.channel])
 
     def augment_batch(self, waveforms: torch.Tensor, lengths=None, noise: str = "device",
                       seed: Optional[int] = None, return_lengths: bool = False):
@@ -564,10 +557,8 @@ class AudioAugmentor:
             if len(lengths) != b or any(v < 1 or v > n for v in lengths):
                 raise ValueError(f"augment_batch: need {b} lengths in 1..{n}")
         items = [self.draw_item_channel(v) for v in (lengths if lengths is not None else [n] * b)]
-        clips, new_lens = [it[0] for it in items], [it[2] for it in items]
-        pairs = [it[1] for it in items] if self.speed else None
-        steps = [it[3] for it in items] if self.pitch else None
-        rirs = [it[4] for it in items] if self.reverb is not None else None
+        col = _chain.columns(items, self)
+        clips, new_lens = col["clips"], [it.length for it in items]
         gaussian = None
         if noise == "host":
             # rows of n' samples; _run_chain cuts the matrix to (B, max n') when a speed step fired
@@ -577,9 +568,9 @@ class AudioAugmentor:
                     gaussian[i, :new_lens[i]] = torch.randn(new_lens[i])
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item()) if noise == "device" else 0
-        out = self._run_chain(waveforms, clips, lengths, pairs, steps, gaussian, int(seed), rirs=rirs)
-        if any(it[5] is not None for it in items):       # no channel coin fired: the launches of a batch without the step
-            out = self._run_channel(out, new_lens, [it[5] for it in items])
+        out = self._run_chain(waveforms, clips, lengths, col["pairs"], col["steps"], gaussian, int(seed), rirs=col["rirs"])
+        if any(it.channel is not None for it in items):  # no channel coin fired: the launches of a batch without the step
+            out = self._run_channel(out, new_lens, col["channels"])
         return (out, torch.tensor(new_lens, dtype=torch.int32)) if return_lengths else out
 
 

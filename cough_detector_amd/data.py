@@ -35,20 +35,14 @@ reference's distributions but are not its random stream (the masks are drawn in 
 masks (one more launch, ``cough_mix_batch``), and the loader then yields ``(features, soft targets (B, 2) float32)``,
 which the trainers' soft-target steps, ``train_epoch_async`` and ``fit`` take as they are.
 
-An ``AudioAugmentor(speed=True)`` adds the speed step to a training batch (``cough_detector_amd/warp.py``): one more
-launch, ``cough_warp_rows``, reads the clips in place from the bank, shifts and resamples each by its own rate pair, and
-the rest of the chain and ``cough_prepare_rows`` then work on the warped rows and their new lengths ``n'``.  With
-``draws="host"`` the per-row plans and ``n'`` travel with the batch's pinned upload (a batch in which no speed coin
-fired runs the launches it ran before); with ``draws="device"`` ``cough_draw_speed`` draws them first, the output is as
-wide as the slowest factor can make the longest row, and nothing is read back.
-
-An ``AudioAugmentor(pitch=True)`` adds the pitch step behind it (``cough_detector_amd/pitch.py``): two more launches,
-``cough_stretch_rows`` and ``cough_warp_rows``, which keep every row's length.  Without a speed step the stretch reads
-the clips in place from the bank and applies the time shift.  With ``draws="host"`` the two plans per row travel with
-the pinned upload (a batch in which no pitch coin fired runs the launches it ran before); with ``draws="device"``
-``cough_draw_pitch`` draws them, and the stretched rows are as wide as the largest number of semitones can make the
-longest row.  The augmentor's ``phase_lock`` is the stretch's mode for the rows with semitones: it rides in the host's
-stretch plans or in the table ``cough_draw_pitch`` reads, and changes neither the draws nor the launches.
+An ``AudioAugmentor`` with ``speed=True``, ``pitch=True``, a ``reverb`` or a ``channel`` bank adds that step's launches
+to a training batch: ``cough_warp_rows``; ``cough_stretch_rows`` and ``cough_warp_rows``; ``cough_reverb_rows``; and,
+behind the augmentation kernel, ``cough_channel_rows``.  The first of them reads the clips in place from the bank and
+applies the time shift; the rest of the batch works on the rows' new lengths ``n'``.  With ``draws="host"`` the plans
+travel with the batch's pinned upload, and a batch in which a step's coin never fired runs the launches it ran before;
+with ``draws="device"`` the plans are drawn on the device first, the rows are as wide as the slowest speed factor can
+make the longest one, and nothing is read back.  The loader names none of these steps: the chain lives in
+``cough_detector_amd/chain.py``; a new step is added there, in the augmentor's one draw method, and as a ``BatchPlan`` column.
 """
 from __future__ import annotations
 
@@ -65,11 +59,6 @@ from torch.utils.data import RandomSampler, WeightedRandomSampler
 
 from . import _lib
 from . import chain as _chain
-from . import draws as _draws
-from . import pitch as _pitch
-from . import channel as _channel
-from . import reverb as _reverb
-from . import warp as _warp
 from ._native import _stream, cuda_device
 from .augmentation import AudioAugmentor, MixUp, SpecAugment, mask_images, mix_batch_rows, mix_coefficients
 
@@ -486,13 +475,11 @@ class BatchPlan:
     """The host draws of one batch: ``clips`` (a ``CoughAugClip`` per item, or None without waveform augmentation),
     ``gaussian`` (the ``torch.randn`` rows of ``noise="host"``, or None), ``seed`` (the device generator's) and ``masks``
     (per item the ``[(axis, start, end)]`` of SpecAugment, empty when its coin did not fire; None without it); with a
-    ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None.  With an augmentor that
-    has ``speed=True``, ``pairs`` (per item the speed step's ``(orig, new)``, None when its coin did not fire) and
-    ``new_lengths`` (per item ``n'``); else None.  ``gaussian`` rows then hold ``n'`` samples.  With an augmentor that
-    has ``pitch=True``, ``steps`` (per item the pitch step's semitones, None when its coin did not fire); else None.
-    With an augmentor that has a ``reverb`` bank, ``rirs`` (per item the reverb step's response, None when its coin did
-    not fire); else None.  With an augmentor that has a ``channel`` bank, ``channels`` (per item the channel step's
-    ``(filter, clip_ratio)``, None when its coin did not fire); else None."""
+    ``MixUp``, ``perm`` (the batch's ``torch.randperm``) and ``lam`` (its float64 λ), else None.  One column per optional
+    step of the augmentor (``chain.columns``), None as a whole when the step is switched off and None at an item whose
+    coin did not fire: ``pairs`` (the speed step's ``(orig, new)``) with ``new_lengths`` (per item ``n'``; ``gaussian``
+    rows then hold ``n'`` samples), ``steps`` (the pitch step's semitones), ``rirs`` (the reverb step's response) and
+    ``channels`` (the channel step's ``(filter, clip_ratio)``)."""
 
     __slots__ = ("clips", "gaussian", "seed", "masks", "perm", "lam", "pairs", "new_lengths", "steps", "rirs", "channels")
 
@@ -501,9 +488,7 @@ class BatchPlan:
         self.clips, self.gaussian, self.seed, self.masks = clips, gaussian, seed, masks
         self.perm, self.lam = perm, lam
         self.pairs, self.new_lengths = pairs, new_lengths
-        self.steps = steps
-        self.rirs = rirs
-        self.channels = channels
+        self.steps, self.rirs, self.channels = steps, rirs, channels
 
     def mics(self) -> bool:
         """Whether a channel step fired in this batch."""
@@ -583,7 +568,6 @@ class DeviceDataLoader:
         self._cache: Optional[torch.Tensor] = None
         self.draws = draws
         self.last_epoch_seed: Optional[int] = None
-        self._pitch_table: Optional[torch.Tensor] = None     # cough_draw_pitch's table, on the device
 
     def _mask_slots(self) -> List[int]:
         s = self.spec_augmentor
@@ -618,52 +602,31 @@ class DeviceDataLoader:
     def _draw_items(self, plan: BatchPlan, indices: Sequence[int]) -> BatchPlan:
         if not (self._augments or self._masks):
             return plan
-        lengths = [int(self.bank.lengths[i]) for i in indices]
+        lengths = self.bank.lengths.numpy()[np.asarray(indices, dtype=np.int64)].tolist()    # one gather, not a tensor read per item
         f, t = self.feature_shape()
-        speed = self._augments and self.audio_augmentor.speed
-        pitch = self._augments and self.audio_augmentor.pitch
-        reverb = self._augments and self.audio_augmentor.reverb is not None
-        channel = self._augments and self.audio_augmentor.channel is not None
-        if self._augments:
-            plan.clips = []
-            if channel:
-                plan.channels = []
-            if speed:
-                plan.pairs, plan.new_lengths = [], []
-            if pitch:
-                plan.steps = []
-            if reverb:
-                plan.rirs = []
-            if self.noise == "host":
-                aug = self.audio_augmentor
-                wide = _warp.drawn_width(max(lengths), aug.speed_range, aug.sample_rate) if speed else max(lengths)
-                plan.gaussian = torch.zeros((len(indices), wide), dtype=torch.float32, pin_memory=self._pinned())
-        if self._masks:
+        draw = self.audio_augmentor.draw_item_channel if self._augments else None
+        spec = self.spec_augmentor if self._masks else None
+        items = []
+        if spec is not None:
             plan.masks = []
+        if self._augments and self.noise == "host":      # as wide as the speed step can make the longest row
+            plan.gaussian = torch.zeros((len(indices), _chain.drawn_width(max(lengths), self.audio_augmentor)),
+                                        dtype=torch.float32, pin_memory=self.bank.device.type == "cuda")
         for row, n in enumerate(lengths):
-            if self._augments:
-                c, pair, n, steps, rir, mic = self.audio_augmentor.draw_item_channel(n)   # n' from here on; n without a speed step
-                plan.clips.append(c)
-                if channel:
-                    plan.channels.append(mic)
-                if pitch:
-                    plan.steps.append(steps)
-                if reverb:
-                    plan.rirs.append(rir)
-                if speed:
-                    plan.pairs.append(pair)
-                    plan.new_lengths.append(n)
-                if c.gaussian and plan.gaussian is not None:
-                    plan.gaussian[row, :n] = torch.randn(n)
-            if self._masks:
-                fired = not (random.random() > self.spec_augmentor.p)
-                plan.masks.append(self.spec_augmentor.draw_masks(f, t) if fired else [])
-        if self._augments and self.noise == "device":
-            plan.seed = int(torch.randint(0, 2**62, (1,)).item())
+            if draw is not None:
+                item = draw(n)
+                items.append(item)
+                if plan.gaussian is not None and item.record.gaussian:
+                    plan.gaussian[row, :item.length] = torch.randn(item.length)      # n' samples; n without a speed step
+            if spec is not None:
+                fired = not (random.random() > spec.p)
+                plan.masks.append(spec.draw_masks(f, t) if fired else [])
+        if self._augments:                               # one column per step that is switched on, None for the others
+            for name, column in _chain.columns(items, self.audio_augmentor).items():
+                setattr(plan, name, column)
+            if self.noise == "device":
+                plan.seed = int(torch.randint(0, 2**62, (1,)).item())
         return plan
-
-    def _pinned(self) -> bool:
-        return self.bank.device.type == "cuda"
 
     # ------------------------------------------------------------------ device side: five launches
     def _mask_arrays(self, masks: List[list]) -> np.ndarray:
@@ -733,116 +696,59 @@ class DeviceDataLoader:
         if plan.perm is not None:
             words.add("coef", mix_coefficients(plan.lam), align8=True)
             words.add("perm", np.asarray(plan.perm).astype(np.int32))
-        plans = None
-        if plan.clips is not None and (plan.warps() or plan.pitches() or plan.reverbs()):  # the plans ride behind the other words
-            plans = _chain.host_plans([c.shift for c in plan.clips], plan.pairs, plan.steps, host_lens,
-                                      self.audio_augmentor.sample_rate, row_len, self.audio_augmentor.phase_lock,
-                                      reverb=plan.rirs)
+        aug, plans = self.audio_augmentor, None
+        if plan.clips is not None and (plan.warps() or plan.pitches() or plan.reverbs() or plan.mics()):
+            plans = _chain.host_plans([c.shift for c in plan.clips], plan.pairs, plan.steps, host_lens, aug.sample_rate,
+                                      row_len, aug.phase_lock, reverb=plan.rirs, channel=plan.channels,
+                                      n_channels=len(aug.channel or ()))
             row_len = plans.width
-            for name, array in plans.arrays.items():
+            for name, array in plans.arrays.items():     # the plans ride behind the other words
                 words.add(name, array, align8=name == "stretch")
-        if plan.clips is not None and plan.mics():       # the channel step's plans ride in the same upload
-            mics = _channel.plan_array([c if c is not None else (-1, 1.0) for c in plan.channels], len(self.audio_augmentor.channel))
-            words.add("channel", mics.view(np.int32).reshape(-1, 2))
         i64, i32 = self._send(idx, row_len, words)
 
         rows = None
         if not self.cache_features:
             src, offsets, lens, out_offsets = bank.data, i64[:b], words.view(i32, "lengths"), i64[b:2 * b]
             if plan.clips is not None:
-                if plans is None:                # cough_augment_waveforms takes a matrix
+                go = _chain.launches(plans, lambda name: words.view(i32, name), aug, keep=True)
+                if not go.front:                 # no launch in front of the kernel: cough_augment_waveforms takes a matrix
                     src = torch.empty((b, row_len), dtype=torch.float32, device=dev)
                     _lib.check_data(_lib.load_data().cough_gather_rows(bank.data.data_ptr(), offsets.data_ptr(),
                                                                        lens.data_ptr(), b, src.data_ptr(), row_len, row_len,
                                                                        _stream(dev)), "cough_gather_rows")
                     clips, lens_now = plan.clips, host_lens
                 else:                            # read in place from the bank; the first launch shifts the rows
-                    d = {name: words.view(i32, name) for name in plans.arrays}
-                    speed = (d["warp"], d["new_lengths"], row_len) if "warp" in d else None
-                    pitch = (d["stretch"], d["back"], plans.stretch_width, row_len) if "stretch" in d else None
-                    reverb = (d["reverb"], self.audio_augmentor.reverb, row_len) if "reverb" in d else None
-                    src, _, lens = _chain.run(src, offsets, lens, speed, pitch, out_offsets, reverb=reverb)
+                    src, _, lens = _chain.run(src, offsets, lens, go.speed, go.pitch, out_offsets, reverb=go.reverb)
                     clips, lens_now = _chain.unshifted(plan.clips), plans.new_lengths
                 gaussian = plan.gaussian
                 if gaussian is not None:
                     if gaussian.shape[1] != row_len:                 # drawn for the widest that the speed step can give
                         gaussian = gaussian[:, :row_len].contiguous()
                     gaussian = gaussian.to(dev, non_blocking=True)
-                src, offsets = self.audio_augmentor._run(src, clips, lens_now, gaussian, plan.seed), out_offsets
-                if "channel" in words:           # the microphone hears the room and the noise: on the kernel's matrix, in place
-                    _channel.channel_rows(src.view(-1), offsets, lens, words.view(i32, "channel"), row_len,
-                                          self.audio_augmentor.channel, out=src)
+                src, offsets = aug._run(src, clips, lens_now, gaussian, plan.seed), out_offsets
+                if go.channel is not None:       # the microphone hears the room and the noise: in place on the kernel's matrix
+                    _chain.finish(src, offsets, lens, go.channel, aug.channel, out=src)
             rows = (src, offsets, lens)
         return self._tail(i64, rows, words.view(i32, "masks") if n_masks else None,
                           (words.view(i32, "coef"), words.view(i32, "perm")) if plan.perm is not None else None)
 
     def launch_batch_drawn(self, indices: Sequence[int], seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
-        gaussian noise): draw, augment the rows in place in the bank, ``cough_prepare_rows``, the featuriser, and
-        ``cough_mask_images`` when there are masks.  The result equals ``launch_batch(indices, plan)`` for the
-        ``BatchPlan`` that holds the same records and masks with ``seed`` as its noise seed.  With an augmentor that has
-        ``speed=True``, ``cough_draw_speed`` runs first and the records are drawn for the new lengths; ``cough_warp_rows``
-        then shifts and resamples the rows from the bank, and the augmentation runs on its output with the shifts
-        cleared.  With ``pitch=True``, ``cough_draw_pitch`` draws the two plans of the pitch step for the (new) lengths;
-        ``cough_stretch_rows`` and ``cough_warp_rows`` run behind the speed step -- the time shift rides in the stretch's
-        read when there is no speed step: its word is copied from the records into the stretch plans on the device.
-        With a ``reverb`` bank, ``cough_draw_reverb`` draws the rows' responses (Philox counter ``(0, row, 0, 4)``) and
-        ``cough_reverb_rows`` runs behind the pitch step with ``out_len`` the row's current length; the time shift rides in
-        its read when neither of the other steps exists, copied into its plans in the same way.  With a ``channel`` bank,
-        ``cough_draw_channel`` draws the rows' plans (Philox counter ``(0, row, 0, 5)``) and ``cough_channel_rows`` runs on
-        the matrix the augmentation kernel wrote, in place."""
+        gaussian noise) by ``chain.run_drawn``, then ``cough_prepare_rows``, the featuriser, and ``cough_mask_images`` when
+        there are masks.  The result equals ``launch_batch(indices, plan)`` for the ``BatchPlan`` that holds the same draws
+        with ``seed`` as its noise seed.  The rows are sized for the slowest speed factor: no draw is read back."""
         idx, host_lens, words = self._head(indices)
-        b, bank = len(idx), self.bank
-        row_len = int(host_lens.max())
+        b, aug = len(idx), self.audio_augmentor if self._augments else None
         if self._mixes:
             perm, lam = mix_draws(seed, b, self.mixup.alpha)
             words.add("coef", mix_coefficients(lam), align8=True)
             words.add("perm", perm)
-        aug = self.audio_augmentor if self._augments else None
-        if aug is not None and aug.speed:        # wide enough for the slowest factor: the draws are never read back
-            row_len = _warp.drawn_width(row_len, aug.speed_range, aug.sample_rate)
+        row_len = _chain.drawn_width(int(host_lens.max()), aug)
         i64, i32 = self._send(idx, row_len, words)
-        lens, out_offsets = words.view(i32, "lengths"), i64[b:2 * b]
-        speed = pitch = None
-        lens_new = lens
-        if aug is not None and aug.speed:
-            speed = _warp.draw_speed(seed, lens, aug.p_augment, aug.speed_range, aug.sample_rate) + (row_len,)
-            lens_new = speed[1]
-        if aug is not None and aug.pitch:
-            if self._pitch_table is None:        # the augmentor's stretch mode rides in the table's entries
-                self._pitch_table = torch.from_numpy(_pitch.step_table(aug.pitch_range, aug.sample_rate,
-                                                                       aug.phase_lock)).to(bank.device)
-            pitch = _pitch.draw_pitch(seed, lens_new, aug.p_augment, aug.pitch_range, aug.sample_rate,
-                                      self._pitch_table)[:2] + (_pitch.drawn_width(row_len, aug.pitch_range), row_len)
-        reverb = None
-        if aug is not None and aug.reverb is not None:           # out_len is the row's current length: the step keeps it
-            reverb = (_reverb.draw_reverb(seed, lens_new, aug.p_augment, aug.reverb), aug.reverb, row_len)
-        clips, masks = _draws.draw_batch(seed, lens_new, aug, self.spec_augmentor if self._n_masks else None,
-                                         self.feature_shape())
-
-        rows = None
-        if not self.cache_features:
-            src, offsets, lens_now = bank.data, i64[:b], lens
-            if clips is not None:
-                if speed is not None:
-                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, speed=speed, out_offsets=out_offsets)
-                elif pitch is not None:          # the records' shift words into the stretch plans' (both lead their struct)
-                    pitch[0].view(torch.int32).view(b, _pitch.PLAN_BYTES // 4)[:, 0] = \
-                        clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
-                elif reverb is not None:         # likewise into the reverb plans' when the reverb reads the bank's rows
-                    reverb[0][:, 0] = clips.view(torch.int32).view(b, _draws.CLIP_BYTES // 4)[:, 0]
-                if speed is not None or pitch is not None or reverb is not None:
-                    _warp.clear_shifts(clips)
-                if pitch is not None:            # in a call of its own: the records lose their shift between the steps
-                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, pitch=pitch, out_offsets=out_offsets)
-                if reverb is not None:
-                    src, offsets, lens_now = _chain.run(src, offsets, lens_now, reverb=reverb, out_offsets=out_offsets)
-                src, offsets = _draws.augment_rows_drawn(src, offsets, lens_now, row_len, clips, aug, seed), out_offsets
-                if aug.channel is not None:
-                    mics = _channel.draw_channel(seed, b, aug.p_augment, aug.channel, aug.p_clip, aug.clip_range, bank.device)
-                    _channel.channel_rows(src.view(-1), offsets, lens_now, mics, row_len, aug.channel, out=src)
-            rows = (src, offsets, lens_now)
-        return self._tail(i64, rows, masks, (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
+        rows, masks = _chain.run_drawn(seed, self.bank.data, i64[:b], words.view(i32, "lengths"), i64[b:2 * b], row_len, aug,
+                                       self.spec_augmentor if self._n_masks else None, self.feature_shape())
+        return self._tail(i64, None if self.cache_features else rows, masks,      # cached features: no augmentor ran
+                          (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         indices = self.epoch_indices()

@@ -15,13 +15,15 @@ reference draws its masks in float32 (``torch.rand(1)``); here they are drawn in
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import TYPE_CHECKING, Optional, Tuple
 
 import torch
 
 from . import _lib
 from ._native import _on_gpu, _stream
-from .augmentation import AudioAugmentor, SpecAugment
+
+if TYPE_CHECKING:                                # the augmentors run the chain, which launches through this module
+    from .augmentation import AudioAugmentor, SpecAugment
 
 CLIP_BYTES = C.sizeof(_lib.CoughAugClip)        # 40: one cough_aug_clip
 

@@ -2,7 +2,9 @@
 
 ``recording()`` wraps the Python entry points of the chain's launches for the duration of a block -- ``warp.warp_rows``,
 ``pitch.stretch_rows``, ``reverb.reverb_rows``, ``AudioAugmentor._run`` and ``draws.augment_rows_drawn`` -- the way
-``tests/test_gpu_reverb.py`` wraps ``reverb_rows``.  ``pitch_shift_rows`` stays as it is: its two launches appear as
+``tests/test_gpu_reverb.py`` wraps ``reverb_rows``.  ``recording(channel=True)`` also wraps ``channel.channel_rows``, the
+launch behind the augmentation kernel, as a link of kind ``channel``; it is off by default, so ``check_trace``'s callers
+see the links in front of it and no other.  ``pitch_shift_rows`` stays as it is: its two launches appear as
 ``stretch`` and ``back``.  For every call it keeps host copies of the rows the call was given (cut out of ``src`` by its
 offsets and lengths), the lengths, the plans read back from the device after the call, the records of the augmentation
 link, and the output matrix -- a link in the form ``tests/chain_ref.py`` describes.  A plain helper, not a fixture.
@@ -12,6 +14,7 @@ import contextlib
 import numpy as np
 import torch
 
+from cough_detector_amd import channel as cch
 from cough_detector_amd import draws as cdraws
 from cough_detector_amd import pitch as cpitch
 from cough_detector_amd import reverb as crev
@@ -37,8 +40,9 @@ def _bank(aug):
 
 
 @contextlib.contextmanager
-def recording():
-    """-> the list that receives one link per launch, in order, while the block runs."""
+def recording(channel=False):
+    """-> the list that receives one link per launch, in order, while the block runs.  ``channel``: record
+    ``channel_rows`` too (its rows are cut out before the call: it may write in place)."""
     trace = []
     real = dict(warp=cwarp.warp_rows, stretch=cpitch.stretch_rows, reverb=crev.reverb_rows, run=AudioAugmentor._run,
                 drawn=cdraws.augment_rows_drawn)
@@ -85,10 +89,22 @@ def recording():
                           gaussian=None, bank=_bank(aug)))
         return res
 
+    def channel_rows(packed, offsets, lengths, plans, width, bank, out=None):
+        rows = _cut(packed, offsets, lengths)
+        res = real["channel"](packed, offsets, lengths, plans, width, bank, out=out)
+        p = np.ascontiguousarray(_host(plans)).view(np.int32).reshape(-1, 2)
+        trace.append(dict(kind="channel", rows=rows, lengths=_host(lengths).astype(np.int64), shift=np.zeros(len(p), np.int64),
+                          param=[(int(f), float(r)) for f, r in zip(p[:, 0], p[:, 1].copy().view(np.float32))], out=_host(res)))
+        return res
+
     cwarp.warp_rows, cpitch.stretch_rows, crev.reverb_rows = warp_rows, stretch_rows, reverb_rows
+    if channel:
+        real["channel"], cch.channel_rows = cch.channel_rows, channel_rows
     AudioAugmentor._run, cdraws.augment_rows_drawn = run, augment_rows_drawn
     try:
         yield trace
     finally:
         cwarp.warp_rows, cpitch.stretch_rows, crev.reverb_rows = real["warp"], real["stretch"], real["reverb"]
         AudioAugmentor._run, cdraws.augment_rows_drawn = real["run"], real["drawn"]
+        if channel:
+            cch.channel_rows = real["channel"]
