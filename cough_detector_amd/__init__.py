@@ -27,6 +27,8 @@ from .audit import (LabelIssues, OutOfFoldScores, audit_labels, bank_files, find
                     stratified_kfold)
 from .scenes import (EventSweep, ScenePlan, TruthTable, compose_scenes, draw_scene_plan, event_report, match_events,
                      missed_events, pick_threshold, truth_window_ranges)
+from .windows import (ComposedWindowLoader, WindowLabels, WindowPlan, compose_windows, draw_window_plan, edge_margin,
+                      scene_window_bank, window_labels)
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -46,4 +48,6 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "ScenePlan", "TruthTable", "EventSweep", "draw_scene_plan", "compose_scenes", "truth_window_ranges",
            "match_events", "event_report", "pick_threshold", "missed_events",
            "RirBank", "synth_rirs", "reverb_rows", "draw_reverb", "reverberate_bank",
-           "ChannelBank", "synth_channels", "channel_rows", "draw_channel"]
+           "ChannelBank", "synth_channels", "channel_rows", "draw_channel",
+           "WindowPlan", "WindowLabels", "draw_window_plan", "edge_margin", "compose_windows", "ComposedWindowLoader",
+           "window_labels", "scene_window_bank"]

@@ -341,6 +341,11 @@ def _open() -> dict:
             "cough_channel_rows": (None, [vp, vp, vp, i, vp, vp, i, vp, i, vp]),
             "cough_draw_channel": (None, [C.c_ulonglong, i, d, i, d, d, d, vp, vp]),
         }),
+        # include/cough_amd_windows.h: a batch of training windows composed in one launch
+        Library("windows", 1, {
+            "cough_windows_abi_version": (i, None), "cough_windows_last_error": (s, None),
+            "cough_compose_windows": (None, [vp, ll, vp, vp, i, vp, ll, vp, vp, vp, i, vp, i, i, vp, vp, vp, vp]),
+        }),
     )}
 
 

@@ -70,6 +70,8 @@ OPEN_UNITS = {
     "reverb": ("reverb.hip",),
     # the capture channel: a biquad cascade per row, run block-parallel by a scan over the workgroup, and the hard clip
     "channel": ("channel.hip",),
+    # training windows composed per batch: background power, gains and the mix of up to four events per row, one launch
+    "windows": ("windows.hip",),
 }
 
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}
