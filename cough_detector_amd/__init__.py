@@ -29,6 +29,7 @@ from .scenes import (EventSweep, ScenePlan, TruthTable, compose_scenes, draw_sce
                      missed_events, pick_threshold, truth_window_ranges)
 from .windows import (ComposedWindowLoader, WindowLabels, WindowPlan, compose_windows, draw_window_plan, edge_margin,
                       scene_window_bank, window_labels)
+from .windows import compose_window_records, draw_window_records, snr_levels, train_windows
 
 __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "CoughDetectorResidual",
            "CoughDetector", "CoughDetectorSmall", "ConvBlock",
@@ -50,4 +51,5 @@ __all__ = ["AudioPreprocessor", "RealtimePreprocessor", "create_preprocessor", "
            "RirBank", "synth_rirs", "reverb_rows", "draw_reverb", "reverberate_bank",
            "ChannelBank", "synth_channels", "channel_rows", "draw_channel",
            "WindowPlan", "WindowLabels", "draw_window_plan", "edge_margin", "compose_windows", "ComposedWindowLoader",
-           "window_labels", "scene_window_bank"]
+           "window_labels", "scene_window_bank",
+           "train_windows", "draw_window_records", "compose_window_records", "snr_levels"]

@@ -346,6 +346,12 @@ def _open() -> dict:
             "cough_windows_abi_version": (i, None), "cough_windows_last_error": (s, None),
             "cough_compose_windows": (None, [vp, ll, vp, vp, i, vp, ll, vp, vp, vp, i, vp, i, i, vp, vp, vp, vp]),
         }),
+        # include/cough_amd_windraw.h: a batch's window plans and labels drawn on the device
+        Library("windraw", 1, {
+            "cough_windraw_abi_version": (i, None), "cough_windraw_last_error": (s, None),
+            "cough_draw_window_plans": (None, [C.c_ulonglong, i, i, vp, i, vp, i, vp, i, vp, i, d, i, i, d, d, d, vp, i, i, d,
+                                               vp, vp, vp]),
+        }),
     )}
 
 

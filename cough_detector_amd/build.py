@@ -72,6 +72,8 @@ OPEN_UNITS = {
     "channel": ("channel.hip",),
     # training windows composed per batch: background power, gains and the mix of up to four events per row, one launch
     "windows": ("windows.hip",),
+    # the window plans of a batch drawn on the device: one thread per row writes the composer's record and the label
+    "windraw": ("windraw.hip",),
 }
 
 LIBS = {name: os.path.join(HERE, _named("libcough_amd", name, ".so")) for name in UNITS}

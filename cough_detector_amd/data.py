@@ -666,12 +666,17 @@ class DeviceDataLoader:
         return _upload(bank.device, np.concatenate([bank.offsets.numpy()[idx], np.arange(len(idx), dtype=np.int64) * row_len,
                                                     bank.labels.numpy()[idx], idx]), words.array())
 
-    def _tail(self, i64: torch.Tensor, rows, masks, mix) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _tail(self, i64: torch.Tensor, rows, masks, mix, targets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """What both modes end with: the features of ``rows`` -- ``(src, offsets, lens)``, the batch's waveforms after the
         chain -- or, when ``rows`` is None, the cached ones; ``cough_mask_images`` with the device arrays ``masks`` (None:
-        no masks); ``cough_mix_batch`` with ``mix``, the upload's ``(coefficients, permutation)`` (None: no MixUp)."""
+        no masks); ``cough_mix_batch`` with ``mix``, the upload's ``(coefficients, permutation)`` (None: no MixUp).
+        ``targets``: the rows' labels where they already are on the device (None: the uploaded ones)."""
         b = i64.numel() // 4
-        targets = i64[2 * b:3 * b]
+        if targets is None:
+            targets = i64[2 * b:3 * b]
+        elif not isinstance(targets, torch.Tensor) or targets.dtype != torch.int64 or tuple(targets.shape) != (b,) \
+                or targets.device != i64.device or not targets.is_contiguous():
+            raise ValueError(f"DeviceDataLoader: targets must be a contiguous int64 tensor of {b} labels on {i64.device}")
         if rows is None:
             if self._cache is None:
                 self._fill_cache()
@@ -685,8 +690,11 @@ class DeviceDataLoader:
             return mixed.unsqueeze(1), soft
         return feats.unsqueeze(1), targets
 
-    def launch_batch(self, indices: Sequence[int], plan: BatchPlan) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Everything of a batch that runs on the device, stream-ordered; nothing here waits for the device."""
+    def launch_batch(self, indices: Sequence[int], plan: BatchPlan,
+                     targets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Everything of a batch that runs on the device, stream-ordered; nothing here waits for the device.
+        ``targets``: a device int64 ``(B,)`` tensor of the rows' labels, used (for MixUp too) instead of the bank's
+        uploaded labels -- for a bank whose labels were made on the device."""
         idx, host_lens, words = self._head(indices)
         b, bank, dev = len(idx), self.bank, self.bank.device
         row_len = int(host_lens.max())
@@ -730,13 +738,15 @@ class DeviceDataLoader:
                     _chain.finish(src, offsets, lens, go.channel, aug.channel, out=src)
             rows = (src, offsets, lens)
         return self._tail(i64, rows, words.view(i32, "masks") if n_masks else None,
-                          (words.view(i32, "coef"), words.view(i32, "perm")) if plan.perm is not None else None)
+                          (words.view(i32, "coef"), words.view(i32, "perm")) if plan.perm is not None else None, targets)
 
-    def launch_batch_drawn(self, indices: Sequence[int], seed: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    def launch_batch_drawn(self, indices: Sequence[int], seed: int,
+                           targets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``launch_batch`` with the batch's draws made on the device under ``seed`` (its records, its masks and its
         gaussian noise) by ``chain.run_drawn``, then ``cough_prepare_rows``, the featuriser, and ``cough_mask_images`` when
         there are masks.  The result equals ``launch_batch(indices, plan)`` for the ``BatchPlan`` that holds the same draws
-        with ``seed`` as its noise seed.  The rows are sized for the slowest speed factor: no draw is read back."""
+        with ``seed`` as its noise seed.  The rows are sized for the slowest speed factor: no draw is read back.
+        ``targets`` as in ``launch_batch``."""
         idx, host_lens, words = self._head(indices)
         b, aug = len(idx), self.audio_augmentor if self._augments else None
         if self._mixes:
@@ -748,7 +758,7 @@ class DeviceDataLoader:
         rows, masks = _chain.run_drawn(seed, self.bank.data, i64[:b], words.view(i32, "lengths"), i64[b:2 * b], row_len, aug,
                                        self.spec_augmentor if self._n_masks else None, self.feature_shape())
         return self._tail(i64, None if self.cache_features else rows, masks,      # cached features: no augmentor ran
-                          (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None)
+                          (words.view(i32, "coef"), words.view(i32, "perm")) if self._mixes else None, targets)
 
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         indices = self.epoch_indices()
